@@ -20,6 +20,12 @@ flush), and p50_first_pcm_ms = dialog_ss -> PCM of the first vocoder chunk known
 Weights: counter-hash synthetic weights at Qwen2-7B / paper geometry (configs/real), generated on
 device; no checkpoint is on the box.  `--gpus N` (N > 1) starts N ranks itself (torch.distributed.run, one rank
 per GPU, RCCL); under an outer torch.distributed.run each process is one rank and --gpus must equal WORLD_SIZE.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds the legs that take runs of their
+own (config-2 single user, live kernel probes, codec-id exact match, CPU baseline; duplex: the probed run); their
+fields are null in a plain line.  --dump-outputs DIR writes what the last timed step handed its caller as
+DIR/<name>.npy (turn_arrays; duplex: each session's state probabilities); the inputs are seeded, so two builds
+run with the same arguments can be compared array by array.
 """
 import argparse
 import ctypes
@@ -95,6 +101,13 @@ def parse():
                     help="Python thread switch interval (s) while the sentence-speech worker runs beside the text "
                          "decode (default: the interpreter's 5 ms)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs the headline figure does not need: the config-2 "
+                         "(1 user) turn, the live gate/up weight-stream probes, the codec-id exact-match check and the "
+                         "CPU baseline (turn); the probed run behind the tick roofline and stage split (duplex).  "
+                         "--no-single-user / --no-cpu-baseline drop single legs of it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--launch-selftest", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args()
 
@@ -195,7 +208,9 @@ class Turn:
         self.pe = 0
 
 
-def run_turn(engine, base_kv, pcms, args, sync):
+def run_turn(engine, base_kv, pcms, args, sync, keep=False):
+    """One step.  keep: also return what the turn handed its caller (the text ids and hidden rows, each sentence's
+    codec ids and PCM segments, still on the device) under "outputs", for dump_outputs."""
     import torch
     B = len(pcms)
     t_begin = time.perf_counter()
@@ -249,7 +264,7 @@ def run_turn(engine, base_kv, pcms, args, sync):
     n_sent = (T + S - 1) // S
     # 400 codec tokens per response (EOS masked until then), dealt over the sentences
     codec_per = [args.codec_tokens // n_sent + (1 if s < args.codec_tokens % n_sent else 0) for s in range(n_sent)]
-    rec = SpeechRecorder(B)
+    rec = SpeechRecorder(B, keep)
     tts = None
     if args.concurrent_tts:
         tts = LaneTTS(engine, args, rec) if args.tts_lane else SentenceTTS(engine, args, rec)
@@ -304,28 +319,34 @@ def run_turn(engine, base_kv, pcms, args, sync):
         stage[f"sentence{k}_wait"] = (rec.sent_start[k] - rec.sentences[k]) * 1e3
         stage[f"sentence{k}_speech"] = (rec.sent_end[k] - rec.sent_start[k]) * 1e3
     return dict(t_ss=t_ss, first=rec.first, last=rec.last, samples=rec.samples, first_pcm=rec.first_pcm,
-                stage=stage, n_sent=n_sent, codec_tokens=rec.codec_tokens)
+                stage=stage, n_sent=n_sent, codec_tokens=rec.codec_tokens,
+                outputs=dict(text_ids=text_ids, hiddens=hiddens, codec_ids=rec.codec_ids, segments=rec.kept) if keep
+                else None)
 
 
 class SpeechRecorder:
     """Per-user timing of the speech of one turn, over all its sentences."""
 
-    def __init__(self, B):
+    def __init__(self, B, keep=False):
+        self.kept = [] if keep else None   # --dump-outputs: (sentence, user, PCM segment) as released, last step only
         self.first = [None] * B        # first PCM segment released by the silence gate
         self.first_pcm = [None] * B    # first vocoder chunk's PCM known on the host (before the gate)
         self.last = [None] * B
         self.samples = [0] * B
         self.codec_tokens = [0] * B
+        self.codec_ids = {}            # (sentence, user) -> the codec ids of that sentence's speech
         self.sentences = []            # host time of each sentence boundary
         self.sent_start = {}           # host time each sentence's speech started / ended (worker side)
         self.sent_end = {}
 
-    def segment(self, i, seg):
+    def segment(self, i, seg, k=0):
         now = time.perf_counter()      # the segment's length is known on the host: the cut index was read back
         if self.first[i] is None:
             self.first[i] = now
         self.last[i] = now
         self.samples[i] += seg.numel()
+        if self.kept is not None:
+            self.kept.append((k, i, seg))
 
 
 def sentence_items(engine, hiddens, ids):
@@ -357,12 +378,13 @@ def run_sentence(engine, args, rec, hiddens, ids, n_codec, k=0, stream=None, voc
         states = []
         for i, seg in speak(engine, items, top_k=args.top_k, min_tokens=n_codec, max_tokens=n_codec,
                             states_out=states, stream=stream, voc_stream=voc):
-            rec.segment(i, seg)
+            rec.segment(i, seg, k)
     rec.sent_end[k] = time.perf_counter()
     for i, st in enumerate(states):
         if rec.first_pcm[i] is None:
             rec.first_pcm[i] = st.t_first_pcm
         rec.codec_tokens[i] += len(st.all_ids)
+        rec.codec_ids[k, i] = st.all_ids
 
 
 class LaneTTS:
@@ -407,13 +429,14 @@ class LaneTTS:
                             return
                         continue
                     for i, seg in lane.pump():
-                        rec.segment(lane.states[i].key, seg)
+                        rec.segment(lane.states[i].key, seg, lane.states[i].tag)
                     for k in lane.done_groups:
                         rec.sent_end[k] = time.perf_counter()
                         for st in (s for s in lane.states if s.tag == k):
                             if rec.first_pcm[st.key] is None:
                                 rec.first_pcm[st.key] = st.t_first_pcm
                             rec.codec_tokens[st.key] += len(st.all_ids)
+                            rec.codec_ids[k, st.key] = st.all_ids
                     lane.done_groups.clear()
             except BaseException as e:  # re-raised in the main thread by join()
                 self.err = e
@@ -544,6 +567,42 @@ def turn_roofline(eng, B, n_chunks, text_tokens, codec_per_sentence, ctx0, bw=8.
     return ms, {"listen_GB": listen_b / 1e9, "listen_stages": stages, "listen_per_chunk_GB": listen_one / 1e9,
                 "text_GB": text_b / 1e9, "speak_GB": speak_b / 1e9,
                 "vocoder_TFLOP": speak_f / 1e12, "kv_fp32_extra_GB": kv_extra / 1e9}
+
+
+def dump_outputs(path, arrays, limit=64 * 10 ** 6):
+    """--dump-outputs: each array as path/<name>.npy, float32 or float64 (ids as float64), at most `limit` bytes in
+    all.  When the arrays exceed the limit, each one larger than an equal share of it is cut to a fixed sample of its
+    flattened elements (sorted indices drawn with seed 0 from the array's size, so two builds keep the same ones)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64)
+              for k, v in arrays.items()}
+    if sum(v.nbytes for v in arrays.values()) > limit:
+        share = limit // len(arrays)
+        for k, v in arrays.items():
+            if v.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).choice(v.size, share // v.itemsize, replace=False))
+                arrays[k] = v.reshape(-1)[idx]
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
+def turn_arrays(out, tag=""):
+    """What the last timed turn handed its caller (run_turn(keep=True)), as host arrays: per user the text ids
+    [B, T] and the LLM hidden rows behind them [B, T, D], the codec ids of every sentence [B, sentences, n] (-1 past a
+    sentence's end) and the PCM the silence gate released, sentence by sentence in emission order (one array a user)."""
+    import torch
+    B = len(out["text_ids"])
+    n_sent = 1 + max(k for k, _ in out["codec_ids"])
+    n = max(len(v) for v in out["codec_ids"].values())
+    codec = np.full((B, n_sent, n), -1.0)
+    for (k, i), ids in out["codec_ids"].items():
+        codec[i, k, :len(ids)] = ids
+    arrays = {"text_ids": np.asarray(out["text_ids"], dtype=np.float64),
+              "text_hidden": torch.stack(out["hiddens"], 1).float().cpu().numpy(), "codec_ids": codec}
+    for i in range(B):
+        segs = [s for k in range(n_sent) for kk, ii, s in out["segments"] if (kk, ii) == (k, i)]
+        arrays[f"pcm_user{i:02d}"] = (torch.cat(segs).float().cpu().numpy() if segs else np.zeros(0, np.float32))
+    return {tag + k: v for k, v in arrays.items()}
 
 
 def codec_ids_check(eng):
@@ -929,10 +988,14 @@ def run_duplex(eng, args, seconds, sync, probe=False):
         account(done)
     sync()
     wall = time.perf_counter() - t_all
+    # what each session's caller saw, prefill by prefill: identity (0 user, 1 system) and the state head's
+    # probabilities (NaN where a prefill returned none) -- dump_outputs
+    decisions = [np.array([[float(ident != "user")] + ([p["state_1"], p["state_2"]] if p else [np.nan, np.nan])
+                           for ident, _, _, p in s.states], dtype=np.float64).reshape(-1, 3) for s in sch.sessions]
     for s in sch.sessions:
         s.release()
     return {"wall": wall, "ticks": ticks, "counts": counts, "audio_s": args.users * n * ch / 16000.0,
-            "stages": stages}
+            "stages": stages, "decisions": decisions}
 
 
 def dist_info(dist, world):
@@ -1000,9 +1063,12 @@ def main_duplex(args, eng, dev, dist, world, rank, load_s):
     if dist is not None:
         dist.barrier()
     runs = [run_duplex(eng, args, args.duplex_sec, sync) for _ in range(args.steps)]
-    # untimed: the same script with the per-tick stage probe (HIP events on the engine stream, host gating timed
-    # apart) -- the split and the tick roofline come from here, the headline numbers from the runs above
-    pr = run_duplex(eng, args, min(args.duplex_sec, 30.0), sync, probe=True)["stages"]
+    if args.dump_outputs and runs:
+        dump_outputs(args.dump_outputs, {f"{'rank%d_' % rank if world > 1 else ''}session{u:02d}_states": d
+                                         for u, d in enumerate(runs[-1]["decisions"])})
+    # --full, untimed: the same script with the per-tick stage probe (HIP events on the engine stream, host gating
+    # timed apart) -- the split and the tick roofline come from here, the headline numbers from the runs above
+    pr = run_duplex(eng, args, min(args.duplex_sec, 30.0), sync, probe=True)["stages"] if args.full else None
     wall = sum(r["wall"] for r in runs)
     audio = sum(r["audio_s"] for r in runs)
     ticks = [t * 1e3 for r in runs for t in r["ticks"]]
@@ -1019,7 +1085,7 @@ def main_duplex(args, eng, dev, dist, world, rank, load_s):
             "metric": "duplex: real-time factor of two-party dialogue audio processed + p50 state-decision latency",
             "value": round(audio / wall, 3),
             "unit": "x real-time (seconds of per-session dialogue per wall second, all sessions)",
-            **topology(world), "steps": args.steps, "warmup": args.warmup,
+            **topology(world), "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(wall / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "bf16w-fp32a",
             "data": "synthetic (counter-hash weights; synthetic 16 kHz PCM for both parties; scripted VAD)",
@@ -1127,12 +1193,15 @@ def main():
         dist.barrier()
     sync()
     t_start = time.perf_counter()
-    stats = [run_turn(eng, base_kv, pcms, args, sync) for _ in range(args.steps)]
+    stats = [run_turn(eng, base_kv, pcms, args, sync, keep=bool(args.dump_outputs) and s == args.steps - 1)
+             for s in range(args.steps)]
     sync()
     if dist is not None:
         dist.barrier()
     sync()
     wall = time.perf_counter() - t_start
+    if args.dump_outputs and stats:
+        dump_outputs(args.dump_outputs, turn_arrays(stats[-1].pop("outputs"), f"rank{rank}_" if world > 1 else ""))
     sr = 24000.0
     audio = sum(sum(s["samples"]) for s in stats) / sr
     lat = [(f - s["t_ss"]) * 1e3 for s in stats for f in s["first_pcm"] if f is not None]
@@ -1140,7 +1209,7 @@ def main():
     rtf_user = [(n / sr) / (l - s["t_ss"]) for s in stats for n, l in zip(s["samples"], s["last"]) if l is not None]
     # config 2 from the same invocation: one user alone on the replica (1 warm-up turn + 1 timed turn)
     single = None
-    if args.users > 1 and not args.no_single_user:
+    if args.full and args.users > 1 and not args.no_single_user:
         run_turn(eng, base_kv, pcms[:1], args, sync)
         sync()
         t1 = time.perf_counter()
@@ -1157,9 +1226,10 @@ def main():
     # `users` rows (k_gemm_xs, 33 steps x 28 layers), ahead of the grouped listen's gate/up (k_gemm_rows at
     # 2 x users x C rows, 8 stages x 28 layers: 6.4 %), which is reported beside it (listen_kernel)
     group_rows = 2 * args.users * args.listen_chunks if args.pipeline else 2 * args.users
-    probe = gemm_probe(eng, args.users)
-    probe_l = gemm_probe(eng, group_rows, down=16 < group_rows <= 64) if group_rows > 16 else None
-    codec_ok, codec_n = codec_ids_check(eng)
+    # (the live probes and the codec-id check are runs of their own: --full)
+    probe = gemm_probe(eng, args.users) if args.full else None
+    probe_l = gemm_probe(eng, group_rows, down=16 < group_rows <= 64) if args.full and group_rows > 16 else None
+    codec_ok, codec_n = codec_ids_check(eng) if args.full else (None, None)
     n_chunks = int(math.ceil(n_samp / 2560))
     roof_ms, roof_units = turn_roofline(eng, args.users, n_chunks, args.text_tokens,
                                         [args.codec_tokens // stats[0]["n_sent"]] * stats[0]["n_sent"], base_kv.length,
@@ -1204,7 +1274,7 @@ def main():
                              "rocprof_avg_launch_us": None if rl_us is None else round(rl_us, 2),
                              "rocprof_calls": rl_calls}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 cpu = cpu_baseline(args.config, args.cpu_threads, args.text_tokens, args.sentence_tokens,
                                    args.codec_tokens)
@@ -1215,7 +1285,7 @@ def main():
             "metric": "real-time factor + p50 first-audio-chunk latency, Qwen2-7B, N users/GPU",
             "value": round(audio / wall, 3),
             "unit": "x real-time (aggregate seconds of 24 kHz speech out per wall second)",
-            **topology(world), "steps": args.steps, "warmup": args.warmup,
+            **topology(world), "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(wall / args.steps * 1e3, 2),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16w-fp32a",
             "data": "synthetic (counter-hash weights at Qwen2-7B + paper geometry; synthetic 16 kHz PCM)",
@@ -1240,19 +1310,22 @@ def main():
             "load_s": round(load_s, 2), "weight_broadcast_s": None if bcast_s is None else round(bcast_s, 3),
             "weight_broadcast_bytes": bcast_bytes, "weights_verified": weights_verified,
             "dist": dist_info(dist, world),
-            "roofline": {"bound": "hbm", "achieved": round(probe["gbps"], 1), "peak": peak, "unit": "GB/s",
-                         "frac": round(probe["gbps"] / peak, 4),
+            # the live figures (achieved, frac, *_per_launch, listen_kernel) come from the --full probes: None without
+            "roofline": {"bound": "hbm", "achieved": probe and round(probe["gbps"], 1), "peak": peak, "unit": "GB/s",
+                         "frac": probe and round(probe["gbps"] / peak, 4),
                          "traffic": None if traffic is None else round(traffic),
                          "traffic_source": traffic_src,
                          "kernel": kname,
-                         "bytes_per_launch": probe["bytes"], "avg_launch_us": round(probe["seconds"] * 1e6, 2),
+                         "bytes_per_launch": probe and probe["bytes"],
+                         "avg_launch_us": probe and round(probe["seconds"] * 1e6, 2),
                          "frac_source": "live: HIP events around every layer's gate/up launch on the engine stream "
                                         "(gemm_probe); rocprof_* = the committed rocprofv3 summary of this command "
                                         "(split-K kernels: the stream kernel alone, its reduce not included)",
                          "listen_kernel": listen_kernel,
                          "rocprof_avg_launch_us": None if rp_us is None else round(rp_us, 2),
                          "rocprof_calls": rp_calls,
-                         "rocprof_frac": None if rp_us is None else round(probe["bytes"] / (rp_us * 1e-6) / 1e9 / peak, 4),
+                         "rocprof_frac": None if rp_us is None or probe is None else
+                         round(probe["bytes"] / (rp_us * 1e-6) / 1e9 / peak, 4),
                          "rocprof_source": rp_src,
                          # the whole turn against its speed of light: Σ over the turn's units of
                          # max(bytes / 8 TB/s, FLOPs / 2.5 PF) vs the measured ms per turn, and each stage vs its

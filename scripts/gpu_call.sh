@@ -4,7 +4,7 @@
 # started after a fault, abort or time-out). Outputs go to gpurun_out/<tag>_*.
 #   tests      pytest -m gpu (PYTEST_K=expr narrows it)
 #   smoke      __graft_entry__.smoke()
-#   bench      the default bench line (cpu_baseline + config-2 leg)      -> <tag>_bench.json
+#   bench      the bench line with --full (cpu_baseline + config-2 leg)  -> <tag>_bench.json
 #   quick      bench without the CPU baseline / config-2 leg, 3 turns    -> <tag>_quick.json
 #   prof       rocprofv3 --kernel-trace --stats of the bench (2 turns)   -> <tag>_prof/
 #   fetch      FETCH_SIZE pass on the dominant kernel                    -> <tag>_pmc/
@@ -12,7 +12,7 @@
 #   tts        rocprofv3 kernel stats of the AR decode step alone        -> <tag>_prof_tts/
 #   text       rocprofv3 kernel stats of the text step alone             -> <tag>_prof_text/
 #   steptrace  per-node timeline of the AR decode step (kernel trace)   -> <tag>_step_timeline.txt
-#   duplex     the config-5 duplex line                                  -> <tag>_duplex.json
+#   duplex     the config-5 duplex line with --full (tick stage split)   -> <tag>_duplex.json
 #   profdup    rocprofv3 kernel trace + stats of a 20 s duplex run       -> <tag>_profdup/, <tag>_profdup_table.txt
 #   profstage  rocprofv3 kernel trace of scripts/llm_stage_time.py (LLM / encoder stage replays) -> <tag>_profstage_table.txt
 #   profgroup  rocprofv3 kernel trace of scripts/group_stage_time.py $GROUP_C (grouped listen stages) -> <tag>_profgroup_table.txt
@@ -43,7 +43,7 @@ for S in "$@"; do
              ${PYTEST_K:+-k "$PYTEST_K"} > ${O}_pytest_gpu.log 2>&1; rc=$?; tail -3 ${O}_pytest_gpu.log ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > ${O}_smoke.log 2>&1
            rc=$?; tail -1 ${O}_smoke.log ;;
-    bench) timeout -k 10 900 python -u bench.py --out ${O}_bench.json > ${O}_bench.log 2>&1; rc=$?
+    bench) timeout -k 10 900 python -u bench.py --full --out ${O}_bench.json > ${O}_bench.log 2>&1; rc=$?
            [ $rc -eq 0 ] && line ${O}_bench.log ;;
     quick) timeout -k 10 400 python -u bench.py --no-cpu-baseline --no-single-user --steps 3 --out ${O}_quick.json \
              > ${O}_quick.log 2>&1; rc=$?; [ $rc -eq 0 ] && line ${O}_quick.log ;;
@@ -72,7 +72,7 @@ for S in "$@"; do
              [ $rc -eq 0 ] && python3 scripts/trace_table.py ${O}_profgroup 60 stage > ${O}_profgroup_table.txt 2>&1; head -62 ${O}_profgroup_table.txt ;;
     text)  (cd /tmp && timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $ROOTD/${O}_prof_text -o text -f csv -- \
              python3 $ROOTD/scripts/text_step_time.py) > ${O}_prof_text.log 2>&1; rc=$? ;;
-    duplex) timeout -k 10 400 python -u bench.py --scenario duplex --out ${O}_duplex.json > ${O}_duplex.log 2>&1; rc=$?
+    duplex) timeout -k 10 400 python -u bench.py --scenario duplex --full --out ${O}_duplex.json > ${O}_duplex.log 2>&1; rc=$?
             [ $rc -eq 0 ] && line ${O}_duplex.log ;;
     rehearsal) FO_DIST_REHEARSAL=1 timeout -k 10 600 python -u bench.py --gpus 2 --steps 1 --warmup 1 --no-cpu-baseline \
              --no-single-user --out ${O}_rehearsal_n2.json > ${O}_rehearsal_n2.log 2>&1; rc=$? ;;

@@ -32,6 +32,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 REF = "/root/reference"
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(HERE))
+from goldenio import load_golden, save_parts  # noqa: E402  (fixtures over 1 MiB are stored in parts)
 from oracle import configs as C  # noqa: E402
 from oracle.weights import synth_param  # noqa: E402
 
@@ -573,7 +575,7 @@ def gold_real_t2(seed=7):
         out[f"{kind}_pe"] = np.array(pes)
         out[f"{kind}_pe0"] = np.array(pe0)
         print(f"T2 encoder {kind}: {n} chunks, enc {out[kind + '_enc'].shape}, adapter {out[kind + '_ada'].shape}")
-    np.savez_compressed(os.path.join(HERE, "real_encoder_t2.npz"), **out)
+    save_parts("real_encoder_t2.npz", out)
 
     idim, odim, args = cfg["decoder_json"]
     m = LLM2TTSCodecAR(idim, odim, argparse.Namespace(**args))
@@ -724,10 +726,10 @@ def gold_real_qwen2(seed=7, n_layers=2, n_sess=8):
         torch.multinomial = orig
     out["sampler_probs"] = sp
     out["sampler_settings"] = np.array(REAL_QWEN2_SETTINGS, np.float64)
-    np.savez_compressed(os.path.join(HERE, "real_qwen2_t2.npz"), **out)
+    parts = save_parts("real_qwen2_t2.npz", out)
     print("real qwen2: kept counts", [[int((sp[r, s] > 0).sum()) for s in range(len(REAL_QWEN2_SETTINGS))]
                                       for r in range(len(rows))],
-          f"fixture {os.path.getsize(os.path.join(HERE, 'real_qwen2_t2.npz')) / 1e6:.2f} MB")
+          f"fixture {sum(os.path.getsize(p) for p in parts) / 1e6:.2f} MB in {len(parts)} parts")
 
 
 # rows per session of the 17..64-row steps after the 128-row prefill (batched over the 8 sessions): M = 32 (4 framing-B
@@ -763,7 +765,7 @@ def gold_real_qwen2_mid(seed=7, n_layers=2, n_sess=8):
     head = torch.nn.Linear(D, 4)
     init_module(head, seed, "predictor_head.", cfg["overrides"])
     obj = types.SimpleNamespace(llm_decoder=m, predictor_head=head)
-    base = np.load(os.path.join(HERE, "real_qwen2_t2.npz"))
+    base = load_golden("real_qwen2_t2.npz")
     rows0 = base["rows0"].tolist()
     emb0 = base["emb0"]
     cols = np.sort(np.random.default_rng(77).choice(D, 1024, replace=False))
@@ -808,8 +810,8 @@ def gold_real_qwen2_mid(seed=7, n_layers=2, n_sess=8):
             v = per[s]
             out[f"{k}{s}"] = np.concatenate(v) if k in ("hcols", "hsum", "hsq") else np.array(v)
     out["input_sum"] = np.array(insum)
-    np.savez_compressed(os.path.join(HERE, "real_qwen2_mid_t2.npz"), **out)
-    print(f"real qwen2 mid: fixture {os.path.getsize(os.path.join(HERE, 'real_qwen2_mid_t2.npz')) / 1e6:.2f} MB, "
+    parts = save_parts("real_qwen2_mid_t2.npz", out)
+    print(f"real qwen2 mid: fixture {sum(os.path.getsize(p) for p in parts) / 1e6:.2f} MB in {len(parts)} parts, "
           f"input sum {insum:.6f}")
 
 

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from goldenio import load_golden
 from oracle import configs
 from oracle.weights import synth_param
 
@@ -61,7 +62,7 @@ def test_speech_encoder_reference_constructor_matches_golden(dev):
     sd = _state(enc, cfg["seed"], "encoder_user.")   # the golden's global_cmvn buffers are hashed too (init_module)
     r = enc.load_state_dict(sd)
     assert not r.missing_keys and not r.unexpected_keys
-    g = np.load(os.path.join(G, "real_encoder_t2.npz"))
+    g = load_golden("real_encoder_t2.npz")
     buf, pe = None, int(g["A_pe0"])
     for i in range(g["A_feats"].shape[0]):
         o, buf, _, _, pe = enc.infer(torch.from_numpy(g["A_feats"][i]).unsqueeze(0), buf, 0, None, pe)

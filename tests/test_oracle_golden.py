@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+from goldenio import load_golden
 from oracle import audio, configs, host, nets
 from oracle.params import audiollm_shapes, codec_shapes, llm_shapes, tts_shapes
 from oracle.weights import SynthCheckpoint, bf16_round, hash_uniform
@@ -15,7 +16,7 @@ CFG = configs.get("tiny")
 
 
 def load(name):
-    return np.load(os.path.join(G, name))
+    return load_golden(name)   # one .npz, or its parts (goldenio)
 
 
 @pytest.fixture(scope="module")

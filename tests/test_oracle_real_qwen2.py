@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+from goldenio import load_golden
 from oracle import configs, nets
 from oracle.params import all_shapes
 from oracle.weights import SynthCheckpoint, synth_rows
@@ -19,7 +20,7 @@ G = os.path.join(os.path.dirname(__file__), "golden")
 
 @pytest.mark.slow
 def test_oracle_qwen2_real_geometry_matches_reference():
-    g = np.load(os.path.join(G, "real_qwen2_t2.npz"))
+    g = load_golden("real_qwen2_t2.npz")
     cfg = configs.get("real")
     cfg["llm"]["num_hidden_layers"] = 2
     shapes = all_shapes(cfg)

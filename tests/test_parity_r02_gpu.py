@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+from goldenio import load_golden
 from oracle import configs
 from oracle.params import adapter_shapes, codec_shapes, encoder_shapes, tts_shapes
 
@@ -30,7 +31,7 @@ CFG = configs.get("tiny")
 
 
 def load(n):
-    return np.load(os.path.join(G, n))
+    return load_golden(n)   # one .npz, or its parts (goldenio)
 
 
 def close(a, b, rtol=2e-3, atol=2e-4):

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+from goldenio import load_golden
 from refdir import make_reference_dir_real
 from test_real_qwen2_gpu import check_llm_against_golden
 
@@ -40,12 +41,12 @@ def eng(dev, tmp_path_factory):
 
 
 def test_qwen2_from_sharded_safetensors_matches_reference(dev, eng):
-    check_llm_against_golden(eng.llm, dev, np.load(os.path.join(G, "real_qwen2_t2.npz")))
+    check_llm_against_golden(eng.llm, dev, load_golden("real_qwen2_t2.npz"))
 
 
 @pytest.mark.parametrize("ident", ["user", "system"])
 def test_encoder_adapter_from_upstream_names_match_reference(dev, eng, ident):
-    g = np.load(os.path.join(G, "real_encoder_t2.npz"))
+    g = load_golden("real_encoder_t2.npz")
     enc, ada = eng.enc[ident], eng.ada[ident]
     for kind in ("A", "B"):
         ec, ac, pe = enc.new_cache(), ada.new_cache(), int(g[f"{kind}_pe0"])

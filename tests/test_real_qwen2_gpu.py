@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 
+from goldenio import load_golden
 from oracle import configs
 from oracle.params import all_shapes
 
@@ -29,7 +30,7 @@ G = os.path.join(os.path.dirname(__file__), "golden")
 
 @pytest.fixture(scope="module")
 def gold():
-    return np.load(os.path.join(G, "real_qwen2_t2.npz"))
+    return load_golden("real_qwen2_t2.npz")
 
 
 @pytest.fixture(scope="module")
@@ -163,7 +164,7 @@ def test_qwen2_real_geometry_17_to_64_row_steps_match_reference(dev, llm, gold):
     1e-4), state probs 5e-4, logits 1e-3 abs + 1e-3 rel; greedy ids equal where the reference's top-2 margin
     exceeds 2e-3 (otherwise within its top 2)."""
     from fo import _lib, ops
-    mid = np.load(os.path.join(G, "real_qwen2_mid_t2.npz"))
+    mid = load_golden("real_qwen2_mid_t2.npz")
     lib = _lib.load()
     assert lib.fo_gemm_set_pipe(3) >= -1
     B, D = 8, llm.D
