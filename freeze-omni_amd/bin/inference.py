@@ -48,6 +48,8 @@ def get_args(argv=None):
     p.add_argument("--input_wav", required=True, help="input wav")
     p.add_argument("--output_wav", required=True, help="output wav")
     p.add_argument("--device", default="cuda:0")
+    p.add_argument("--llm_mlp_weights", choices=["bf16", "fp8"], default="bf16",
+                   help="Qwen2 gate/up/down weights: bf16, or weight-only FP8 (e4m3 codes x a power of two per row)")
     p.add_argument("--role", default="You are a helpful assistant.")
     p.add_argument("--max_text_tokens", type=int, default=MAX_TEXT_TOKENS)
     args = p.parse_args(argv)

@@ -1,0 +1,569 @@
+// Weight-only FP8 (OCP e4m3fn) GEMMs for the Qwen2 MLP at <= 16 activation rows, and their quantiser.
+//
+//   W'[n, k] = q[n, k] * 2^e[n]      q an e4m3fn code, e[n] one integer per output row (stored as the fp32 2^e[n])
+//   Y[M, N]  = epilogue( X[M, K] (fp32, split into bf16 hi + lo) . W'^T )
+//
+// An e4m3 value has at most 4 significant bits, so q * 2^e is exactly a bf16 value: W' has an exact bf16 image, which
+// the engine keeps packed for the bf16 kernels (every launch above 16 rows).  The kernels here stream the codes --
+// half the bytes of that image -- decode them to bf16 in registers (exact) and run the same bf16 MFMAs; the column
+// scale multiplies the fp32 sum once per output element, before anything else in the epilogue, so both paths compute
+// X . W'^T to the accumulation-order difference that already exists between the bf16 kernels.
+//
+// Code layout (include/fo_hip.h): [tile][K64][64 lanes][16 codes], a lane's 16 bytes being its 8-element MFMA
+// B-fragments of two consecutive 32-column k-steps, K padded to a multiple of 64 with zero codes.
+//  * k_w8: the general form, any K % 32 == 0; one workgroup per output tile (per gate/up pair), its waves split K and
+//    reduce through LDS in wave order.
+//  * k_w8_xs: the SwiGLU pair at K = 3584, X-stationary and persistent as k_gemm_xs (fo_gemm.hip): X hi in registers,
+//    lo in LDS, units dealt evenly to at most one workgroup per CU, the next unit's codes issued before the current
+//    one is reduced, a fixed-order cross-wave reduction.
+//  * k_w8_sk: long-K plain projections (the down, K = 18944): 4 tiles per workgroup share each X fragment's load and
+//    hi / lo split, and K is split across workgroups to fill the chip.  The splits merge inside the launch, in this
+//    file: each stores its partial tiles write-through and takes the tile group's ticket; the split that arrives
+//    last sums every partial in split order (so the bits do not depend on which one that is) and runs the epilogue.
+// Results are deterministic in every form.
+#include <stdlib.h>
+
+#include "fo_common.h"
+
+namespace {
+
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+
+struct W8Args {
+  const float* X;
+  const void* Q;       // codes in packed order
+  const float* scale;  // [ntiles][16], packed tile order
+  float* Y;
+  int ldx, ldy;
+  int M, K, N;         // N: logical output columns (after SwiGLU pairing)
+  int ntiles;          // packed 16-column tiles in Q
+  int KK;              // 64-column code steps per tile: ceil(K / 64)
+  int residual;
+  // the RMSNorm split across two GEMMs, as fo_gemm_rms (fo_gemm.hip GemmArgs)
+  float* sout;
+  const float* gnext;
+  float* yg;
+  const float* rstats;
+  int rgroups;
+  float reps;
+};
+
+// 8 e4m3fn codes (two dwords) -> 8 bf16: v_cvt_pk_f32_fp8 per code pair, then the upper halves of the two floats in
+// one v_perm (an e4m3 value has 4 significant bits: the truncation is exact)
+__device__ __forceinline__ bf16x8 dec8(unsigned a, unsigned b) {
+  const f32x2 f0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a, false), f1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a, true);
+  const f32x2 f2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)b, false), f3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)b, true);
+  u32x4 r;
+  r[0] = __builtin_amdgcn_perm(__float_as_uint(f0[1]), __float_as_uint(f0[0]), 0x07060302u);
+  r[1] = __builtin_amdgcn_perm(__float_as_uint(f1[1]), __float_as_uint(f1[0]), 0x07060302u);
+  r[2] = __builtin_amdgcn_perm(__float_as_uint(f2[1]), __float_as_uint(f2[0]), 0x07060302u);
+  r[3] = __builtin_amdgcn_perm(__float_as_uint(f3[1]), __float_as_uint(f3[0]), 0x07060302u);
+  return __builtin_bit_cast(bf16x8, r);
+}
+
+__device__ __forceinline__ void split8(const float4 p0, const float4 p1, bf16x8& hi, bf16x8& lo) {
+  const float f[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const __bf16 h = (__bf16)f[i];
+    hi[i] = h;
+    lo[i] = (__bf16)(f[i] - (float)h);
+  }
+}
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t code_rsrc(const W8Args& a) {
+  // the descriptor covers exactly the codes (ntiles * KK KiB): a load of "tile ntiles" is out of range and dropped
+  const unsigned long long b = (unsigned long long)a.Q;
+  return __builtin_amdgcn_make_buffer_rsrc(
+      reinterpret_cast<void*>(((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(b >> 32)) << 32) |
+                              (unsigned)__builtin_amdgcn_readfirstlane((unsigned)b)),
+      (short)0, __builtin_amdgcn_readfirstlane(a.ntiles * a.KK * 1024), 0x00020000);
+}
+
+// Output element (row rr, column c) of unit u, thread e = 16 rr + c of the first 256: x1 / x2 are the fp32 sums of
+// the unit's (gate, up) tiles (SW) or of its one tile.  The column scale first, then the consumer's rstd, SwiGLU,
+// the residual and the store; a producer also writes yg = y * gamma_next and the row's sum of squares over the
+// unit's 16 columns.  Rows >= M (computed from a clamped row) are neither stored nor summed.
+template <bool SW>
+__device__ __forceinline__ void w8_epilogue(const W8Args& a, int u, int groups, int rr, int c, float x1, float x2,
+                                            const float* rstd_s) {
+  const int n = u * 16 + c;
+  const bool live = rr < a.M && n < a.N;
+  float y = 0.f;
+  if (live) {
+    if constexpr (SW) {
+      x1 *= a.scale[(2 * u) * 16 + c];
+      x2 *= a.scale[(2 * u + 1) * 16 + c];
+    } else {
+      x1 *= a.scale[n];
+    }
+    if (a.rstats) {
+      x1 *= rstd_s[rr];
+      x2 *= rstd_s[rr];
+    }
+    y = SW ? x1 / (1.f + expf(-x1)) * x2 : x1;
+    const size_t o = (size_t)rr * a.ldy + n;
+    if (a.residual) y += a.Y[o];
+    a.Y[o] = y;
+    if (a.yg) a.yg[o] = y * a.gnext[n];
+  }
+  if constexpr (!SW) {
+    if (a.sout) {   // (uniform; the row's 16 columns are one 16-lane row of the wave)
+      float sq = y * y;
+      sq += lane_xor<8>(sq);
+      sq += lane_xor<4>(sq);
+      sq += lane_xor<2>(sq);
+      sq += lane_xor<1>(sq);
+      if (c == 0 && rr < a.M) a.sout[(size_t)rr * groups + u] = sq;
+    }
+  }
+}
+
+template <int NW>
+__device__ __forceinline__ void w8_rstd(const W8Args& a, float* rstd_s, int wave, int lane) {
+  for (int rr = wave; rr < 16; rr += NW) {
+    const int m = min(rr, a.M - 1);
+    float v = 0.f;
+    for (int j = lane; j < a.rgroups; j += 64) v += a.rstats[(size_t)m * a.rgroups + j];
+    v = wave_sum(v);
+    if (lane == 0) rstd_s[rr] = rsqrtf(v / (float)a.K + a.reps);
+  }
+}
+
+// ---- general form: workgroup u = output tile u (SW: the (gate, up) pair 2u, 2u + 1); wave w takes the code steps
+// [KK w / NW, KK (w + 1) / NW), U of them (per tile) in flight
+template <int NW, bool SW>
+__global__ __launch_bounds__(NW * 64) void k_w8(W8Args a) {
+  constexpr int T = SW ? 2 : 1, U = SW ? 2 : 4;   // (4 pair steps spill at 16 waves' 128 VGPRs)
+  __shared__ float part[NW][T][16][17];
+  __shared__ float rstd_s[16];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int u = blockIdx.x;
+  const __amdgpu_buffer_rsrc_t srd = code_rsrc(a);
+  const int kb = (int)((long)a.KK * wave / NW), ke = (int)((long)a.KK * (wave + 1) / NW);
+  const int row = min(lane & 15, a.M - 1);
+  const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
+  const int voff = lane * 16;
+  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
+  f32x4 acc[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int k0 = kb; k0 < ke; k0 += U) {
+    u32x4 q[U][T];
+    float4 x[U][4];
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+      const int kk = k0 + i;
+      if (kk < ke) {
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+          q[i][t] = __builtin_bit_cast(
+              u32x4, __builtin_amdgcn_raw_buffer_load_b128(srd, voff, ((T * u + t) * a.KK + kk) * 1024, 2));
+        const float* p = xp + (size_t)kk * 64;
+        x[i][0] = reinterpret_cast<const float4*>(p)[0];
+        x[i][1] = reinterpret_cast<const float4*>(p)[1];
+        if (kk * 64 + 32 < a.K) {   // (K % 64 == 32: the last step's second half is zero codes and no X)
+          x[i][2] = reinterpret_cast<const float4*>(p + 32)[0];
+          x[i][3] = reinterpret_cast<const float4*>(p + 32)[1];
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+      const int kk = k0 + i;
+      if (kk < ke) {
+        bf16x8 hi, lo;
+        split8(x[i][0], x[i][1], hi, lo);
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+          const bf16x8 w = dec8(q[i][t][0], q[i][t][1]);
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hi, w, acc[t], 0, 0, 0);
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lo, w, acc[t], 0, 0, 0);
+        }
+        if (kk * 64 + 32 < a.K) {
+          split8(x[i][2], x[i][3], hi, lo);
+#pragma unroll
+          for (int t = 0; t < T; ++t) {
+            const bf16x8 w = dec8(q[i][t][2], q[i][t][3]);
+            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hi, w, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lo, w, acc[t], 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < T; ++t)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) part[wave][t][4 * (lane >> 4) + i][lane & 15] = acc[t][i];
+  __syncthreads();
+  const int e = threadIdx.x;
+  if (e < 256) {
+    const int rr = e >> 4, c = e & 15;
+    float x1 = 0.f, x2 = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      x1 += part[w][0][rr][c];
+      if constexpr (SW) x2 += part[w][1][rr][c];
+    }
+    w8_epilogue<SW>(a, u, gridDim.x, rr, c, x1, x2, rstd_s);
+  }
+}
+
+// ---- long-K plain form: workgroup (tg, sp) = tiles NT tg .. + NT over the sp-th of S slices of the code steps, the
+// slice split over the waves as in k_w8.  ws: S slabs of [16][groups * NT * 16] partial sums; counters: one zeroed
+// ticket per tile group, left zeroed.  The hand-off is fo_common.h's (st_wt / ld_sc1): no fences, no waiting.
+template <int NW, int NT>
+__global__ __launch_bounds__(NW * 64) void k_w8_sk(W8Args a, int S, float* ws, int* counters) {
+  constexpr int U = 2;
+  __shared__ float part[NW][NT][16][17];
+  __shared__ float red[NT][16][17];
+  __shared__ float rstd_s[16];
+  __shared__ int last_s;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int tg = blockIdx.x, sp = blockIdx.y;
+  const __amdgpu_buffer_rsrc_t srd = code_rsrc(a);
+  const int k_lo = (int)((long)a.KK * sp / S), k_n = (int)((long)a.KK * (sp + 1) / S) - k_lo;
+  const int kb = k_lo + (int)((long)k_n * wave / NW), ke = k_lo + (int)((long)k_n * (wave + 1) / NW);
+  const int row = min(lane & 15, a.M - 1);
+  const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
+  const int voff = lane * 16;
+  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
+  f32x4 acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int k0 = kb; k0 < ke; k0 += U) {
+    u32x4 q[U][NT];
+    float4 x[U][4];
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+      const int kk = k0 + i;
+      if (kk < ke) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t)   // (a tile past ntiles is out of the descriptor's range: zero codes)
+          q[i][t] = __builtin_bit_cast(
+              u32x4, __builtin_amdgcn_raw_buffer_load_b128(srd, voff, ((NT * tg + t) * a.KK + kk) * 1024, 2));
+        const float* p = xp + (size_t)kk * 64;
+        x[i][0] = reinterpret_cast<const float4*>(p)[0];
+        x[i][1] = reinterpret_cast<const float4*>(p)[1];
+        if (kk * 64 + 32 < a.K) {
+          x[i][2] = reinterpret_cast<const float4*>(p + 32)[0];
+          x[i][3] = reinterpret_cast<const float4*>(p + 32)[1];
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+      const int kk = k0 + i;
+      if (kk < ke) {
+        bf16x8 hi, lo;
+        split8(x[i][0], x[i][1], hi, lo);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          const bf16x8 w = dec8(q[i][t][0], q[i][t][1]);
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hi, w, acc[t], 0, 0, 0);
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lo, w, acc[t], 0, 0, 0);
+        }
+        if (kk * 64 + 32 < a.K) {
+          split8(x[i][2], x[i][3], hi, lo);
+#pragma unroll
+          for (int t = 0; t < NT; ++t) {
+            const bf16x8 w = dec8(q[i][t][2], q[i][t][3]);
+            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hi, w, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lo, w, acc[t], 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) part[wave][t][4 * (lane >> 4) + i][lane & 15] = acc[t][i];
+  __syncthreads();
+  constexpr int NE = NT * 256, NTH = NW * 64;
+  for (int e = threadIdx.x; e < NE; e += NTH) {
+    const int t = e >> 8, rr = (e >> 4) & 15, c = e & 15;
+    float v = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) v += part[w][t][rr][c];
+    red[t][rr][c] = v;
+  }
+  if (S > 1) {
+    const int Ncols = gridDim.x * NT * 16;
+    const size_t sl = (size_t)16 * Ncols;
+    float* slab = ws + (size_t)sp * sl;
+    for (int e = threadIdx.x; e < NE; e += NTH) {   // (each thread stores the elements it just summed)
+      const int t = e >> 8, rr = (e >> 4) & 15, c = e & 15;
+      st_wt(slab + (size_t)rr * Ncols + (tg * NT + t) * 16 + c, red[t][rr][c]);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int* tk = counters + tg;
+      const int old = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      last_s = old == S - 1;
+      if (old == S - 1) __hip_atomic_store(tk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (!last_s) return;
+    // the last split to arrive: every split's partial, summed in split order
+    const __amdgpu_buffer_rsrc_t rws = rsrc_of(ws);
+    for (int e = threadIdx.x; e < NE; e += NTH) {
+      const int t = e >> 8, rr = (e >> 4) & 15, c = e & 15;
+      const size_t o = (size_t)rr * Ncols + (tg * NT + t) * 16 + c;
+      const float own = red[t][rr][c];
+      float v = 0.f;
+      for (int q0 = 0; q0 < S; ++q0) v += q0 != sp ? ld_sc1(rws, q0 * sl + o) : own;
+      red[t][rr][c] = v;
+    }
+  }
+  __syncthreads();
+  const int units = (a.N + 15) / 16;
+  if (threadIdx.x < 256) {
+    const int rr = threadIdx.x >> 4, c = threadIdx.x & 15;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      if (tg * NT + t < units) w8_epilogue<false>(a, tg * NT + t, units, rr, c, red[t][rr][c], 0.f, rstd_s);
+  }
+}
+
+// ---- X-stationary persistent form: the SwiGLU pair, K = NW * KPW * 64 (3584 = 56 code steps)
+template <int NW, int KPW>
+__global__ __launch_bounds__(NW * 64) void k_w8_xs(W8Args a, int units) {
+  __shared__ bf16x8 xlo[NW][2 * KPW][64];
+  __shared__ float part[NW][2][16][17];
+  __shared__ float rstd_s[16];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  constexpr int KK = NW * KPW;
+  const int ub = (int)((long)units * blockIdx.x / gridDim.x);
+  const int ue = (int)((long)units * (blockIdx.x + 1) / gridDim.x);
+  const __amdgpu_buffer_rsrc_t srd = code_rsrc(a);
+  const int voff = (wave * KPW * 64 + lane) * 16;
+  u32x4 q0[KPW], q1[KPW];
+  auto issue = [&](u32x4 (&q)[KPW], int tile) {
+#pragma unroll
+    for (int j = 0; j < KPW; ++j)
+      q[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(srd, voff, (tile * KK + j) * 1024, 2));
+  };
+  issue(q0, ub < ue ? 2 * ub : a.ntiles);
+  issue(q1, ub < ue ? 2 * ub + 1 : a.ntiles);
+  // X slice (hi in registers, lo in LDS); rows >= M clamp to the last row (computed, never stored)
+  bf16x8 xh[2 * KPW];
+  {
+    const int row = min(lane & 15, a.M - 1);
+    const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4) + (size_t)wave * KPW * 64;
+#pragma unroll
+    for (int j = 0; j < 2 * KPW; ++j) {
+      bf16x8 lo;
+      split8(reinterpret_cast<const float4*>(xp + j * 32)[0], reinterpret_cast<const float4*>(xp + j * 32)[1], xh[j],
+             lo);
+      xlo[wave][j][lane] = lo;
+    }
+  }
+  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
+  auto compute = [&](u32x4 (&q)[KPW]) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < KPW; ++j) {
+      const bf16x8 w0 = dec8(q[j][0], q[j][1]), w1 = dec8(q[j][2], q[j][3]);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[2 * j], w0, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xlo[wave][2 * j][lane], w0, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[2 * j + 1], w1, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xlo[wave][2 * j + 1][lane], w1, acc, 0, 0, 0);
+    }
+    return acc;
+  };
+  for (int u = ub; u < ue; ++u) {
+    // the next unit's codes are issued unconditionally; past the last unit they address tile `ntiles`, beyond the
+    // descriptor's range (code_rsrc), which the hardware drops without touching memory
+    const int nxt = u + 1 < ue ? 2 * (u + 1) : a.ntiles;
+    const f32x4 c0 = compute(q0);
+    issue(q0, nxt);
+    const f32x4 c1 = compute(q1);
+    issue(q1, nxt + (u + 1 < ue ? 1 : 0));
+    __syncthreads();  // the previous unit's epilogue has read part[]
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      part[wave][0][4 * (lane >> 4) + i][lane & 15] = c0[i];
+      part[wave][1][4 * (lane >> 4) + i][lane & 15] = c1[i];
+    }
+    __syncthreads();
+    const int e = threadIdx.x;
+    if (e < 256) {
+      const int rr = e >> 4, c = e & 15;
+      float x1 = 0.f, x2 = 0.f;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) {
+        x1 += part[w][0][rr][c];
+        x2 += part[w][1][rr][c];
+      }
+      w8_epilogue<true>(a, u, 0, rr, c, x1, x2, rstd_s);
+    }
+  }
+}
+
+// ---- quantiser.  One workgroup per source row n: the row's amax, e[n] from its exponent and mantissa (the smallest
+// integer with amax * 2^-e <= 448 = 1.75 * 2^8), then 8 consecutive columns per thread: W * 2^-e (exact) rounded to
+// nearest-even e4m3fn by v_cvt_pk_fp8_f32, the 8 codes to their fragment position and the 8 dequantised bf16 values
+// to wdq.  Rows N .. 16 ceil(N / 16) of the last tile get zero codes and scale 1.
+__global__ __launch_bounds__(256) void k_quant_w8(const void* W, int src_bf16, int N, int K, int ldw, unsigned char* q,
+                                                  float* scale, bf16_t* wdq, int KK, int tile_base, int tile_stride) {
+  __shared__ float red[4];
+  const int n = blockIdx.x;
+  const int lane = threadIdx.x & 63;
+  auto at = [&](int k) {
+    return src_bf16 ? bf2f(reinterpret_cast<const bf16_t*>(W)[(size_t)n * ldw + k])
+                    : reinterpret_cast<const float*>(W)[(size_t)n * ldw + k];
+  };
+  float amax = 0.f;
+  if (n < N)
+    for (int k = threadIdx.x; k < K; k += 256) amax = fmaxf(amax, fabsf(at(k)));
+  amax = wave_max(amax);
+  if (lane == 0) red[threadIdx.x >> 6] = amax;
+  __syncthreads();
+  amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  int e = 0;
+  if (amax > 0.f) {
+    const unsigned b = __float_as_uint(amax);
+    e = (int)(b >> 23) - 127 - 8 + ((b & 0x7fffffu) > 0x600000u ? 1 : 0);
+    e = max(e, -126);   // 2^e and 2^-e stay normal floats
+  }
+  const float s = __uint_as_float((unsigned)(e + 127) << 23), inv = __uint_as_float((unsigned)(127 - e) << 23);
+  const size_t dt = (size_t)tile_base + (size_t)(n >> 4) * tile_stride;
+  if (threadIdx.x == 0) scale[dt * 16 + (n & 15)] = s;
+  for (int g = threadIdx.x; g < KK * 8; g += 256) {   // group g: columns 8 g .. + 8
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int k = 8 * g + j;
+      v[j] = (n < N && k < K) ? at(k) * inv : 0.f;
+    }
+    int c0 = 0, c1 = 0;
+    c0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], c0, false);
+    c0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], c0, true);
+    c1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], c1, false);
+    c1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], c1, true);
+    // column k of row n: code step k / 64, lane 16 (k % 32 / 8) + n % 16, byte 8 (k % 64 / 32) + k % 8
+    const int kk = g >> 3, half = (g >> 2) & 1, l = ((g & 3) << 4) + (n & 15);
+    *reinterpret_cast<uint2*>(q + ((dt * KK + kk) * 64 + l) * 16 + 8 * half) = make_uint2((unsigned)c0, (unsigned)c1);
+    if (wdq && n < N) {
+      const bf16x8 d = dec8((unsigned)c0, (unsigned)c1);
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (8 * g + j < K) wdq[(size_t)n * K + 8 * g + j] = f2bf((float)d[j] * s);
+    }
+  }
+}
+
+int g_cus = 0;
+int w8_cus() {
+  if (!g_cus) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    g_cus = n;
+  }
+  return g_cus;
+}
+
+}  // namespace
+
+extern "C" {
+
+long long fo_quant_w8_bytes(int N, int K) { return (long long)((N + 15) / 16) * ((K + 63) / 64) * 1024; }
+
+int fo_quant_w8(const void* W, int src_bf16, int N, int K, int ldw, void* q, float* scale, void* wdq, int tile_base,
+                int tile_stride, hipStream_t stream) {
+  FO_REQUIRE(W && q && scale, "fo_quant_w8: NULL W, q or scale");
+  FO_REQUIRE(N > 0 && K > 0 && ldw >= K, "fo_quant_w8: bad shape N=%d K=%d ldw=%d", N, K, ldw);
+  FO_REQUIRE(tile_base >= 0 && tile_stride >= 1, "fo_quant_w8: bad tile_base=%d tile_stride=%d", tile_base,
+             tile_stride);
+  const int nt = (N + 15) / 16;
+  hipLaunchKernelGGL(k_quant_w8, dim3(nt * 16), dim3(256), 0, stream, W, src_bf16, N, K, ldw, (unsigned char*)q, scale,
+                     (bf16_t*)wdq, (K + 63) / 64, tile_base, tile_stride);
+  return fo::check_launch("fo_quant_w8");
+}
+
+int fo_gemm_w8(const float* X, int ldx, int M, int K, const void* Q, const float* scale, int ntiles, int N, int swiglu,
+               float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters, const float* rstats,
+               int rgroups, float eps, float* sout, const float* gnext, float* yg, int* sgroups, hipStream_t stream) {
+  FO_REQUIRE(M > 0 && N > 0 && K > 0, "fo_gemm_w8: bad shape M=%d N=%d K=%d", M, N, K);
+  FO_REQUIRE(M <= 16, "fo_gemm_w8: M=%d rows, the FP8 stream serves M <= 16 (more rows run the bf16 image)", M);
+  FO_REQUIRE((K & 31) == 0, "fo_gemm_w8: K=%d must be a multiple of 32", K);
+  FO_REQUIRE(X && Q && Y, "fo_gemm_w8: NULL X, Q or Y");
+  FO_REQUIRE(scale, "fo_gemm_w8: NULL scale (the per-column 2^e of fo_quant_w8)");
+  FO_REQUIRE(ldx >= K && (ldx & 3) == 0 && ((unsigned long long)X & 15) == 0,
+             "fo_gemm_w8: X needs ldx=%d >= K=%d, ldx %% 4 == 0 and 16-byte alignment", ldx, K);
+  FO_REQUIRE(ldy >= N, "fo_gemm_w8: ldy=%d < N=%d", ldy, N);
+  const int units = (N + 15) / 16;
+  // ntiles is the extent of Q and scale (the code descriptor's range): (gate, up) pairs for SwiGLU
+  FO_REQUIRE(!swiglu || (ntiles & 1) == 0, "fo_gemm_w8: swiglu with an odd ntiles=%d (gate/up tiles come in pairs)",
+             ntiles);
+  FO_REQUIRE(ntiles == (swiglu ? 2 : 1) * units, "fo_gemm_w8: ntiles=%d packed tiles for N=%d%s", ntiles, N,
+             swiglu ? " SwiGLU columns" : " columns");
+  FO_REQUIRE(!rstats || rgroups > 0, "fo_gemm_w8: rstats without rgroups");
+  FO_REQUIRE(!sout || (!swiglu && (!yg || gnext)), "fo_gemm_w8: sout needs a non-SwiGLU launch, yg needs gnext");
+  FO_REQUIRE(sout || !yg, "fo_gemm_w8: yg comes with sout");
+  FO_REQUIRE(!(swiglu && residual), "fo_gemm_w8: swiglu with residual unsupported");
+  const int KK = (K + 63) / 64;
+  FO_REQUIRE((long long)(ntiles + 4) * KK * 1024 < (1ll << 31), "fo_gemm_w8: ntiles=%d x K=%d codes exceed 2 GiB", ntiles, K);
+  W8Args a;
+  a.X = X;
+  a.Q = Q;
+  a.scale = scale;
+  a.Y = Y;
+  a.ldx = ldx;
+  a.ldy = ldy;
+  a.M = M;
+  a.K = K;
+  a.N = N;
+  a.ntiles = ntiles;
+  a.KK = KK;
+  a.residual = residual;
+  a.sout = sout;
+  a.gnext = gnext;
+  a.yg = yg;
+  a.rstats = rstats;
+  a.rgroups = rgroups;
+  a.reps = eps;
+  if (sgroups) *sgroups = units;
+  if (swiglu && K == 3584) {
+    const int G = units < w8_cus() ? units : w8_cus();
+    // 14 waves x 4 code steps (25.4 / 28.5 us at 8 / 16 rows against 27.0 / 29.4 for 8 x 7, which FO_W8_XS=8 runs:
+    // A/B only)
+    static const bool w8 = [] { const char* e = getenv("FO_W8_XS"); return e && atoi(e) == 8; }();
+    if (w8) hipLaunchKernelGGL((k_w8_xs<8, 7>), dim3(G), dim3(512), 0, stream, a, units);
+    else hipLaunchKernelGGL((k_w8_xs<14, 4>), dim3(G), dim3(896), 0, stream, a, units);
+    fo::count_launch(FO_L_GEMM_W8_XS);
+    return fo::check_launch("fo_gemm_w8 (xs)");
+  }
+  // long-K plain projections (the Qwen2 down: 224 tiles x 296 code steps): 4 tiles per workgroup, K split over the
+  // workgroups until the grid is about one workgroup per CU, merged in the launch (needs the caller's workspace and
+  // zeroed tickets; without them the one-tile form below serves)
+  if (!swiglu && KK >= 128 && units >= 16 && ws && counters) {
+    constexpr int NT = 4, NW = 8;
+    const int groups = (units + NT - 1) / NT;
+    int S = w8_cus() / groups;
+    S = S < 1 ? 1 : (S > 8 ? 8 : S);
+    if (S == 1 || ((long long)S * 16 * groups * NT * 16 <= ws_floats && groups <= (1 << 20))) {
+      hipLaunchKernelGGL((k_w8_sk<NW, NT>), dim3(groups, S), dim3(NW * 64), 0, stream, a, S, ws, counters);
+      fo::count_launch(FO_L_GEMM_W8);
+      return fo::check_launch("fo_gemm_w8 (split K)");
+    }
+  }
+  const bool wide = KK >= 32;
+  if (swiglu) {
+    if (wide) hipLaunchKernelGGL((k_w8<16, true>), dim3(units), dim3(1024), 0, stream, a);
+    else hipLaunchKernelGGL((k_w8<4, true>), dim3(units), dim3(256), 0, stream, a);
+  } else {
+    if (wide) hipLaunchKernelGGL((k_w8<16, false>), dim3(units), dim3(1024), 0, stream, a);
+    else hipLaunchKernelGGL((k_w8<4, false>), dim3(units), dim3(256), 0, stream, a);
+  }
+  fo::count_launch(FO_L_GEMM_W8);
+  return fo::check_launch("fo_gemm_w8");
+}
+
+}  // extern "C"

@@ -89,6 +89,10 @@ _SIGS = {
                              c_ll, c_vp]),
     "fo_pack_weight_elems": (c_ll, [c_int, c_int]),
     "fo_pack_weight": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp]),
+    "fo_quant_w8_bytes": (c_ll, [c_int, c_int]),
+    "fo_quant_w8": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
+    "fo_gemm_w8": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_ll,
+                           c_vp, c_vp, c_int, c_float, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), c_vp]),
     "fo_gemm_pick_split": (c_int, [c_int, c_int, c_int]),
     "fo_gemm_workspace_floats": (c_ll, [c_int, c_int, c_int, c_int]),
     "fo_gemm": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int,

@@ -67,14 +67,21 @@ def make_source(cfg, synth, device, model_path=None, llm_path=None, receive=Fals
 
 class FreezeOmniEngine:
     def __init__(self, model_path, llm_path=None, device="cuda:0", max_sessions=64, llm_kv_tokens=None,
-                 tts_kv_tokens=None, source=None, receive_weights=False, train_yaml=None):
-        """receive_weights=True: allocate every packed layout without reading or generating weights; the
+                 tts_kv_tokens=None, source=None, receive_weights=False, train_yaml=None, mlp_weights="bf16"):
+        """mlp_weights: "bf16" (default) or "fp8": the Qwen2 gate/up/down weights under weight-only FP8 (e4m3fn codes
+        times a power of two per output row, DESIGN: `mlp_weights`); Qwen2 steps of <= 16 rows then stream the codes.
+        `src` serves the dequantised weights (fo.weights.FakeQuantSource), so an oracle or a second engine can be
+        built on the same model.
+        receive_weights=True: allocate every packed layout without reading or generating weights; the
         caller fills them with fo.replica.broadcast_frozen(engine, dist) from rank 0 before any use.
         train_yaml: the parsed audiollm/train.yaml as a dict (models/utils.py:init_encoder_llm's configs) in
         place of the file; its cmvn_file, when present on disk, supplies the CMVN statistics
         (models/utils.py:31-38)."""
         if not torch.cuda.is_available():
             raise RuntimeError("FreezeOmniEngine needs an MI355X (gfx950) device: there is no CPU fallback")
+        if mlp_weights not in ("bf16", "fp8"):
+            raise ValueError(f"mlp_weights must be 'bf16' or 'fp8', got {mlp_weights!r}")
+        self.mlp_weights = mlp_weights
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         self.cfg, self.synth, self.llm_path = load_model_dir(model_path, llm_path)
@@ -90,14 +97,19 @@ class FreezeOmniEngine:
             st = {f"encoder_{i}.global_cmvn.{n}": torch.from_numpy(np.asarray(v, np.float32))
                   for i in ("user", "system") for n, v in (("mean", mean), ("istd", istd))}
             src = OverlaySource(CheckpointSource(st, self.device), src)
-        self.src = src
+        if mlp_weights == "fp8" and not receive_weights:
+            from .weights import FakeQuantSource
+            self.src = FakeQuantSource(src)   # (the engines below quantise the raw weights themselves)
+        else:
+            self.src = src
         self.max_sessions = max_sessions
         ty = self.cfg["train_yaml"]
         self.enc = {i: SpeechEncoderEngine(src, self.cfg, i, self.device, max_sessions) for i in ("user", "system")}
         self.ada = {i: AdapterEngine(src, self.cfg, i, self.device, max_sessions) for i in ("user", "system")}
         V = self.cfg["llm"]["vocab_size"]
         self.llm = LLMEngine(src, self.cfg["llm"], self.device,
-                             kv_tokens=llm_kv_tokens or min(max_sessions * 4096, 1 << 17))
+                             kv_tokens=llm_kv_tokens or min(max_sessions * 4096, 1 << 17),
+                             mlp_w8=mlp_weights == "fp8")
         self.tts = TTSEngine(src, self.cfg["decoder_json"], self.device,
                              kv_tokens=tts_kv_tokens or min(max_sessions * 2048, 1 << 17))
         self.codec = CodecEngine(src, self.cfg["codec_json"], self.device)
@@ -128,7 +140,9 @@ class FreezeOmniEngine:
         if bad:
             raise RuntimeError("load_checkpoint: shape mismatch: " + "; ".join(bad[:20]))
         state = {k: v for k, v in state.items() if k in need}
-        src = OverlaySource(CheckpointSource(state, self.device), self.src)
+        from .weights import FakeQuantSource
+        fq = isinstance(self.src, FakeQuantSource)
+        src = OverlaySource(CheckpointSource(state, self.device), self.src.inner if fq else self.src)
         for g in list(self._lgraphs.values()) + list(self._tgraphs.values()):
             g.destroy()
         self._lgraphs, self._tgraphs = {}, {}
@@ -140,10 +154,11 @@ class FreezeOmniEngine:
             kv_tokens = self.llm.pool.n_pages * self.llm.pool.PS
             self.llm = None   # release the old weights and pool first (15 GB at Qwen2-7B size)
             torch.cuda.empty_cache()
-            self.llm = LLMEngine(src, self.cfg["llm"], self.device, kv_tokens=kv_tokens)
+            self.llm = LLMEngine(src, self.cfg["llm"], self.device, kv_tokens=kv_tokens,
+                                 mlp_w8=self.mlp_weights == "fp8")
         elif "predictor_head.weight" in src:
             self.llm.head_w, self.llm.head_b = src.get("predictor_head.weight"), src.get("predictor_head.bias")
-        self.src = src
+        self.src = FakeQuantSource(src) if fq else src
         return sorted(state)
 
     # ------------------------------------------------------------------ chat template (audioLLM.py:112-126)

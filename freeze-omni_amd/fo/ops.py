@@ -317,6 +317,102 @@ class PackedLinear:
         return out
 
 
+class PackedLinearW8:
+    """A bias-free linear layer under weight-only FP8 (fo.quant, include/fo_hip.h fo_quant_w8): the weight is
+    W'[n, k] = q[n, k] * 2^e[n] with q an e4m3fn code.  Holds the packed codes `q`, the per-column `scales` and
+    `bf16`, a PackedLinear over the dequantised weight (W' is exactly a bf16 matrix).  Calls of <= 16 fp32 rows stream
+    the codes (fo_gemm_w8); every other call forwards to the bf16 image, so both compute X . W'^T.
+
+    w: [N, K] device weight (bf16 or fp32), quantised on the device; swiglu_up as PackedLinear.
+    receive=True: storages allocated, nothing quantised (a replica whose weights arrive by broadcast)."""
+
+    bias = None
+
+    def __init__(self, w, swiglu_up=None, receive=False):
+        _check_dev(w)
+        self.N, self.K = w.shape
+        self.Kp = (self.K + 31) // 32 * 32
+        self.swiglu = swiglu_up is not None
+        self.device = w.device
+        self.ntiles = (self.N + 15) // 16 * (2 if self.swiglu else 1)
+        self.q = torch.empty(self.ntiles * ((self.K + 63) // 64) * 1024, dtype=torch.uint8, device=w.device)
+        self.scales = torch.empty(self.ntiles * 16, dtype=F32, device=w.device)
+        if receive:
+            self.bf16 = PackedLinear(w, swiglu_up=swiglu_up)
+            return
+        dq = [self._quant(w, 0, 2 if self.swiglu else 1)]
+        if self.swiglu:
+            dq.append(self._quant(swiglu_up, 1, 2))
+        self.bf16 = PackedLinear(dq[0], swiglu_up=dq[1] if self.swiglu else None)
+
+    def _quant(self, w, base, stride):
+        if w.dtype not in (BF16, F32):
+            w = w.float()
+        w = w.contiguous()
+        dq = torch.empty(self.N, self.K, dtype=BF16, device=w.device)
+        _lib.call("fo_quant_w8", w.data_ptr(), 1 if w.dtype == BF16 else 0, self.N, self.K, self.K, self.q.data_ptr(),
+                  self.scales.data_ptr(), dq.data_ptr(), base, stride, stream(w.device))
+        return dq
+
+    @property
+    def packed(self):
+        return self.bf16.packed
+
+    @property
+    def nbytes(self):
+        """The bf16 image (what `weight_bytes` has always counted); the codes are fp8_nbytes."""
+        return self.bf16.nbytes
+
+    @property
+    def fp8_nbytes(self):
+        return self.q.numel() + self.scales.numel() * 4
+
+    def __call__(self, x, out=None, act="none", residual=False, out_dtype=F32, splitk=0, M=None, norm=None,
+                 stats_out=None, xpack=None, ypack=None):
+        rows = x.shape[0] if M is None else M
+        if rows > 16 or x.dtype != F32 or act != "none" or out_dtype != F32 or (out is not None and out.dtype != F32):
+            return self.bf16(x, out=out, act=act, residual=residual, out_dtype=out_dtype, splitk=splitk, M=M, norm=norm,
+                             stats_out=stats_out, xpack=xpack, ypack=ypack)
+        import ctypes
+        _check_dev(x)
+        if x.stride(-1) != 1 or x.shape[-1] < self.Kp:
+            raise ValueError(f"PackedLinearW8 input needs unit stride and >= {self.Kp} columns, got {tuple(x.shape)}")
+        if out is None:
+            out = torch.empty(rows, self.N, dtype=F32, device=x.device)
+        rst, rg, eps = (None, 0, 0.0) if norm is None else (norm[0].buf.data_ptr(), norm[0].groups, float(norm[1]))
+        if norm is not None and rg <= 0:
+            raise RuntimeError("RowStats consumed before any GEMM produced them")
+        so = gn = yg = None
+        if stats_out is not None:
+            so, gn, yg = stats_out.buf.data_ptr(), stats_out.gamma.data_ptr(), stats_out.yg.data_ptr()
+            if stats_out.yg.stride(0) != out.stride(0):
+                raise ValueError("yg must share the output's row stride")
+            if (self.N + 15) // 16 > stats_out.max_groups:
+                raise RuntimeError(f"RowStats holds {stats_out.max_groups} groups per row, fo_gemm_w8 writes "
+                                   f"{(self.N + 15) // 16}")
+        sg = ctypes.c_int(0)
+        rt = Runtime.get(x.device)
+        # (x is read as fp32 rows and the output is written row-major only: xpack / ypack stay untouched)
+        _lib.call("fo_gemm_w8", x.data_ptr(), x.stride(0), rows, self.Kp, self.q.data_ptr(), self.scales.data_ptr(),
+                  self.ntiles, self.N, 1 if self.swiglu else 0, out.data_ptr(), out.stride(0), 1 if residual else 0,
+                  rt.ws.data_ptr(), rt.ws.numel(), rt.counters.data_ptr(), rst, rg, eps, so, gn, yg, ctypes.byref(sg),
+                  stream(x.device))
+        if stats_out is not None:
+            stats_out.groups = sg.value
+        return out
+
+
+def quant_w8(w):
+    """fo_quant_w8 of one [N, K] device weight (bf16 or fp32) -> (packed codes uint8, packed scales fp32 [tiles * 16],
+    dequantised weight bf16 [N, K]); the CPU reference is fo.quant.quantize_rows_e4m3."""
+    p = PackedLinearW8.__new__(PackedLinearW8)
+    p.N, p.K = w.shape
+    nt = (p.N + 15) // 16
+    p.q = torch.empty(nt * ((p.K + 63) // 64) * 1024, dtype=torch.uint8, device=w.device)
+    p.scales = torch.empty(nt * 16, dtype=F32, device=w.device)
+    return p.q, p.scales, p._quant(w, 0, 1)
+
+
 # FO_XPACK=0 turns the packed <= 64-row activations off (A/B only)
 XPACK = os.environ.get("FO_XPACK", "1") != "0"
 
@@ -425,7 +521,7 @@ def h2d(a, device, dtype=None):
 # ---------------------------------------------------------------- launch counters (include/fo_hip.h FoLaunchKind)
 LAUNCH_KINDS = ("gemm_xs", "gemm_xsk", "gemm_xp", "gemm_reduce", "gemm_ln", "gemm_xp32", "gemm_ypack", "gemm_ypack32",
                 "gemm_mid", "gemm_rope4", "gemm_pipe", "gemm_other", "attn_mfma", "attn_decode", "attn_opack", "relpos",
-                "subsample", "attn_o", "enc_block", "gemm_rows")
+                "subsample", "attn_o", "enc_block", "gemm_rows", "gemm_w8", "gemm_w8_xs")
 
 
 def launch_counts():

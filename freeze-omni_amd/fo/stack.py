@@ -14,7 +14,8 @@ import torch
 
 from . import ops
 from .kv import BatchMeta
-from .ops import F32, PackedLinear
+from .ops import F32, PackedLinear, PackedLinearW8
+from .weights import ReceiveSource
 
 # FO_ATTN_DENSE=0 passes the item table even for one-token-per-sequence batches (A/B against a
 # library older than fo_attention's items == NULL form)
@@ -32,7 +33,10 @@ class Layer:
 
 class DecoderStack:
     def __init__(self, src, prefix, n_layers, D, H, KVH, eps, bias, rope, pool, kv_layer0=0, first_fp16=False,
-                 attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT):
+                 attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT, mlp_w8=False):
+        """mlp_w8: gate/up and down under weight-only FP8 (ops.PackedLinearW8: the model's MLP weights become
+        q * 2^e; forwards of <= 16 rows stream the codes, larger ones the exact bf16 image of the same weights)."""
+        self.mlp_w8 = bool(mlp_w8)
         self.n, self.D, self.H, self.KVH, self.hd, self.eps = n_layers, D, H, KVH, D // H, eps
         self.attn_kps = attn_keys_per_split
         self.cos, self.sin = rope
@@ -53,9 +57,15 @@ class DecoderStack:
             L.qkv = PackedLinear(torch.cat([wq, wk, wv]), b, rope_hd=self.hd)
             del wq, wk, wv
             L.o = PackedLinear(src.get(q + "self_attn.o_proj.weight", torch.bfloat16))
-            L.gu = PackedLinear(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
-                                swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16))
-            L.down = PackedLinear(src.get(q + "mlp.down_proj.weight", torch.bfloat16))
+            if self.mlp_w8:
+                recv = isinstance(src, ReceiveSource)   # storages only: the broadcast fills codes, scales and image
+                L.gu = PackedLinearW8(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
+                                      swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16), receive=recv)
+                L.down = PackedLinearW8(src.get(q + "mlp.down_proj.weight", torch.bfloat16), receive=recv)
+            else:
+                L.gu = PackedLinear(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
+                                    swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16))
+                L.down = PackedLinear(src.get(q + "mlp.down_proj.weight", torch.bfloat16))
             self.layers.append(L)
         # decode steps (one token per sequence) of an MHA stack with a small o projection -- the AR speech decoder, 14
         # heads of 64, o 896 x 896 -- fuse the attention with the o projection (fo_attention_o: each (session, head)
@@ -70,6 +80,11 @@ class DecoderStack:
     @property
     def weight_bytes(self):
         return sum(L.qkv.nbytes + L.o.nbytes + L.gu.nbytes + L.down.nbytes for L in self.layers)
+
+    @property
+    def mlp_fp8_bytes(self):
+        """The FP8 codes and scales held beside the bf16 image (0 without mlp_w8)."""
+        return sum(getattr(L.gu, "fp8_nbytes", 0) + getattr(L.down, "fp8_nbytes", 0) for L in self.layers)
 
     def workspace(self, T, nsplit, device):
         """Preallocated per-forward buffers for T tokens (graph capture must not allocate)."""
@@ -126,6 +141,10 @@ class DecoderStack:
                   meta.block_table.shape[1] * self.pool.PS <= 4096)
         if fuse_o:
             xgp = attp = None
+        # <= 16 rows under mlp_w8: the FP8 gate/up reads fp32 rows and the FP8 down writes none packed, so nobody
+        # fills or reads the packed x*gamma (the next q|k|v reads the fp32 rows); the o input stays packed
+        if self.mlp_w8 and T <= 16:
+            xgp = None
         # (a captured graph's meta carries its capacity, not the replay's keys: graphs keep 128-key splits, which fill
         # the chip at the listen / text shapes, r03c; eager launches -- duplex ticks, prefills -- size them per launch)
         eager = x.is_cuda and not torch.cuda.is_current_stream_capturing()

@@ -119,3 +119,23 @@ class ReceiveSource:
 
     def get(self, name, dtype=torch.float32):
         return torch.empty(tuple(self.shapes[name]), dtype=dtype, device=self.device)
+
+
+class FakeQuantSource:
+    """`inner` with the Qwen2 MLP weights (gate_proj, up_proj, down_proj of every model.layers.N) replaced by their
+    weight-only FP8 image W' = q * 2^e (fo.quant; quantised on the device from the bf16 weight, returned
+    dequantised -- exactly bf16 values).  An engine with mlp_weights="fp8" serves its weights through this, so the
+    oracle, or a second engine of either mode, can be built on the same model."""
+
+    MLP = ("mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
+
+    def __init__(self, inner):
+        self.inner = inner
+
+    def __contains__(self, name):
+        return name in self.inner
+
+    def get(self, name, dtype=torch.float32):
+        if not (name.startswith("model.layers.") and name.endswith(self.MLP)):
+            return self.inner.get(name, dtype)
+        return ops.quant_w8(self.inner.get(name, torch.bfloat16))[2].to(dtype)

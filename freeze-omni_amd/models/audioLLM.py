@@ -91,9 +91,11 @@ class AudioLLM:
             setattr(self, f"adpter_{i}", CNNSubsampling(self.engine.ada[i]))
 
     @classmethod
-    def from_model_dir(cls, model_path, llm_path=None, device="cuda:0", train_yaml=None, receive_weights=False, **kw):
+    def from_model_dir(cls, model_path, llm_path=None, device="cuda:0", train_yaml=None, receive_weights=False,
+                       mlp_weights="bf16", **kw):
+        """mlp_weights: "bf16" or "fp8" (FreezeOmniEngine: the Qwen2 MLP under weight-only FP8)."""
         return cls(FreezeOmniEngine(model_path, llm_path, device=device, train_yaml=train_yaml,
-                                    receive_weights=receive_weights), **kw)
+                                    receive_weights=receive_weights, mlp_weights=mlp_weights), **kw)
 
     def setup_logger(self, parent_logger=None):
         if parent_logger is not None:

@@ -27,7 +27,9 @@ class inferencePipeline:
     def __init__(self, args, weights_from=None):
         """weights_from: another inferencePipeline (any device) whose frozen weights this replica copies
         instead of reading / generating its own (fo.replica.copy_frozen: the in-process form of the
-        start-up broadcast, bin/pool.py's `devices` replicas)."""
+        start-up broadcast, bin/pool.py's `devices` replicas).
+        args["llm_mlp_weights"]: "bf16" (default) or "fp8", the engine's mlp_weights (every replica of a pool takes
+        the same value, so the copied layouts match)."""
         if isinstance(args, argparse.Namespace):
             args = vars(args)
         self.args = args
@@ -39,7 +41,8 @@ class inferencePipeline:
                                              top_k=top_k if top_k is not None else 1,
                                              top_p=args.get("top_p", 0.0) or 0.0,
                                              temperature=args.get("temperature", 1.0) or 1.0,
-                                             receive_weights=weights_from is not None)
+                                             receive_weights=weights_from is not None,
+                                             mlp_weights=args.get("llm_mlp_weights") or "bf16")
         if weights_from is not None:
             from fo.replica import copy_frozen
             copy_frozen(weights_from.model.engine, self.model.engine)

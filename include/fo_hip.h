@@ -177,10 +177,39 @@ enum FoLaunchKind {
   FO_L_ATTN_O = 17,     /* k_attn_decode_o: decode attention + o projection + residual + next-norm statistics */
   FO_L_ENC_BLOCK = 18,  /* k_enc_attn_block: the attention half of a speech-encoder block */
   FO_L_GEMM_ROWS = 19,  /* k_gemm_rows: 65..128 rows, the waves split the rows, weights shared through an LDS ring */
+  FO_L_GEMM_W8 = 20,    /* k_w8: the general <= 16-row FP8-weight GEMM (fo_gemm_w8) */
+  FO_L_GEMM_W8_XS = 21, /* k_w8_xs: the X-stationary FP8-weight gate/up stream (fo_gemm_w8, SwiGLU at K = 3584) */
   FO_LAUNCH_KINDS = 24
 };
 int fo_launch_counts(long long* out, int n);
 int fo_launch_counts_reset(void);
+/* Weight-only FP8 (OCP e4m3fn, gfx950's format) for <= 16-row launches: W'[n, k] = q[n, k] * 2^e[n], q an e4m3fn
+ * code and e[n] one integer per output row, the smallest with max|W[n, :]| * 2^-e[n] <= 448 (taken from the float's
+ * exponent and mantissa; 0 for an all-zero row); q = W * 2^-e (exact) rounded to nearest-even.  q * 2^e has at most
+ * 4 significant bits, so W' is exactly representable in bf16.
+ * Packed layout: codes [tile][ceil(K/64)][64 lanes][16 bytes] (fo_quant_w8_bytes(N, K) bytes per 16 ceil(N/16) rows),
+ * tile t = rows 16 t .. + 16.  Lane l of code step s holds row 16 t + (l & 15): bytes 0..7 are columns
+ * 64 s + 8 (l >> 4) .. + 8 (its MFMA B fragment of k-step 2 s), bytes 8..15 columns 64 s + 32 + 8 (l >> 4) .. + 8
+ * (k-step 2 s + 1), so a lane's load stays 16 bytes; columns K .. 64 ceil(K/64) and rows beyond N are zero codes.
+ * Scales: fp32 2^e[n] at [tile][16] in the same tile order (1 for rows beyond N).
+ * fo_quant_w8: quantises the device weight W [N][K] (row stride ldw; bf16 if src_bf16, else fp32): source tile t goes
+ *   to packed tile tile_base + t * tile_stride of q and scale (gate at base 0 and up at base 1 with stride 2
+ *   interleave the SwiGLU pair, as fo_pack_weight); wdq (optional) receives the dequantised W' as bf16 [N][K]
+ *   (contiguous), from which fo_pack_weight builds the bf16 image.
+ * fo_gemm_w8: Y = X . W'^T for fp32 X (split into bf16 hi + lo) of M <= 16 rows, K % 32 == 0, fp32 Y; ntiles is the
+ *   packed tile count of q / scale (ceil(N/16), twice that with swiglu).  Epilogues, with fo_gemm_rms's semantics:
+ *   plain, + Y (residual), swiglu (Y = silu(s_g g) * (s_u u)), the RMSNorm consumer (rstats / rgroups / eps) and
+ *   producer (sout, gnext, yg; *sgroups = ceil(N/16) groups per row).  The column scale multiplies the fp32 sum
+ *   before anything else.  It has no bias, affine, activation, bf16 output, RoPE, LayerNorm-on-load or packed X / Y;
+ *   those and M > 16 run the bf16 image through fo_gemm.  ws / ws_floats / counters (fo_gemm's: scratch floats and
+ *   zeroed ints, left zeroed; may be NULL) let long-K plain launches (the Qwen2 down) split K across workgroups and
+ *   merge inside the launch, the partials summed in split order: deterministic in every form. */
+long long fo_quant_w8_bytes(int N, int K);
+int fo_quant_w8(const void* W, int src_bf16, int N, int K, int ldw, void* q, float* scale, void* wdq, int tile_base,
+                int tile_stride, hipStream_t stream);
+int fo_gemm_w8(const float* X, int ldx, int M, int K, const void* q, const float* scale, int ntiles, int N, int swiglu,
+               float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters, const float* rstats,
+               int rgroups, float eps, float* sout, const float* gnext, float* yg, int* sgroups, hipStream_t stream);
 /* Software-pipelined one-row-tile fp32-X weight-stream GEMMs (M <= 16, >= 32 MB of weights: the next
  * k-group's weights + X in flight during this group's MFMAs).  3 (default): the measured policy; 0: plain
  * loops; 1 / 2: every such GEMM pipelined with 4 / 2 k-steps per group (sweeps).  Unset, the

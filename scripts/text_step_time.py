@@ -1,7 +1,7 @@
 """Wall and device time of one text-decode step (TextGraph: 28 Qwen2 layers + lm_head + sampler) for B
 sessions at real geometry after a ~150-token context, as the bench's speak stage runs it.
-python scripts/text_step_time.py [B] [steps] (GPU only; run under rocprofv3 --kernel-trace --stats for
-the per-kernel split)."""
+python scripts/text_step_time.py [B] [steps] [fp8] (GPU only; run under rocprofv3 --kernel-trace --stats for
+the per-kernel split).  The third argument `fp8` turns mlp_weights="fp8" on (the MLP streams FP8 codes)."""
 import os
 import sys
 import time
@@ -14,8 +14,9 @@ from fo.engine import FreezeOmniEngine  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 40
+MODE = sys.argv[3] if len(sys.argv) > 3 else "bf16"
 dev = torch.device("cuda:0")
-eng = FreezeOmniEngine(os.path.join(ROOT, "configs", "real"), device=dev, max_sessions=max(8, B))
+eng = FreezeOmniEngine(os.path.join(ROOT, "configs", "real"), device=dev, max_sessions=max(8, B), mlp_weights=MODE)
 base = eng.system_role("<|im_start|>system\nYou are a helpful assistant.")
 kvs = [base.fork() for _ in range(B)]
 ctx = list(range(100, 230))
@@ -30,5 +31,8 @@ for _ in range(N):
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t) / N
 gb = (eng.llm.stack.weight_bytes + eng.llm.lm_head.nbytes) / 1e9
-print(f"text step B={B}: {dt * 1e3:.3f} ms wall/step, {gb:.2f} GB weights -> {gb / dt / 1e3:.2f} TB/s "
+if MODE == "fp8":   # the MLP streams its codes instead of its bf16 image
+    L = eng.llm.stack.layers
+    gb += (eng.llm.mlp_fp8_bytes - sum(l.gu.nbytes + l.down.nbytes for l in L)) / 1e9
+print(f"text step B={B} mlp_weights={MODE}: {dt * 1e3:.3f} ms wall/step, {gb:.2f} GB weights -> {gb / dt / 1e3:.2f} TB/s "
       f"(roofline {gb / 8.0:.3f} ms at 8 TB/s)", flush=True)
