@@ -1,10 +1,11 @@
-// Weight-only FP8 (OCP e4m3fn) GEMMs for the Qwen2 MLP at <= 16 activation rows, and their quantiser.
+// Weight-only FP8 (OCP e4m3fn) GEMMs for the Qwen2 MLP at <= 16 activation rows (and, opt-in, 17..64), and their
+// quantiser.
 //
 //   W'[n, k] = q[n, k] * 2^e[n]      q an e4m3fn code, e[n] one integer per output row (stored as the fp32 2^e[n])
 //   Y[M, N]  = epilogue( X[M, K] (fp32, split into bf16 hi + lo) . W'^T )
 //
 // An e4m3 value has at most 4 significant bits, so q * 2^e is exactly a bf16 value: W' has an exact bf16 image, which
-// the engine keeps packed for the bf16 kernels (every launch above 16 rows).  The kernels here stream the codes --
+// the engine keeps packed for the bf16 kernels (every launch above 16 rows, or above 64 with fo_gemm_w8_rows).  The kernels here stream the codes --
 // half the bytes of that image -- decode them to bf16 in registers (exact) and run the same bf16 MFMAs; the column
 // scale multiplies the fp32 sum once per output element, before anything else in the epilogue, so both paths compute
 // X . W'^T to the accumulation-order difference that already exists between the bf16 kernels.
@@ -20,6 +21,9 @@
 //    hi / lo split, and K is split across workgroups to fill the chip.  The splits merge inside the launch, in this
 //    file: each stores its partial tiles write-through and takes the tile group's ticket; the split that arrives
 //    last sums every partial in split order (so the bits do not depend on which one that is) and runs the epilogue.
+//  * k_w8_rows + k_w8_rows_merge (fo_gemm_w8_rows): 17..64 rows, any K and N, SwiGLU or plain: k_gemm_xsk's design
+//    on the codes, X stationary per K slice (hi in registers, lo in LDS), K split over workgroups, units of two
+//    packed tiles; a second launch sums the splits' slabs in split order and runs the epilogue.
 // Results are deterministic in every form.
 #include <stdlib.h>
 
@@ -404,6 +408,187 @@ __global__ __launch_bounds__(NW * 64) void k_w8_xs(W8Args a, int units) {
   }
 }
 
+// ---- 17..64 rows (RB = 2..4 row blocks of 16): X-stationary with K split over workgroups, k_gemm_xsk's design
+// (fo_gemm.hip) on the codes.  Workgroup (g, sp): the sp-th of S slices of the code steps for units [ub, ue) of
+// column group g; a unit is a packed tile pair (the (gate, up) pair, or two adjacent plain tiles: the second of an
+// odd count's last pair lies past the code descriptor and loads zeros).  Wave w owns KPW code steps of the slice:
+// their X fragments of all RB row blocks are split once (hi in VGPRs, lo in its LDS region; k-steps at or past K
+// hold zeros and read no X), each 16-byte code load is decoded once per unit (dec8) and feeds RB x (hi, lo) MFMAs per
+// k-step, the next unit's codes in flight meanwhile.  Per unit the NW partial tiles are summed through LDS in wave
+// order (both tiles in one round where the LDS allows).  S == 1: the epilogue follows.  S > 1: the sums are stored as
+// split sp's slab of `ws` ([S][RB * 16][ntiles * 16] floats) and k_w8_rows_merge, the next launch, sums the slabs in
+// split order and runs the epilogue.
+template <int NW, int KPW, int RB, bool SW>
+__global__ __launch_bounds__(NW * 64) void k_w8_rows(W8Args a, int S, int per, float* ws) {
+  constexpr int ROWS = RB * 16, NTH = NW * 64, NE = ROWS * 16, EPT = (NE + NTH - 1) / NTH;
+  constexpr int PT = (NW * RB * 2 * KPW * 1024 + NW * 2 * ROWS * 17 * 4 + 512 <= 160 * 1024) ? 2 : 1;
+  __shared__ bf16x8 xlo[NW][RB][2 * KPW][64];
+  __shared__ float part[NW][PT][ROWS][17];
+  __shared__ float rstd_s[ROWS];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int G = gridDim.x, g = blockIdx.x, sp = blockIdx.y;
+  const int units = (a.ntiles + 1) >> 1, tiles = (a.N + 15) / 16;   // (tiles: output tiles, the statistics' groups)
+  const int ub = (int)((long)units * g / G), ue = (int)((long)units * (g + 1) / G);
+  const __amdgpu_buffer_rsrc_t srd = code_rsrc(a);
+  // this wave's code steps: [k0, k0 + nj) inside the slice [sp * per, (sp + 1) * per) and inside KK (wave-uniform)
+  const int k0 = sp * per + wave * KPW;
+  const int nj = max(0, min(KPW, min(a.KK, (sp + 1) * per) - k0));
+  const int voff = lane * 16;
+  u32x4 q[2][2][KPW];
+  auto issue = [&](u32x4 (&qq)[2][KPW], int u) {   // u >= ue: past the workgroup's range, no load issued
+    if (u < ue) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int j = 0; j < KPW; ++j)
+          if (j < nj)
+            qq[t][j] = __builtin_bit_cast(
+                u32x4, __builtin_amdgcn_raw_buffer_load_b128(srd, voff, ((2 * u + t) * a.KK + k0 + j) * 1024, 2));
+    }
+  };
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int j = 0; j < KPW; ++j) q[b][t][j] = u32x4{0u, 0u, 0u, 0u};   // code steps past the slice: zero codes
+  issue(q[0], ub);
+  issue(q[1], ub + 1);
+  bf16x8 zero;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) zero[i] = (__bf16)0.f;
+  bf16x8 xh[RB][2 * KPW];
+#pragma unroll
+  for (int r = 0; r < RB; ++r) {
+    const int row = min(r * 16 + (lane & 15), a.M - 1);   // rows >= M: computed, never stored or summed
+    const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
+#pragma unroll
+    for (int j = 0; j < 2 * KPW; ++j) {
+      bf16x8 hi = zero, lo = zero;
+      const int col = (2 * k0 + j) * 32;   // (K % 64 == 32: the last code step's second k-step is past K)
+      if ((j >> 1) < nj && col < a.K)
+        split8(reinterpret_cast<const float4*>(xp + col)[0], reinterpret_cast<const float4*>(xp + col)[1], hi, lo);
+      xh[r][j] = hi;
+      xlo[wave][r][j][lane] = lo;
+    }
+  }
+  if (S == 1) {   // the consumer's rstd of every row (rows >= M from the clamped row)
+    if (a.rstats)
+      for (int rr = wave; rr < ROWS; rr += NW) {
+        const int m = min(rr, a.M - 1);
+        float v = 0.f;
+        for (int j = lane; j < a.rgroups; j += 64) v += a.rstats[(size_t)m * a.rgroups + j];
+        v = wave_sum(v);
+        if (lane == 0) rstd_s[rr] = rsqrtf(v / (float)a.K + a.reps);
+      }
+    __syncthreads();
+  }
+  const int Ncols = a.ntiles * 16;
+  float* slab = ws + (size_t)sp * ROWS * Ncols;
+  auto unit = [&](u32x4 (&qq)[2][KPW], int u) {
+    float v[2][EPT];
+#pragma unroll
+    for (int t0 = 0; t0 < 2; t0 += PT) {
+      f32x4 acc[PT][RB];
+#pragma unroll
+      for (int p = 0; p < PT; ++p) {
+#pragma unroll
+        for (int r = 0; r < RB; ++r) acc[p][r] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < KPW; ++j)
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const bf16x8 w = dec8(qq[t0 + p][j][2 * h], qq[t0 + p][j][2 * h + 1]);
+#pragma unroll
+            for (int r = 0; r < RB; ++r) {
+              acc[p][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[r][2 * j + h], w, acc[p][r], 0, 0, 0);
+              acc[p][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xlo[wave][r][2 * j + h][lane], w, acc[p][r], 0, 0, 0);
+            }
+          }
+      }
+      if (t0 + PT == 2) issue(qq, u + 2);   // (the unit's codes are decoded: its buffer takes the unit after next)
+      __syncthreads();  // the previous reduction has read part[]
+#pragma unroll
+      for (int p = 0; p < PT; ++p)
+#pragma unroll
+        for (int r = 0; r < RB; ++r)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) part[wave][p][r * 16 + 4 * (lane >> 4) + i][lane & 15] = acc[p][r][i];
+      __syncthreads();
+#pragma unroll
+      for (int p = 0; p < PT; ++p)
+#pragma unroll
+        for (int i = 0; i < EPT; ++i) {
+          const int e = threadIdx.x + i * NTH;
+          float s = 0.f;
+          if (e < NE) {
+#pragma unroll
+            for (int w = 0; w < NW; ++w) s += part[w][p][e >> 4][e & 15];
+            if (S > 1 && 2 * u + t0 + p < a.ntiles)
+              slab[(size_t)(e >> 4) * Ncols + (2 * u + t0 + p) * 16 + (e & 15)] = s;
+          }
+          v[t0 + p][i] = s;
+        }
+    }
+    if (S == 1) {
+#pragma unroll
+      for (int i = 0; i < EPT; ++i) {
+        const int e = threadIdx.x + i * NTH;   // (NTH % 16 == 0: a row's 16 columns are one 16-lane row of a wave)
+        const int rr = e < NE ? e >> 4 : ROWS, c = e & 15;
+        if constexpr (SW) {
+          w8_epilogue<true>(a, u, tiles, rr, c, v[0][i], v[1][i], rstd_s);
+        } else {
+          w8_epilogue<false>(a, 2 * u, tiles, rr, c, v[0][i], 0.f, rstd_s);
+          if (2 * u + 1 < a.ntiles) w8_epilogue<false>(a, 2 * u + 1, tiles, rr, c, v[1][i], 0.f, rstd_s);
+        }
+      }
+    }
+  };
+  for (int u = ub; u < ue; u += 2) {   // (workgroup-uniform: every wave reaches unit's barriers)
+    unit(q[0], u);
+    if (u + 1 < ue) unit(q[1], u + 1);
+  }
+}
+
+// The merge of k_w8_rows's slabs: workgroup (u, rb) = output tile u (SW: the (gate, up) pair) x row block rb, thread
+// 16 rr + c one element: every split's partial summed in split order (8 loads in flight; a missing split adds 0),
+// then the epilogue.
+template <bool SW>
+__global__ __launch_bounds__(256) void k_w8_rows_merge(W8Args a, int S, const float* ws, int rows) {
+  constexpr int T = SW ? 2 : 1;
+  __shared__ float rstd_s[64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int u = blockIdx.x, rb = blockIdx.y;
+  if (a.rstats) {
+    for (int r = wave; r < 16; r += 4) {
+      const int m = min(rb * 16 + r, a.M - 1);
+      float v = 0.f;
+      for (int j = lane; j < a.rgroups; j += 64) v += a.rstats[(size_t)m * a.rgroups + j];
+      v = wave_sum(v);
+      if (lane == 0) rstd_s[rb * 16 + r] = rsqrtf(v / (float)a.K + a.reps);
+    }
+    __syncthreads();
+  }
+  const int rr = rb * 16 + (threadIdx.x >> 4), c = threadIdx.x & 15;
+  const int Ncols = a.ntiles * 16;
+  const size_t sl = (size_t)rows * Ncols;
+  float x[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    const float* p0 = ws + (size_t)rr * Ncols + (T * u + t) * 16 + c;
+    float s = 0.f;
+    for (int s0 = 0; s0 < S; s0 += 8) {
+      float p[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) p[k] = s0 + k < S ? p0[(s0 + k) * sl] : 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) s += p[k];
+    }
+    x[t] = s;
+  }
+  w8_epilogue<SW>(a, u, gridDim.x, rr, c, x[0], x[T - 1], rstd_s);
+}
+
 // ---- quantiser.  One workgroup per source row n: the row's amax, e[n] from its exponent and mantissa (the smallest
 // integer with amax * 2^-e <= 448 = 1.75 * 2^8), then 8 consecutive columns per thread: W * 2^-e (exact) rounded to
 // nearest-even e4m3fn by v_cvt_pk_fp8_f32, the 8 codes to their fragment position and the 8 dequantised bf16 values
@@ -564,6 +749,89 @@ int fo_gemm_w8(const float* X, int ldx, int M, int K, const void* Q, const float
   }
   fo::count_launch(FO_L_GEMM_W8);
   return fo::check_launch("fo_gemm_w8");
+}
+
+int fo_gemm_w8_rows(const float* X, int ldx, int M, int K, const void* Q, const float* scale, int ntiles, int N,
+                    int swiglu, float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters,
+                    const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
+                    int* sgroups, hipStream_t stream) {
+  FO_REQUIRE(M > 0 && N > 0 && K > 0, "fo_gemm_w8_rows: bad shape M=%d N=%d K=%d", M, N, K);
+  FO_REQUIRE(M >= 17 && M <= 64,
+             "fo_gemm_w8_rows: M=%d rows, this FP8 stream serves 17 <= M <= 64 (fo_gemm_w8 serves M <= 16, more than "
+             "64 rows run the bf16 image)", M);
+  FO_REQUIRE((K & 31) == 0, "fo_gemm_w8_rows: K=%d must be a multiple of 32", K);
+  FO_REQUIRE(X && Q && Y, "fo_gemm_w8_rows: NULL X, Q or Y");
+  FO_REQUIRE(scale, "fo_gemm_w8_rows: NULL scale (the per-column 2^e of fo_quant_w8)");
+  FO_REQUIRE(ldx >= K && (ldx & 3) == 0 && ((unsigned long long)X & 15) == 0,
+             "fo_gemm_w8_rows: X needs ldx=%d >= K=%d, ldx %% 4 == 0 and 16-byte alignment", ldx, K);
+  FO_REQUIRE(ldy >= N, "fo_gemm_w8_rows: ldy=%d < N=%d", ldy, N);
+  const int units = (N + 15) / 16;
+  FO_REQUIRE(ntiles == (swiglu ? 2 : 1) * units, "fo_gemm_w8_rows: ntiles=%d packed tiles for N=%d%s", ntiles, N,
+             swiglu ? " SwiGLU columns" : " columns");
+  FO_REQUIRE(!rstats || rgroups > 0, "fo_gemm_w8_rows: rstats without rgroups");
+  FO_REQUIRE(!sout || (!swiglu && (!yg || gnext)), "fo_gemm_w8_rows: sout needs a non-SwiGLU launch, yg needs gnext");
+  FO_REQUIRE(sout || !yg, "fo_gemm_w8_rows: yg comes with sout");
+  FO_REQUIRE(!(swiglu && residual), "fo_gemm_w8_rows: swiglu with residual unsupported");
+  const int KK = (K + 63) / 64;
+  FO_REQUIRE((long long)(ntiles + 4) * KK * 1024 < (1ll << 31), "fo_gemm_w8_rows: ntiles=%d x K=%d codes exceed 2 GiB",
+             ntiles, K);
+  W8Args a;
+  a.X = X;
+  a.Q = Q;
+  a.scale = scale;
+  a.Y = Y;
+  a.ldx = ldx;
+  a.ldy = ldy;
+  a.M = M;
+  a.K = K;
+  a.N = N;
+  a.ntiles = ntiles;
+  a.KK = KK;
+  a.residual = residual;
+  a.sout = sout;
+  a.gnext = gnext;
+  a.yg = yg;
+  a.rstats = rstats;
+  a.rgroups = rgroups;
+  a.reps = eps;
+  // NW waves x KPW code steps of X per K slice (hi in VGPRs, lo in LDS): 7 x 4 at 2 row blocks, 7 x 2 at 3 and 6 x 2
+  // at 4, the largest slices whose LDS still holds both tiles of a unit in one reduction round (7 x 3 at 3 row blocks
+  // reduced a tile at a time and measured 63.8 against 58.1 us on gate/up at 48 rows, 7 x 2 at 4 row blocks 48.7
+  // against 46.7 us on the down at 64).  S slices of `per` code steps, units of two packed tiles, about one workgroup
+  // per CU.  S > 1: the slabs are merged by a second launch (k_w8_rows_merge), one small workgroup per (tile, row
+  // block)
+  const int RB = (M + 15) / 16;
+  const int NW = RB == 4 ? 6 : 7, KPW = RB == 2 ? 4 : 2;
+  const int S = (KK + NW * KPW - 1) / (NW * KPW), per = (KK + S - 1) / S;
+  const int pairs = (ntiles + 1) / 2;
+  const int per_split = w8_cus() / S < 1 ? 1 : w8_cus() / S;
+  const int G = pairs < per_split ? pairs : per_split;
+  if (S > 1) {
+    const long long need = (long long)S * RB * 16 * ntiles * 16;
+    FO_REQUIRE(ws && need <= ws_floats,
+               "fo_gemm_w8_rows: K=%d splits over %d workgroups: split-K workspace too small (%lld floats needed, "
+               "%lld given)", K, S, need, ws ? ws_floats : 0ll);
+  }
+  (void)counters;
+  if (sgroups) *sgroups = units;
+  const dim3 grid(G, S), block(NW * 64);
+#define FO_W8_ROWS(NW_, KPW_, RB_)                                                                         \
+  do {                                                                                                     \
+    if (swiglu) hipLaunchKernelGGL((k_w8_rows<NW_, KPW_, RB_, true>), grid, block, 0, stream, a, S, per, ws); \
+    else hipLaunchKernelGGL((k_w8_rows<NW_, KPW_, RB_, false>), grid, block, 0, stream, a, S, per, ws);    \
+  } while (0)
+  if (RB == 2) FO_W8_ROWS(7, 4, 2);
+  else if (RB == 3) FO_W8_ROWS(7, 2, 3);
+  else FO_W8_ROWS(6, 2, 4);
+#undef FO_W8_ROWS
+  if (S > 1) {
+    const int rc = fo::check_launch("fo_gemm_w8_rows");
+    if (rc) return rc;
+    if (swiglu) hipLaunchKernelGGL((k_w8_rows_merge<true>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
+    else hipLaunchKernelGGL((k_w8_rows_merge<false>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
+  }
+  fo::count_launch(FO_L_GEMM_W8_ROWS);
+  return fo::check_launch("fo_gemm_w8_rows");
 }
 
 }  // extern "C"

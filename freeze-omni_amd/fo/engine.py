@@ -67,11 +67,15 @@ def make_source(cfg, synth, device, model_path=None, llm_path=None, receive=Fals
 
 class FreezeOmniEngine:
     def __init__(self, model_path, llm_path=None, device="cuda:0", max_sessions=64, llm_kv_tokens=None,
-                 tts_kv_tokens=None, source=None, receive_weights=False, train_yaml=None, mlp_weights="bf16"):
+                 tts_kv_tokens=None, source=None, receive_weights=False, train_yaml=None, mlp_weights="bf16",
+                 mlp_fp8_rows=16):
         """mlp_weights: "bf16" (default) or "fp8": the Qwen2 gate/up/down weights under weight-only FP8 (e4m3fn codes
         times a power of two per output row, DESIGN: `mlp_weights`); Qwen2 steps of <= 16 rows then stream the codes.
         `src` serves the dequantised weights (fo.weights.FakeQuantSource), so an oracle or a second engine can be
         built on the same model.
+        mlp_fp8_rows: 16 (default) or 64, with mlp_weights="fp8" only: 64 lets Qwen2 steps of 17..64 rows (duplex
+        ticks, prefixed first chunks, one-chunk listens of more than 8 sessions) stream the codes too, for the GEMMs
+        and row counts of ops.W8_ROWS_POLICY; the model is the same, every other step is unchanged.
         receive_weights=True: allocate every packed layout without reading or generating weights; the
         caller fills them with fo.replica.broadcast_frozen(engine, dist) from rank 0 before any use.
         train_yaml: the parsed audiollm/train.yaml as a dict (models/utils.py:init_encoder_llm's configs) in
@@ -81,7 +85,12 @@ class FreezeOmniEngine:
             raise RuntimeError("FreezeOmniEngine needs an MI355X (gfx950) device: there is no CPU fallback")
         if mlp_weights not in ("bf16", "fp8"):
             raise ValueError(f"mlp_weights must be 'bf16' or 'fp8', got {mlp_weights!r}")
+        if mlp_fp8_rows not in (16, 64):
+            raise ValueError(f"mlp_fp8_rows must be 16 or 64, got {mlp_fp8_rows!r}")
+        if mlp_fp8_rows == 64 and mlp_weights != "fp8":
+            raise ValueError("mlp_fp8_rows=64 needs mlp_weights='fp8'")
         self.mlp_weights = mlp_weights
+        self.mlp_fp8_rows = mlp_fp8_rows
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         self.cfg, self.synth, self.llm_path = load_model_dir(model_path, llm_path)
@@ -109,7 +118,7 @@ class FreezeOmniEngine:
         V = self.cfg["llm"]["vocab_size"]
         self.llm = LLMEngine(src, self.cfg["llm"], self.device,
                              kv_tokens=llm_kv_tokens or min(max_sessions * 4096, 1 << 17),
-                             mlp_w8=mlp_weights == "fp8")
+                             mlp_w8=mlp_weights == "fp8", mlp_w8_rows=mlp_fp8_rows)
         self.tts = TTSEngine(src, self.cfg["decoder_json"], self.device,
                              kv_tokens=tts_kv_tokens or min(max_sessions * 2048, 1 << 17))
         self.codec = CodecEngine(src, self.cfg["codec_json"], self.device)
@@ -155,7 +164,7 @@ class FreezeOmniEngine:
             self.llm = None   # release the old weights and pool first (15 GB at Qwen2-7B size)
             torch.cuda.empty_cache()
             self.llm = LLMEngine(src, self.cfg["llm"], self.device, kv_tokens=kv_tokens,
-                                 mlp_w8=self.mlp_weights == "fp8")
+                                 mlp_w8=self.mlp_weights == "fp8", mlp_w8_rows=self.mlp_fp8_rows)
         elif "predictor_head.weight" in src:
             self.llm.head_w, self.llm.head_b = src.get("predictor_head.weight"), src.get("predictor_head.bias")
         self.src = FakeQuantSource(src) if fq else src

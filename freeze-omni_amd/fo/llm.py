@@ -14,7 +14,7 @@ from .stack import DecoderStack
 
 class LLMEngine:
     def __init__(self, src, llm_cfg, device, head_src=None, kv_tokens=65536, page_size=16, max_pos=None,
-                 mlp_w8=False):
+                 mlp_w8=False, mlp_w8_rows=16):
         c = llm_cfg
         self.device = torch.device(device)
         self.D, self.V = c["hidden_size"], c["vocab_size"]
@@ -27,7 +27,8 @@ class LLMEngine:
         n_pages = (kv_tokens + page_size - 1) // page_size
         self.pool = KVPool(c["num_hidden_layers"], self.KVH, self.hd, n_pages, page_size, self.device)
         self.stack = DecoderStack(src, "model.layers.", c["num_hidden_layers"], self.D, self.H, self.KVH, self.eps,
-                                  True, self.rope, self.pool, first_fp16=True, mlp_w8=mlp_w8)
+                                  True, self.rope, self.pool, first_fp16=True, mlp_w8=mlp_w8,
+                                  mlp_w8_rows=mlp_w8_rows)
         self.embed_tokens = src.get("model.embed_tokens.weight", torch.bfloat16)
         self.norm = src.get("model.norm.weight")
         self.lm_head = PackedLinear(src.get("lm_head.weight", torch.bfloat16))

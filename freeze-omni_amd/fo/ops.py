@@ -317,6 +317,13 @@ class PackedLinear:
         return out
 
 
+# Which 17..64-row launches of a PackedLinearW8(stream_rows=64) stream the codes: per GEMM, the row-block counts
+# (ceil(rows / 16)) at which fo_gemm_w8_rows beat the bf16 image by more than that arm's spread -- for the down, by
+# more than the packed input it costs the next q|k|v as well (scripts/gemm_w8_rows_ab.py,
+# profiles/mlp_fp8_rows_gemm_ab.txt).  The one place the policy lives.
+W8_ROWS_POLICY = {"gate_up": (2, 3, 4), "down": (2,)}
+
+
 class PackedLinearW8:
     """A bias-free linear layer under weight-only FP8 (fo.quant, include/fo_hip.h fo_quant_w8): the weight is
     W'[n, k] = q[n, k] * 2^e[n] with q an e4m3fn code.  Holds the packed codes `q`, the per-column `scales` and
@@ -324,12 +331,19 @@ class PackedLinearW8:
     the codes (fo_gemm_w8); every other call forwards to the bf16 image, so both compute X . W'^T.
 
     w: [N, K] device weight (bf16 or fp32), quantised on the device; swiglu_up as PackedLinear.
-    receive=True: storages allocated, nothing quantised (a replica whose weights arrive by broadcast)."""
+    receive=True: storages allocated, nothing quantised (a replica whose weights arrive by broadcast).
+    stream_rows: 16 (default) or 64.  64 also lets calls of 17..64 fp32 rows stream the codes (fo_gemm_w8_rows), for
+    the row-block counts in `rows_rb`: W8_ROWS_POLICY's for this GEMM, the pairs that measured faster than the image.
+    Setting `rows_rb = (2, 3, 4)` on an instance sends every 17..64-row call there (tests, A/B scripts)."""
 
     bias = None
 
-    def __init__(self, w, swiglu_up=None, receive=False):
+    def __init__(self, w, swiglu_up=None, receive=False, stream_rows=16):
         _check_dev(w)
+        if stream_rows not in (16, 64):
+            raise ValueError(f"stream_rows must be 16 or 64, got {stream_rows!r}")
+        self.stream_rows = stream_rows
+        self.rows_rb = W8_ROWS_POLICY["gate_up" if swiglu_up is not None else "down"]
         self.N, self.K = w.shape
         self.Kp = (self.K + 31) // 32 * 32
         self.swiglu = swiglu_up is not None
@@ -367,10 +381,15 @@ class PackedLinearW8:
     def fp8_nbytes(self):
         return self.q.numel() + self.scales.numel() * 4
 
+    def streams(self, rows):
+        """Whether a call of `rows` fp32 rows streams the codes (else it runs the bf16 image)."""
+        return rows <= 16 or (rows <= self.stream_rows and (rows + 15) // 16 in self.rows_rb)
+
     def __call__(self, x, out=None, act="none", residual=False, out_dtype=F32, splitk=0, M=None, norm=None,
                  stats_out=None, xpack=None, ypack=None):
         rows = x.shape[0] if M is None else M
-        if rows > 16 or x.dtype != F32 or act != "none" or out_dtype != F32 or (out is not None and out.dtype != F32):
+        if (not self.streams(rows) or x.dtype != F32 or act != "none" or out_dtype != F32 or
+                (out is not None and out.dtype != F32)):
             return self.bf16(x, out=out, act=act, residual=residual, out_dtype=out_dtype, splitk=splitk, M=M, norm=norm,
                              stats_out=stats_out, xpack=xpack, ypack=ypack)
         import ctypes
@@ -393,8 +412,8 @@ class PackedLinearW8:
         sg = ctypes.c_int(0)
         rt = Runtime.get(x.device)
         # (x is read as fp32 rows and the output is written row-major only: xpack / ypack stay untouched)
-        _lib.call("fo_gemm_w8", x.data_ptr(), x.stride(0), rows, self.Kp, self.q.data_ptr(), self.scales.data_ptr(),
-                  self.ntiles, self.N, 1 if self.swiglu else 0, out.data_ptr(), out.stride(0), 1 if residual else 0,
+        _lib.call("fo_gemm_w8" if rows <= 16 else "fo_gemm_w8_rows", x.data_ptr(), x.stride(0), rows, self.Kp,
+                  self.q.data_ptr(), self.scales.data_ptr(), self.ntiles, self.N, 1 if self.swiglu else 0, out.data_ptr(), out.stride(0), 1 if residual else 0,
                   rt.ws.data_ptr(), rt.ws.numel(), rt.counters.data_ptr(), rst, rg, eps, so, gn, yg, ctypes.byref(sg),
                   stream(x.device))
         if stats_out is not None:
@@ -521,7 +540,7 @@ def h2d(a, device, dtype=None):
 # ---------------------------------------------------------------- launch counters (include/fo_hip.h FoLaunchKind)
 LAUNCH_KINDS = ("gemm_xs", "gemm_xsk", "gemm_xp", "gemm_reduce", "gemm_ln", "gemm_xp32", "gemm_ypack", "gemm_ypack32",
                 "gemm_mid", "gemm_rope4", "gemm_pipe", "gemm_other", "attn_mfma", "attn_decode", "attn_opack", "relpos",
-                "subsample", "attn_o", "enc_block", "gemm_rows", "gemm_w8", "gemm_w8_xs")
+                "subsample", "attn_o", "enc_block", "gemm_rows", "gemm_w8", "gemm_w8_xs", "gemm_w8_rows")
 
 
 def launch_counts():

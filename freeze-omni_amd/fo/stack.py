@@ -33,10 +33,12 @@ class Layer:
 
 class DecoderStack:
     def __init__(self, src, prefix, n_layers, D, H, KVH, eps, bias, rope, pool, kv_layer0=0, first_fp16=False,
-                 attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT, mlp_w8=False):
+                 attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT, mlp_w8=False, mlp_w8_rows=16):
         """mlp_w8: gate/up and down under weight-only FP8 (ops.PackedLinearW8: the model's MLP weights become
-        q * 2^e; forwards of <= 16 rows stream the codes, larger ones the exact bf16 image of the same weights)."""
+        q * 2^e; forwards of <= 16 rows stream the codes, larger ones the exact bf16 image of the same weights).
+        mlp_w8_rows: 16 or 64, PackedLinearW8's stream_rows (64: 17..64-row forwards stream the codes too)."""
         self.mlp_w8 = bool(mlp_w8)
+        self.mlp_w8_rows = mlp_w8_rows
         self.n, self.D, self.H, self.KVH, self.hd, self.eps = n_layers, D, H, KVH, D // H, eps
         self.attn_kps = attn_keys_per_split
         self.cos, self.sin = rope
@@ -60,8 +62,10 @@ class DecoderStack:
             if self.mlp_w8:
                 recv = isinstance(src, ReceiveSource)   # storages only: the broadcast fills codes, scales and image
                 L.gu = PackedLinearW8(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
-                                      swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16), receive=recv)
-                L.down = PackedLinearW8(src.get(q + "mlp.down_proj.weight", torch.bfloat16), receive=recv)
+                                      swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16), receive=recv,
+                                      stream_rows=mlp_w8_rows)
+                L.down = PackedLinearW8(src.get(q + "mlp.down_proj.weight", torch.bfloat16), receive=recv,
+                                        stream_rows=mlp_w8_rows)
             else:
                 L.gu = PackedLinear(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
                                     swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16))
@@ -143,8 +147,14 @@ class DecoderStack:
             xgp = attp = None
         # <= 16 rows under mlp_w8: the FP8 gate/up reads fp32 rows and the FP8 down writes none packed, so nobody
         # fills or reads the packed x*gamma (the next q|k|v reads the fp32 rows); the o input stays packed
-        if self.mlp_w8 and T <= 16:
-            xgp = None
+        # (17..64 rows under mlp_w8_rows=64 likewise, per GEMM: an FP8 gate/up leaves the o's packed x*gamma unread,
+        # an FP8 down fills none for the next q|k|v)
+        xgp_gu = xgp_qkv = xgp
+        if self.mlp_w8 and self.layers:
+            if self.layers[0].gu.streams(T):
+                xgp_gu = None
+            if self.layers[0].down.streams(T):
+                xgp_qkv = None
         # (a captured graph's meta carries its capacity, not the replay's keys: graphs keep 128-key splits, which fill
         # the chip at the listen / text shapes, r03c; eager launches -- duplex ticks, prefills -- size them per launch)
         eager = x.is_cuda and not torch.cuda.is_current_stream_capturing()
@@ -158,7 +168,7 @@ class DecoderStack:
             xin, norm = (h, None) if i == 0 else (xg, (sA, self.eps))
             if i == 0 and not pre_normed:
                 ops.rmsnorm(x, L.ln1, self.eps, out=h, round_fp16=self.first_fp16, M=T)
-            L.qkv.qkv_rope(xin, T, *rope, norm=norm, xpack=xgp if i > 0 else None)
+            L.qkv.qkv_rope(xin, T, *rope, norm=norm, xpack=xgp_qkv if i > 0 else None)
             if fuse_o:
                 ops.attention_o(q, T, None if dense else meta.items, meta.tok_nvis, meta.block_table, self.pool.PS,
                                 self.pool.k[li], self.pool.v[li], H, hd, scale, L.o, ws["o_part"], ws["o_tickets"], x,
@@ -168,12 +178,12 @@ class DecoderStack:
                               meta.block_table, self.pool.PS, self.pool.k[li], self.pool.v[li], H, KVH, hd, scale,
                               nsplit, part_ml, part_o, att, tickets=ws["tickets"], keys_per_split=kps,
                               opack=attp)
-                L.o(att, out=x, residual=True, M=T, stats_out=sB.set(L.ln2, xg), xpack=attp, ypack=xgp)
-            L.gu(xg, out=m, M=T, norm=(sB, self.eps), xpack=xgp)
+                L.o(att, out=x, residual=True, M=T, stats_out=sB.set(L.ln2, xg), xpack=attp, ypack=xgp_gu)
+            L.gu(xg, out=m, M=T, norm=(sB, self.eps), xpack=xgp_gu)
             if i == last and final_norm is None:
                 L.down(m, out=x, residual=True, M=T)
             elif i == last:
                 L.down(m, out=x, residual=True, M=T, stats_out=sA.set(final_norm, xg))
             else:
-                L.down(m, out=x, residual=True, M=T, stats_out=sA.set(self.layers[i + 1].ln1, xg), ypack=xgp)
+                L.down(m, out=x, residual=True, M=T, stats_out=sA.set(self.layers[i + 1].ln1, xg), ypack=xgp_qkv)
         return x

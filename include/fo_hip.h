@@ -179,11 +179,13 @@ enum FoLaunchKind {
   FO_L_GEMM_ROWS = 19,  /* k_gemm_rows: 65..128 rows, the waves split the rows, weights shared through an LDS ring */
   FO_L_GEMM_W8 = 20,    /* k_w8: the general <= 16-row FP8-weight GEMM (fo_gemm_w8) */
   FO_L_GEMM_W8_XS = 21, /* k_w8_xs: the X-stationary FP8-weight gate/up stream (fo_gemm_w8, SwiGLU at K = 3584) */
+  FO_L_GEMM_W8_ROWS = 22, /* k_w8_rows (+ its merge): the 17..64-row X-stationary split-K FP8-weight stream (fo_gemm_w8_rows) */
   FO_LAUNCH_KINDS = 24
 };
 int fo_launch_counts(long long* out, int n);
 int fo_launch_counts_reset(void);
-/* Weight-only FP8 (OCP e4m3fn, gfx950's format) for <= 16-row launches: W'[n, k] = q[n, k] * 2^e[n], q an e4m3fn
+/* Weight-only FP8 (OCP e4m3fn, gfx950's format) for <= 16-row launches (fo_gemm_w8) and, where the caller opts in,
+ * 17..64-row ones (fo_gemm_w8_rows): W'[n, k] = q[n, k] * 2^e[n], q an e4m3fn
  * code and e[n] one integer per output row, the smallest with max|W[n, :]| * 2^-e[n] <= 448 (taken from the float's
  * exponent and mantissa; 0 for an all-zero row); q = W * 2^-e (exact) rounded to nearest-even.  q * 2^e has at most
  * 4 significant bits, so W' is exactly representable in bf16.
@@ -203,13 +205,25 @@ int fo_launch_counts_reset(void);
  *   before anything else.  It has no bias, affine, activation, bf16 output, RoPE, LayerNorm-on-load or packed X / Y;
  *   those and M > 16 run the bf16 image through fo_gemm.  ws / ws_floats / counters (fo_gemm's: scratch floats and
  *   zeroed ints, left zeroed; may be NULL) let long-K plain launches (the Qwen2 down) split K across workgroups and
- *   merge inside the launch, the partials summed in split order: deterministic in every form. */
+ *   merge inside the launch, the partials summed in split order: deterministic in every form.
+ * fo_gemm_w8_rows: the same product, arguments and epilogues for 17 <= M <= 64 rows (any other M is refused on the
+ *   host), any K % 32 == 0 and any N, SwiGLU or plain: X stationary per K slice (k_w8_rows), K split over workgroups
+ *   whenever it exceeds one slice (28 / 14 / 12 code steps at 2 / 3 / 4 row blocks of 16).  A split launch needs ws
+ *   (slices x 16 ceil(M/16) x 16 ntiles floats, checked against ws_floats) and is followed by a second launch
+ *   (k_w8_rows_merge) that sums the slices' partial sums in slice order and runs the epilogue: deterministic.
+ *   counters is accepted for fo_gemm_w8's signature and not used.  Rows >= M are neither stored nor summed.  It reads
+ *   fp32 rows and writes row-major Y / yg only (no packed X / Y).  Both launches are capture-safe; one call counts
+ *   one FO_L_GEMM_W8_ROWS. */
 long long fo_quant_w8_bytes(int N, int K);
 int fo_quant_w8(const void* W, int src_bf16, int N, int K, int ldw, void* q, float* scale, void* wdq, int tile_base,
                 int tile_stride, hipStream_t stream);
 int fo_gemm_w8(const float* X, int ldx, int M, int K, const void* q, const float* scale, int ntiles, int N, int swiglu,
                float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters, const float* rstats,
                int rgroups, float eps, float* sout, const float* gnext, float* yg, int* sgroups, hipStream_t stream);
+int fo_gemm_w8_rows(const float* X, int ldx, int M, int K, const void* q, const float* scale, int ntiles, int N,
+                    int swiglu, float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters,
+                    const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
+                    int* sgroups, hipStream_t stream);
 /* Software-pipelined one-row-tile fp32-X weight-stream GEMMs (M <= 16, >= 32 MB of weights: the next
  * k-group's weights + X in flight during this group's MFMAs).  3 (default): the measured policy; 0: plain
  * loops; 1 / 2: every such GEMM pipelined with 4 / 2 k-steps per group (sweeps).  Unset, the
