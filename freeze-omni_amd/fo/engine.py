@@ -19,6 +19,7 @@ import torch
 
 from . import _lib, ops
 from .codec import CodecEngine
+from .kv import GroupMeta
 from .llm import LLMEngine
 from .ops import F32, I32
 from .params import all_shapes
@@ -774,11 +775,12 @@ class ListenGroupGraph:
     ([chunk][session][token]); the LLM stage then prefills all C x B x To rows at once -- each session's C chunks are
     its next C*To positions, causal, so chunk j's rows see chunks < j of the same stage as the sequential order does
     -- and the dialog-state head reads every chunk's last row (one decision per chunk, models/audioLLM.py:420-429).
-    Work items are (session, chunk): To tokens each, as in ListenGraph.  The Qwen2 weights stream once per C chunks
-    instead of once per chunk; the GEMMs run at C x 16 rows (k_gemm_xsk / the 17..64-row paths), whose row-count
-    dependent tilings give the sequential results to fp32 rounding, not bit for bit.  A group of m < C chunks (the
-    end of the input) replays an LLM stage captured for m.  Two slots: the encoder stages of group g+1 run on the side
-    stream while group g's LLM stage runs (ListenPipe)."""
+    Work items are (chunk, session): To tokens each, as in ListenGraph (the tables: kv.GroupMeta).  The Qwen2 weights
+    stream once per C chunks instead of once per chunk; the GEMMs run at m x B x To rows -- at 8 sessions of 2 tokens,
+    m x 16: the split-K 17..64-row paths (k_gemm_xsk) up to m = 4, the 65..128-row family (k_gemm_rows) from m = 5
+    to the benchmark's C = 8 -- whose row-count dependent tilings give the sequential results to fp32 rounding, not
+    bit for bit.  A group of m < C chunks (the end of the input) replays an LLM stage captured for m.  Two slots: the
+    encoder stages of group g+1 run on the side stream while group g's LLM stage runs (ListenPipe)."""
 
     def __init__(self, eng, ident, B, R, max_keys, C):
         dev = eng.device
@@ -795,25 +797,17 @@ class ListenGroupGraph:
         assert To * G <= 16, "listen group graph: one attention work item per (session, chunk)"
         self.n1 = n1 = B * To
         self.n = n = C * n1
-        PS = llm.pool.PS
-        self.maxb = (max_keys + PS - 1) // PS
+        # the Qwen2 stage's chunk-major tables (kv.GroupMeta): items, decision rows, per-m views, host fill
+        self.gm = gm = GroupMeta(B, To, C, G, max_keys, llm.pool.PS, dev)
+        self.maxb = gm.maxb
         # encoder metadata [chunk j: enc 4B] x C | ada slots B -- filled chunk by chunk on the host, uploaded once
         self.emeta_d = torch.zeros(4 * B * C + B, dtype=I32, device=dev)
         self.hmeta = np.zeros(4 * B * C + B, np.int32)
-        self.lmeta_d = torch.zeros(3 * n + B * self.maxb, dtype=I32, device=dev)
-        self.ering, self.lring = _HostRing(4 * B * C + B), _HostRing(3 * n + B * self.maxb)
+        self.lmeta_d = gm.buf
+        self.ering, self.lring = _HostRing(4 * B * C + B), _HostRing(gm.size)
         self.eb["meta"] = self.emeta_d[0:4 * B * C]
         self.ab["slots"] = self.emeta_d[4 * B * C:]
-        lm = self.lmeta_d
-        self.items = torch.tensor([[b, j * n1 + b * To, To] for j in range(C) for b in range(B)],
-                                  dtype=I32).reshape(-1).to(dev)
-        self.rows = torch.tensor([j * n1 + b * To + To - 1 for j in range(C) for b in range(B)], dtype=I32).to(dev)
-        bt = lm[3 * n:].view(B, self.maxb)
-        self.metas = {m: SimpleNamespace(T=m * n1, S=B, tok_pos=lm[0:m * n1], tok_slot=lm[n:n + m * n1],
-                                         tok_nvis=lm[2 * n:2 * n + m * n1], block_table=bt,
-                                         items=self.items[:3 * m * B], n_items=m * B, max_rows=To * G,
-                                         max_keys=max_keys, uniform=False)
-                      for m in range(1, C + 1)}
+        self.items, self.rows, self.metas = gm.items, gm.rows, gm.metas
         self.xs = [torch.empty(n, llm.D, dtype=F32, device=dev) for _ in range(2)]
         self.ws = llm.stack.workspace(n, ops.attn_nsplit(max_keys, C * B, llm.KVH), dev)
         self.predict = ident == "user" and bool(eng.predict_usr_state) and llm.head_w is not None
@@ -892,7 +886,7 @@ class ListenGroupGraph:
     def submit_llm(self, groups, pes, k):
         """The LLM stage of the m = len(groups) chunks whose encoder stages filled slot k (engine stream); appends
         m * To KV rows per session.  collect_llm(k) reads its results."""
-        B, To, n1, n, maxb = self.B, self.To, self.n1, self.n, self.maxb
+        B = self.B
         m = len(groups)
         if self.enc_todo[k]:   # a partial group (the end of the input): its encoder stage is queued now
             self.launch_encoder(k)
@@ -900,22 +894,7 @@ class ListenGroupGraph:
         if ex is None:
             ex = self.llm_exec[k][m] = ListenGraph._capture(self.main, lambda: self._llm_body(k, m))
         q, h = self.lring.next()
-        bt = h[3 * n:].reshape(B, maxb)
-        for b, it in enumerate(groups[0]):
-            kv = it["kv"]
-            old = kv.length
-            kv.reserve(old + m * To)
-            if len(kv.pages) > maxb:
-                raise RuntimeError("listen group graph block table too small")
-            for j in range(m):
-                for i in range(To):
-                    r = j * n1 + b * To + i
-                    pos = old + j * To + i
-                    h[r] = pos
-                    h[n + r] = kv.slot(pos)
-                    h[2 * n + r] = pos + 1
-            bt[b, :len(kv.pages)] = kv.pages
-            kv.length = old + m * To
+        self.gm.fill(h, [it["kv"] for it in groups[0]], m)
         st = self.main
         self.lring.upload(q, self.lmeta_d, st)
         _lib.call("fo_stream_wait_event", st.cuda_stream, self.ev_enc[k])

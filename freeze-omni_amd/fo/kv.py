@@ -8,6 +8,7 @@ shares full pages copy-on-write (refcounts), so N sessions forked from one syste
 once, and appending never moves existing keys.
 """
 import threading
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -239,3 +240,53 @@ class BatchMeta:
         self.items = dev[4 * T + S + S * maxb:]
         self.last_rows_host = last_rows
         self._host = host  # keep the staging buffer alive until the copy is consumed
+
+
+class GroupMeta:
+    """Metadata of the Qwen2 stage of a listen group (engine.ListenGroupGraph): m <= C consecutive chunks of B
+    sessions, To tokens a chunk, in one forward whose rows are chunk-major ([chunk][session][token]).  Session b's
+    chunk j holds its positions old + j*To .. old + (j+1)*To - 1, causal, so it sees the keys that chunks < j of the
+    same forward append.  Work items are (chunk, session) in that order, To tokens each; `rows` are the decision rows
+    (each chunk's last row of each session) in the same order.
+
+    buf: the static device block [tok_pos n | tok_slot n | tok_nvis n | block table B x maxb], n = C*B*To, that the
+    captured stages read; metas[m]: the views of a group of m chunks (what DecoderStack.forward takes);
+    fill(h, seqs, m) writes one group's values into a host block of `size` int32 (uploaded to buf by the caller)."""
+
+    def __init__(self, B, To, C, gqa, max_keys, page_size, device):
+        self.B, self.To, self.C = B, To, C
+        self.n1 = n1 = B * To
+        self.n = n = C * n1
+        self.maxb = (max_keys + page_size - 1) // page_size
+        self.size = 3 * n + B * self.maxb
+        self.buf = lm = torch.zeros(self.size, dtype=torch.int32, device=device)
+        self.items = torch.tensor([[b, j * n1 + b * To, To] for j in range(C) for b in range(B)],
+                                  dtype=torch.int32).reshape(-1).to(device)
+        self.rows = torch.tensor([j * n1 + b * To + To - 1 for j in range(C) for b in range(B)],
+                                 dtype=torch.int32).to(device)
+        bt = lm[3 * n:].view(B, self.maxb)
+        self.metas = {m: SimpleNamespace(T=m * n1, S=B, tok_pos=lm[0:m * n1], tok_slot=lm[n:n + m * n1],
+                                         tok_nvis=lm[2 * n:2 * n + m * n1], block_table=bt,
+                                         items=self.items[:3 * m * B], n_items=m * B, max_rows=To * gqa,
+                                         max_keys=max_keys, uniform=False)
+                      for m in range(1, C + 1)}
+
+    def fill(self, h, seqs, m):
+        """One group of m chunks for the B sequences `seqs` into the host block h: reserves m*To KV rows per
+        sequence and advances its length."""
+        B, To, n1, n, maxb = self.B, self.To, self.n1, self.n, self.maxb
+        bt = h[3 * n:].reshape(B, maxb)
+        for b, kv in enumerate(seqs):
+            old = kv.length
+            kv.reserve(old + m * To)
+            if len(kv.pages) > maxb:
+                raise RuntimeError("listen group graph block table too small")
+            for j in range(m):
+                for i in range(To):
+                    r = j * n1 + b * To + i
+                    pos = old + j * To + i
+                    h[r] = pos
+                    h[n + r] = kv.slot(pos)
+                    h[2 * n + r] = pos + 1
+            bt[b, :len(kv.pages)] = kv.pages
+            kv.length = old + m * To

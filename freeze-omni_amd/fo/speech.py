@@ -286,10 +286,12 @@ class SpeechEncoderEngine:
         ops.layernorm(x, *self.embed_ln, out=x, relu=True, M=N * T)
         ops.scale_(x[:N * T], math.sqrt(self.d))
         meta = bufs["meta"]
-        h, qkv, att, f = bufs["h"], bufs["qkv"], bufs["att"], bufs["f"]
         scale = 1.0 / math.sqrt(self.dk)
         if chunks > 1:
             return self._run_chunks(x, B, T, chunks, bufs, meta, scale)
+        # (bufs may be a listen group's, sized for its C chunks, running a last group of one chunk: the row-wise steps
+        # take their row count from these views)
+        x, h, qkv, att, f = x[:B * T], bufs["h"][:B * T], bufs["qkv"][:B * T], bufs["att"][:B * T], bufs["f"][:B * T]
         st, ln, rg, ps = meta[:B], meta[B:2 * B], meta[2 * B:3 * B], meta[3 * B:]
         # pre-norms applied by the GEMMs on load (fo_gemm_ln) from the residual producers' row sums
         fuse_ln = B * T <= 64 and os.environ.get("FO_ENC_LN_ON_LOAD", "1") != "0"
@@ -366,7 +368,9 @@ class SpeechEncoderEngine:
             else:
                 ops.layernorm(x, *L["ln1"], out=h)
                 L["qkv"](h, out=qkv)
-            if CHUNK_ATTN:   # the chunks in order inside one launch per (user, head)
+            # (the one-launch form appends the group's chunks * T rows to the ring in one go, so they must fit it; a
+            # short ring -- the tiny model's 16 slots against 8 chunks of 4 frames -- takes the launch per chunk)
+            if CHUNK_ATTN and chunks * T <= self.cap:   # the chunks in order inside one launch per (user, head)
                 ops.relpos_attention_chunks(qkv, self.kr[i], self.vr[i], self.cap, meta, B, chunks, self.ptab[i],
                                             L["bu"], L["bv"], T, self.h, self.dk, scale, att)
             else:            # one launch per chunk (A/B)

@@ -33,7 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 REF = "/root/reference"
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
-from goldenio import load_golden, save_parts  # noqa: E402  (fixtures over 1 MiB are stored in parts)
+from goldenio import LIMIT as GOLDEN_PART_LIMIT, load_golden, save_parts  # noqa: E402  (fixtures over 1 MiB are stored in parts)
 from oracle import configs as C  # noqa: E402
 from oracle.weights import synth_param  # noqa: E402
 
@@ -815,6 +815,75 @@ def gold_real_qwen2_mid(seed=7, n_layers=2, n_sess=8):
           f"input sum {insum:.6f}")
 
 
+GROUP_CHUNKS = 15   # consecutive 2-row listen chunks per session: 8 + 7 at 8 chunks per Qwen2 stage, 4 + 4 + 4 + 3 at 4
+
+
+def group_embeds(chunk, b, D=3584):
+    """fp16-valued input embeds of session b's listen chunk `chunk` (regenerated by tests/test_real_qwen2_gpu.py)."""
+    return (np.random.default_rng(8765 + 100 * chunk + b).standard_normal((2, D)) * 0.5).astype(np.float16)
+
+
+def gold_real_qwen2_group(seed=7, n_layers=2, n_sess=8):
+    """GROUP_CHUNKS consecutive 2-row listen chunks per session at REAL geometry, fed one call at a time as
+    bin/inference.py feeds a wav's chunks, through the reference's own AudioLLM._llm_forward_core /
+    _prediction_head_forward (models/audioLLM.py:350-429,479-493): the same 2-layer counter-hash Qwen2 and the same
+    eight sessions as gold_real_qwen2 (its 9 + 2b-row prefill, real_qwen2_t2.npz emb0), each session its own
+    DynamicCache.  The odd prefill lengths put a chunk across a 16-token KV page at a different chunk in each
+    session.  Stored (weights and the chunk inputs regenerate) per chunk and session: the full last hidden row, both
+    rows at 1024 fixed columns, both rows' float64 sum / sum of squares over all 3584 columns, the three state
+    probs and the KV length after the chunk."""
+    from transformers import Qwen2Config, Qwen2ForCausalLM
+    sys.argv = ["golden"]
+    from models.audioLLM import AudioLLM
+    cfg = C.get("real")
+    assert cfg["seed"] == seed
+    lc = dict(cfg["llm"], num_hidden_layers=n_layers)
+    m = Qwen2ForCausalLM(Qwen2Config(**lc, torch_dtype="float32"))
+    for k, v in m.state_dict().items():
+        v.copy_(torch.from_numpy(synth_param(seed, k, tuple(v.shape), cfg["overrides"])))
+    m.eval()
+    D = lc["hidden_size"]
+    head = torch.nn.Linear(D, 4)
+    init_module(head, seed, "predictor_head.", cfg["overrides"])
+    obj = types.SimpleNamespace(llm_decoder=m, predictor_head=head)
+    base = load_golden("real_qwen2_t2.npz")
+    rows0 = base["rows0"].tolist()
+    emb0 = base["emb0"]
+    cols = np.sort(np.random.default_rng(78).choice(D, 1024, replace=False))
+    nc = GROUP_CHUNKS
+    out = {"cols": cols.astype(np.int64), "n_chunks": np.array(nc),
+           "hlast": np.zeros((nc, n_sess, D), np.float32), "hcols": np.zeros((nc, n_sess, 2, 1024), np.float32),
+           "hsum": np.zeros((nc, n_sess, 2), np.float64), "hsq": np.zeros((nc, n_sess, 2), np.float64),
+           "probs": np.zeros((nc, n_sess, 3), np.float32), "kvlen": np.zeros((nc, n_sess), np.int64)}
+    insum = 0.0
+    off = np.cumsum([0] + rows0)
+    for b in range(n_sess):
+        e = torch.from_numpy(emb0[off[b]:off[b + 1]].astype(np.float32)).unsqueeze(0)
+        mask = torch.full([1, e.shape[1]], True)
+        h, pkv = AudioLLM._llm_forward_core(obj, {"inputs_embeds": e.half(), "attention_mask": mask, "past_key_values": None})
+        assert np.abs(h[0, -1].numpy() - base["hid0"][b]).max() < 1e-4   # the same prefill as real_qwen2_t2.npz
+        for c in range(nc):
+            x = group_embeds(c, b, D)
+            insum += float(x.astype(np.float64).sum())
+            mask = torch.full([1, pkv.get_seq_length() + 2], True)
+            h, pkv = AudioLLM._llm_forward_core(obj, {"inputs_embeds": torch.from_numpy(x.astype(np.float32)).unsqueeze(0).half(),
+                                                      "attention_mask": mask, "past_key_values": pkv})
+            hv = h[0].numpy().astype(np.float32)
+            out["hlast"][c, b] = hv[-1]
+            out["hcols"][c, b] = hv[:, cols]
+            out["hsum"][c, b] = hv.astype(np.float64).sum(1)
+            out["hsq"][c, b] = (hv.astype(np.float64) ** 2).sum(1)
+            out["probs"][c, b] = AudioLLM._prediction_head_forward(obj, h).numpy()
+            out["kvlen"][c, b] = pkv.get_seq_length()
+        print(f"real qwen2 group session {b}: kv {pkv.get_seq_length()} state probs of the last chunk "
+              f"{[round(float(p), 4) for p in out['probs'][-1, b]]}", flush=True)
+    out["input_sum"] = np.array(insum)
+    parts = save_parts("real_qwen2_group_t2.npz", out)
+    assert all(os.path.getsize(p) <= GOLDEN_PART_LIMIT for p in parts), [os.path.getsize(p) for p in parts]
+    print(f"real qwen2 group: fixture {sum(os.path.getsize(p) for p in parts) / 1e6:.2f} MB in {len(parts)} parts "
+          f"(largest {max(os.path.getsize(p) for p in parts)} bytes), input sum {insum:.6f}")
+
+
 ADAPTER_VARIANTS = [  # CNNSubsampling(enc_out_dim, llm_embed_dim, kernel_size, activation_func, norm)
     {"enc_out_dim": 16, "llm_embed_dim": 128, "kernel_size": 5, "activation_func": "relu", "norm": "batch"},
     {"enc_out_dim": 32, "llm_embed_dim": 128, "kernel_size": 5, "activation_func": "gelu", "norm": "layer"},
@@ -1064,6 +1133,7 @@ def main():
     gold_real_t2()
     gold_real_qwen2()
     gold_real_qwen2_mid()
+    gold_real_qwen2_group()
     gold_adapter_variants(cfg["seed"])
     gold_codec_gst(cfg)
     with open(os.path.join(HERE, "param_shapes_tiny.json"), "w") as f:
@@ -1100,5 +1170,8 @@ if __name__ == "__main__":
     elif sys.argv[1:] == ["real_qwen2_mid"]:
         install_shims()
         gold_real_qwen2_mid()
+    elif sys.argv[1:] == ["real_qwen2_group"]:
+        install_shims()
+        gold_real_qwen2_group()
     else:
         main()

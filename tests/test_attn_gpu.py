@@ -191,3 +191,75 @@ def test_long_sequence_prefill_splits_stay_within_the_page_table(dev, kps):
             sc = K[kh, :nvis[t]] @ qd[t, h * hd:(h + 1) * hd] * scale
             ref = torch.softmax(sc, 0) @ V[kh, :nvis[t]]
             torch.testing.assert_close(static[t, h * hd:(h + 1) * hd].cpu().double(), ref, atol=2e-5, rtol=1e-4)
+
+
+# ------------------------------------------------------------------ a listen group's chunk-major item table
+GROUP_OLDS = [15, 1, 37, 130, 0, 64, 263, 30]   # keys per session before the group: odd ones put an item across a page
+_group_cases = {}
+
+
+def _group_case(dev, H, KVH, hd):
+    """One group per geometry (pool, queries, kv.GroupMeta tables filled as ListenGroupGraph fills them, and the
+    float64 reference), shared by the split settings; nothing in it is written after this."""
+    if (H, KVH, hd) in _group_cases:
+        return _group_cases[(H, KVH, hd)]
+    from fo.kv import GroupMeta
+    B, To, C, PS, max_keys = 8, 2, 8, 16, 2048
+    n1 = B * To
+    g = torch.Generator().manual_seed(H * 100 + hd)
+    pool = KVPool(1, KVH, hd, 128, PS, dev)
+    pool.k.copy_(torch.randn(pool.k.shape, generator=g))
+    pool.v.copy_(torch.randn(pool.v.shape, generator=g))
+    seqs = [KVSeq(pool) for _ in range(B)]
+    for s, n in zip(seqs, GROUP_OLDS):
+        if n:
+            BatchMeta([(s, n, 0, True)], dev)
+    gm = GroupMeta(B, To, C, H // KVH, max_keys, PS, dev)
+    hbuf = torch.zeros(gm.size, dtype=torch.int32)
+    gm.fill(hbuf.numpy(), seqs, C)
+    gm.buf.copy_(hbuf)
+    assert [s.length for s in seqs] == [n + C * To for n in GROUP_OLDS]
+    meta = gm.metas[C]
+    # what the tables must say, written down independently: row j*n1 + b*To + i is session b's position
+    # old_b + j*To + i and sees the keys up to itself; items in (chunk, session) order, To rows each
+    host = [None] * (C * n1)
+    for j in range(C):
+        for b in range(B):
+            for i in range(To):
+                host[j * n1 + b * To + i] = (b, GROUP_OLDS[b] + j * To + i + 1)
+    assert meta.tok_nvis.cpu().tolist() == [nv for _, nv in host]
+    assert meta.items.cpu().tolist() == [v for j in range(C) for b in range(B) for v in (b, j * n1 + b * To, To)]
+    assert any(nv % PS == 1 for _, nv in host[1::2])   # a 2-token item whose second token opens a new page
+    q = torch.randn(meta.T, H * hd, generator=g).to(dev)
+    ref = _reference(q, pool, seqs, host, H, KVH, hd, 1 / math.sqrt(hd))
+    _group_cases[(H, KVH, hd)] = (pool, seqs, meta, q, ref, max_keys)
+    return _group_cases[(H, KVH, hd)]
+
+
+@pytest.mark.parametrize("H,KVH,hd", [(28, 4, 128), (4, 2, 32)])
+@pytest.mark.parametrize("graph_splits", [True, False])
+def test_attention_chunk_major_group_items(dev, H, KVH, hd, graph_splits):
+    """The item table of a listen group (engine.ListenGroupGraph at the benchmark's 8 chunks per Qwen2 stage): 8
+    sessions of ragged lengths x 8 chunks of 2 tokens in one launch, rows chunk-major ([chunk][session][token]) so a
+    session's 16 rows are not contiguous, the 64 items in (chunk, session) order -- one session's items interleaved
+    with the others' -- and every row seeing the keys up to its own position (tok_nvis = pos + 1), i.e. the keys of
+    the earlier chunks of the same launch too.  The tables are kv.GroupMeta's, the ones the product builds.
+    graph_splits: a captured graph's setting (128-key splits sized per item, at most ops.attn_nsplit of the graph's
+    2048-key capacity, merged in the launch; twice, the tickets back at zero); else one split.  Against the float64
+    _reference at this file's 2e-5 abs / 1e-4 rel."""
+    pool, seqs, meta, q, ref, max_keys = _group_case(dev, H, KVH, hd)
+    T, scale = meta.T, 1 / math.sqrt(hd)
+    ns = ops.attn_nsplit(max_keys, meta.n_items, KVH) if graph_splits else 1
+    assert not graph_splits or ns >= 2   # 64 items x 4 kv heads: 2 splits at most; x 2 kv heads: 4 (279 keys take 3)
+    part_ml = torch.empty(T * H * ns * 2, device=dev) if ns > 1 else None
+    part_o = torch.empty(T * H * ns * hd, device=dev) if ns > 1 else None
+    tickets = torch.zeros(meta.n_items * KVH, dtype=torch.int32, device=dev) if graph_splits else None
+    out = torch.empty(T, H * hd, device=dev)
+    for _ in range(2 if graph_splits else 1):
+        out.fill_(float("nan"))
+        ops.attention(q, T, meta.items, meta.n_items, meta.max_rows, meta.tok_nvis, meta.block_table, pool.PS,
+                      pool.k[0], pool.v[0], H, KVH, hd, scale, ns, part_ml, part_o, out, tickets=tickets,
+                      keys_per_split=128)
+        torch.testing.assert_close(out.cpu().double(), ref, atol=2e-5, rtol=1e-4)
+        if graph_splits:
+            assert int(tickets.abs().sum()) == 0

@@ -224,15 +224,18 @@ def test_real_geometry_encoder_adapter_match_reference(dev):
             close(emb, ref, rtol=2e-3, atol=2e-3 * float(np.abs(ref).max()))
 
 
-@pytest.mark.parametrize("C,one_launch", [(4, True), (3, True), (4, False)])
+@pytest.mark.parametrize("C,one_launch", [(4, True), (3, True), (4, False), (8, True), (7, True)])
 def test_real_geometry_encoder_chunk_groups_match_reference(dev, C, one_launch, monkeypatch):
     """SpeechEncoderEngine.run(chunks=C) (the offline listen's encoder stage, fo.engine.ListenGroupGraph): C
     consecutive chunks of 2 sessions in one pass -- the front end, norms and GEMMs over all C x B x T rows, the rel-pos
     attention chunk by chunk on the ring -- against the reference's chunk-by-chunk outputs: framing A for 20 chunks
     (the 64-frame ring fills and trims inside a group), framing B for 8 chunks across the RelPE wrap (a partial last
     group); then the adapter chunk by chunk on the group's rows.  one_launch: the group's attention as one
-    fo_relpos_attention_chunks launch per layer (default), else one fo_relpos_attention_fused launch per chunk."""
+    fo_relpos_attention_chunks launch per layer (default), else one fo_relpos_attention_fused launch per chunk.
+    C = 8 and 7 (the benchmark's chunks per stage): framing A's 20 chunks as 8 + 8 + 4 and 7 + 7 + 6, framing B's 8 as
+    8 and 7 + 1.  The launch counter asserts which attention form ran."""
     import fo.speech
+    from fo import ops
     from fo.speech import AdapterEngine, SpeechEncoderEngine
     monkeypatch.setattr(fo.speech, "CHUNK_ATTN", one_launch)
     g = load("real_encoder_t2.npz")
@@ -257,8 +260,14 @@ def test_real_geometry_encoder_chunk_groups_match_reference(dev, C, one_launch, 
                 enc.advance(ecs, T)
                 assert pes == [int(g[f"{kind}_pe"][c0 + j])] * B
             bufs["meta"].copy_(torch.from_numpy(np.concatenate(metas)).to(dev))
+            ops.launch_counts_reset()
             out, T2_ = enc.run(f.contiguous(), B, R, bufs, chunks=m)
             assert T2_ == T
+            # the whole group's attention in one launch per layer, not one per chunk (real geometry: the 72-slot
+            # ring holds 8 chunks of 4 or 7 frames)
+            nb = len(enc.layers)
+            if m > 1:
+                assert ops.launch_counts()["relpos"] == (nb if one_launch else nb * m), (kind, c0, m, ops.launch_counts())
             for j in range(m):
                 ref_e, ref_a = g[f"{kind}_enc"][c0 + j], g[f"{kind}_ada"][c0 + j]
                 rows = out[j * B * T:(j + 1) * B * T]
@@ -458,7 +467,7 @@ def test_grouped_encoder_pass_equals_chunk_by_chunk(dev, kind):
     seq, grp = [enc.new_cache() for _ in range(B)], [enc.new_cache() for _ in range(B)]
     pe_s, pe_g = [0] * B, [0] * B
     worst = 0.0
-    for m in (4, 4, 2, 4):
+    for m in (4, 4, 2, 4, 8, 7):
         feats = [torch.from_numpy((rng.standard_normal((B, R, 80)) * 3).astype(np.float32)).to(dev) for _ in range(m)]
         want = []
         for j in range(m):

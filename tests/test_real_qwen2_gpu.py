@@ -218,3 +218,126 @@ def test_qwen2_real_geometry_17_to_64_row_steps_match_reference(dev, llm, gold):
         for q in seqs:
             q.free()
     assert llm.pool.pages_in_use() == 0
+
+
+# ------------------------------------------------------------------ listen groups (C chunks per Qwen2 stage)
+def _group_embeds(chunk, b, D=3584):
+    """tests/golden/make_golden.py group_embeds: the fp16-valued inputs of the listen chunks (regenerated, checksummed)."""
+    return (np.random.default_rng(8765 + 100 * chunk + b).standard_normal((2, D)) * 0.5).astype(np.float16)
+
+
+@pytest.mark.parametrize("C", [8, 4, 1])
+def test_qwen2_real_geometry_listen_groups_match_reference(dev, llm, gold, C):
+    """real_qwen2_group_t2.npz (make_golden.py real_qwen2_group: 15 consecutive 2-row chunks per session fed one call
+    at a time to the reference's _llm_forward_core / _prediction_head_forward after the 9 + 2b-row prefill, each
+    session its own DynamicCache) against the Qwen2 stage of engine.ListenGroupGraph at C chunks per stage, driven
+    through the product's own tables (kv.GroupMeta: chunk-major rows, (chunk, session) items, decision rows, the
+    tok_pos / tok_slot / tok_nvis / block-table fill), workspace and split count sized as _listen_graph_for sizes
+    them, every distinct m captured with ListenGraph._capture on the engine stream and replayed.
+      C = 8: groups of 8 + 7 chunks, M = 128 and 112 -- the benchmark's listen: the 65..128-row k_gemm_rows family on
+             all four GEMMs of a layer, 64 / 56 attention items whose later chunks read the keys the earlier ones
+             append in the same forward, 64 / 56 state-head rows;
+      C = 4: 4 + 4 + 4 + 3, M = 64 and 48 -- the split-K 17..64-row family;
+      C = 1: fifteen single chunks -- the control: golden and harness agree where nothing is grouped.
+    The odd prefill lengths put a chunk across a 16-token KV page at a different chunk in each session.  The launch
+    counters (read around each capture: a captured graph counts at capture) pin the kernel families, so a policy
+    change cannot route around this test.  Tolerances as the other real-geometry steps: hidden 2e-3 abs (each
+    chunk's whole last row, both rows at 1024 fixed columns, both rows' sum / sum of squares over all 3584 columns at
+    2e-3 x sqrt(3584) / relative 1e-4), state probs 5e-4 for every chunk of every session, KV lengths exact after
+    every group, the regenerated inputs' checksum to 1e-6 relative."""
+    from fo import _lib, ops
+    from fo.engine import ListenGraph, _HostRing
+    from fo.kv import GroupMeta
+    grp = load_golden("real_qwen2_group_t2.npz")
+    lib = _lib.load()
+    assert lib.fo_gemm_set_pipe(3) >= -1   # the default policy (what the bench runs)
+    B, To, D = 8, 2, llm.D
+    NC = int(grp["n_chunks"])
+    assert NC == 15
+    n1, nl = B * To, len(llm.stack.layers)
+    cols = grp["cols"]
+    rows0 = gold["rows0"].tolist()
+    seqs = [llm.new_seq() for _ in range(B)]
+    main = ops.engine_stream(dev)
+    execs, ring = {}, None
+    insum, worst = 0.0, {}   # m: [hidden, state prob] worst deviations
+    try:
+        x0 = torch.from_numpy(gold["emb0"].astype(np.float32)).to(dev)
+        h, bm = llm.forward(x0, [(q, r) for q, r in zip(seqs, rows0)])
+        _close(h[bm.last_rows_host], gold["hid0"], 2e-3, 0, "prefill last rows")
+        torch.cuda.synchronize()
+        # EngineCore._listen_graph_for as ListenPipe._push_group calls it (extra = 64 * 2 * C), ListenGroupGraph.__init__
+        max_keys = max(max(q.length for q in seqs) + 64 * 2 * C + 1024, 2048)
+        gm = GroupMeta(B, To, C, llm.H // llm.KVH, max_keys, llm.pool.PS, dev)
+        x = torch.empty(C * n1, D, dtype=torch.float32, device=dev)
+        ws = llm.stack.workspace(C * n1, ops.attn_nsplit(max_keys, C * B, llm.KVH), dev)
+        probs = torch.empty(C * B, 3, dtype=torch.float32, device=dev)
+        ring = _HostRing(gm.size)
+        with torch.cuda.stream(main):
+            ops.Runtime.get(dev)   # the engine stream's GEMM scratch exists before anything is captured on it
+
+        def body(m):   # ListenGroupGraph._llm_body
+            xm = x[:m * n1]
+            llm.stack.forward(xm, gm.metas[m], ws)
+            ops.rmsnorm(xm, llm.norm, llm.eps, out=xm)
+            ops.state_head(xm, gm.rows[:m * B], llm.head_w, llm.head_b, probs)
+
+        for c0 in range(0, NC, C):
+            m = min(C, NC - c0)
+            M = m * n1
+            what = f"C = {C}, chunks {c0}..{c0 + m - 1} (M = {M})"
+            if m not in execs:
+                ops.launch_counts_reset()
+                execs[m] = ListenGraph._capture(main, lambda: body(m))
+                c = ops.launch_counts()
+                print(f"[listen groups] {what} launches { {k: v for k, v in c.items() if v} }")
+                assert c["attn_mfma"] == nl and c["attn_decode"] == 0, (what, c)
+                if M > 64:    # 65..128 rows: q|k|v, o, gate/up and down (each >= 16 MiB of weights) on k_gemm_rows
+                    assert c["gemm_rows"] == 4 * nl and c["gemm_xsk"] == 0, (what, c)
+                elif M > 16:  # 17..64 rows: the split-K family, as the 17..64-row test above pins it
+                    assert c["gemm_xsk"] == 2 * nl and c["gemm_rope4"] == nl and c["gemm_rows"] == 0, (what, c)
+                    assert c["gemm_xp"] >= 2 * nl - 1 and c["gemm_ypack"] >= 2 * nl - 1, (what, c)
+                    assert c["attn_opack"] == nl, (what, c)
+                else:         # one chunk: neither of the many-row families
+                    assert c["gemm_rows"] == 0 and c["gemm_xsk"] == 0, (what, c)
+            xs = np.empty((M, D), np.float16)
+            for j in range(m):
+                for b in range(B):
+                    e = _group_embeds(c0 + j, b)
+                    insum += float(e.astype(np.float64).sum())
+                    xs[j * n1 + b * To:j * n1 + (b + 1) * To] = e   # chunk-major: [chunk][session][token]
+            k, hb = ring.next()
+            gm.fill(hb, seqs, m)
+            with torch.cuda.stream(main):
+                x[:M].copy_(torch.from_numpy(xs.astype(np.float32)), non_blocking=False)
+            ring.upload(k, gm.buf, main)
+            _lib.call("fo_graph_launch", execs[m], main.cuda_stream)
+            main.synchronize()
+            assert [q.length for q in seqs] == grp["kvlen"][c0 + m - 1].tolist(), what
+            hv = x[:M].cpu().numpy().reshape(m, B, To, D)
+            h64 = hv.astype(np.float64)
+            want = slice(c0, c0 + m)
+            w = worst.setdefault(m, [0.0, 0.0])
+            w[0] = max(w[0], float(np.abs(hv[:, :, -1] - grp["hlast"][want]).max()),
+                       float(np.abs(hv[..., cols] - grp["hcols"][want]).max()))
+            _close(hv[:, :, -1], grp["hlast"][want], 2e-3, 0, f"{what} last rows")
+            _close(hv[..., cols], grp["hcols"][want], 2e-3, 0, f"{what} hidden at fixed columns")
+            np.testing.assert_allclose(h64.sum(-1), grp["hsum"][want], atol=2e-3 * 3584 ** 0.5, err_msg=f"{what} row sums")
+            np.testing.assert_allclose((h64 ** 2).sum(-1), grp["hsq"][want], rtol=1e-4, err_msg=f"{what} row sumsq")
+            p = probs[:m * B].cpu().numpy().reshape(m, B, 3)
+            w[1] = max(w[1], float(np.abs(p - grp["probs"][want]).max()))
+            _close(p, grp["probs"][want], 5e-4, 0, f"{what} state probs")
+        for m, w in worst.items():
+            print(f"[listen groups] C = {C}, groups of {m}: worst hidden deviation {w[0]:.2e}, state probs {w[1]:.2e}")
+        assert sorted(execs) == sorted({min(C, NC - c0) for c0 in range(0, NC, C)})
+        assert abs(insum - float(grp["input_sum"])) < 1e-6 * max(1.0, abs(insum)), (insum, float(grp["input_sum"]))
+        assert [q.length for q in seqs] == [r + 2 * NC for r in rows0]
+    finally:
+        torch.cuda.synchronize()
+        for ex in execs.values():
+            _lib.call("fo_graph_destroy", ex)
+        if ring is not None:
+            ring.destroy()
+        for q in seqs:
+            q.free()
+    assert llm.pool.pages_in_use() == 0
