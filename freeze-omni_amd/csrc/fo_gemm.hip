@@ -918,25 +918,25 @@ inline int pipe_mode() {
   }
   return g_pipe;
 }
-// the pipelining fo_gemm chose for the launch it is issuing (0 none, 1 U-step, 2 two-step groups)
-thread_local int g_launch_pipe = 0;
 template <int NT, int RB, int NW, int U = 4>
 __global__ __launch_bounds__(NW * 64) void k_gemm_ln(GemmArgs a) {
   gemm_body<NT, RB, true, NW, U, false, true>(a);
 }
 
+// pipe: the pipelining the dispatcher chose for this launch (0 none, 1 U-step, 2 two-step groups; one-row-tile
+// fp32-X launches only)
 template <int NT, int RB, int NW, int U, bool SW>
-void launch_gemm(bool wstream, bool x_f32, dim3 grid, const GemmArgs& a, hipStream_t s) {
+void launch_gemm(int pipe, bool wstream, bool x_f32, dim3 grid, const GemmArgs& a, hipStream_t s) {
   const size_t shm = 0;
   if constexpr (RB <= 4 && !SW) {
-    if (x_f32 && a.xph && !(RB == 1 && g_launch_pipe)) {   // X packed by its producer
+    if (x_f32 && a.xph && !(RB == 1 && pipe)) {   // X packed by its producer
       hipLaunchKernelGGL((k_gemm_xp<NT, RB, NW, U>), grid, dim3(NW * 64), shm, s, a);
       return;
     }
   }
   if constexpr (RB == 1) {
-    if (x_f32 && g_launch_pipe) {
-      if (g_launch_pipe == 2) hipLaunchKernelGGL((k_gemm_wpipe<NT, RB, NW, 2, SW>), grid, dim3(NW * 64), shm, s, a);
+    if (x_f32 && pipe) {
+      if (pipe == 2) hipLaunchKernelGGL((k_gemm_wpipe<NT, RB, NW, 2, SW>), grid, dim3(NW * 64), shm, s, a);
       else hipLaunchKernelGGL((k_gemm_wpipe<NT, RB, NW, U, SW>), grid, dim3(NW * 64), shm, s, a);
       return;
     }
@@ -950,7 +950,7 @@ void launch_gemm(bool wstream, bool x_f32, dim3 grid, const GemmArgs& a, hipStre
   }
 }
 
-// 17..64-row fp32-X grid kernels (gemm_impl's mid path): X packed by its producer takes k_gemm_xp
+// 17..64-row fp32-X grid kernels (launch_grid_mid): X packed by its producer takes k_gemm_xp
 template <int NT, int RB, int NW, bool SW>
 void launch_mid(dim3 grid, const GemmArgs& a, hipStream_t s) {
   if constexpr (!SW) {
@@ -963,14 +963,6 @@ void launch_mid(dim3 grid, const GemmArgs& a, hipStream_t s) {
 }
 
 thread_local unsigned long long* g_trc = nullptr;  // fo_gemm_set_trace (probes)
-int g_xs_var = -1;   // fo_gemm_set_xs_variant (probes); -1: FO_XS_VARIANT (0-4) decides at first use, default 0
-inline int xs_variant() {
-  if (g_xs_var < 0) {
-    const char* e = getenv("FO_XS_VARIANT");
-    g_xs_var = (e && e[0] >= '0' && e[0] <= '4') ? e[0] - '0' : 0;
-  }
-  return g_xs_var;
-}
 // packed activations armed for the calling thread's next launch, with their extent (cols, allocated row blocks)
 struct PackArm {
   const void* p0 = nullptr;
@@ -998,34 +990,18 @@ inline int arm_pack(PackArm& g, const void* p0, const void* p1, bool two, int co
 
 // forced (waves, tiles per workgroup) of the M <= 16 kernels; 0 = automatic (sweeps only)
 thread_local int g_force_nw = 0, g_force_nt = 0;
-// k-steps in flight per wave of the one-row-tile fp32-X grid kernel: 4 (default), 7 on 16 waves or 8 on 8
-// waves (every k-step of a wave's K range in one round when waves x U covers K: the Qwen2 o / q|k|v
-// projections, K = 3584 = 16 x 7 x 32); 0 = the policy in gemm_impl
-thread_local int g_force_u = 0;
-thread_local int g_launch_u = 4;
 
+// the one- and two-row-tile grid kernels on nw waves, 4 k-steps of weights in flight per wave
 template <int NT, int RB, bool SW>
-void launch_nw(int nw, bool wstream, bool x_f32, dim3 grid, const GemmArgs& a, hipStream_t s) {
-  if constexpr (RB == 1 && NT <= 2) {
-    if (g_launch_u != 4 && x_f32 && !g_launch_pipe) {
-      if constexpr (NT == 1) {  // (2 tiles x 7 k-steps on 16 waves spill past the 128-VGPR budget: 8 x 8 instead)
-        if (g_launch_u == 7) {
-          hipLaunchKernelGGL((k_gemm<1, 1, true, 16, 7, SW>), grid, dim3(1024), 0, s, a);
-          return;
-        }
-      }
-      hipLaunchKernelGGL((k_gemm<NT, 1, true, 8, 8, SW>), grid, dim3(512), 0, s, a);
-      return;
-    }
-  }
+void launch_nw(int nw, int pipe, bool wstream, bool x_f32, dim3 grid, const GemmArgs& a, hipStream_t s) {
   if constexpr (NT >= 7) {  // 7-8 tiles x 16 waves exceed the 128-VGPR budget of a 1024-thread group
     if (nw == 16) nw = 8;
   } else if (nw == 16) {
-    launch_gemm<NT, RB, 16, 4, SW>(wstream, x_f32, grid, a, s);
+    launch_gemm<NT, RB, 16, 4, SW>(pipe, wstream, x_f32, grid, a, s);
     return;
   }
-  if (nw == 8) launch_gemm<NT, RB, 8, 4, SW>(wstream, x_f32, grid, a, s);
-  else launch_gemm<NT, RB, 4, 4, SW>(wstream, x_f32, grid, a, s);
+  if (nw == 8) launch_gemm<NT, RB, 8, 4, SW>(pipe, wstream, x_f32, grid, a, s);
+  else launch_gemm<NT, RB, 4, 4, SW>(pipe, wstream, x_f32, grid, a, s);
 }
 
 // X-stationary weight stream for M <= 16 fp32 rows and K = NW * KPW * 32 (Qwen2: K = 3584 = 16 x 7 x 32).
@@ -1039,22 +1015,14 @@ void launch_nw(int nw, bool wstream, bool x_f32, dim3 grid, const GemmArgs& a, h
 //    buffered -- the next unit's loads are issued right after the MFMAs that free a buffer;
 //  * per unit the NW partial tiles are reduced through LDS (two barriers), then the epilogue of the
 //    row-major output (the post-scaled RMSNorm and SwiGLU) as in gemm_body.
-// 16 waves x 7 k-steps (round 5, scripts/xs_variant_probe.py: 47.0-47.3 us per 271.6 MB launch against 48.6-49.5 us
-// for round 4's 8 x 14, graph-replayed over cold weight copies); FO_XS_VARIANT=3 runs the 8 x 14 shape
+// 16 waves x 7 k-steps (round 5: 47.0-47.3 us per 271.6 MB launch against 48.6-49.5 us for round 4's 8 x 14,
+// graph-replayed over cold weight copies)
 constexpr int XS_NW = 16, XS_KPW = 7;
-// VAR (probes, fo_gemm_set_xs_variant): bit 0 = no cross-wave reduction (wave 0's partial is stored: WRONG
-// results, the barrier-free bound), bit 1 = default cache policy on the weight loads instead of nt, bit 2 = the
-// cross-wave reduction without workgroup barriers: per-unit partial slots double-buffered by unit parity, an LDS
-// arrival counter per slot; the wave that arrives last sums the NW partials in wave order (the same order, so the
-// same bits as the barrier form) and runs the unit's epilogue while the other waves stream on; a wave reuses a slot
-// only once the reduction two units back has been consumed (LDS generation word)
-template <int NW, int KPW, int VAR = 0>  // the SwiGLU pair (gate, up) of one 16-column output tile per unit
+template <int NW, int KPW>  // the SwiGLU pair (gate, up) of one 16-column output tile per unit
 __global__ __launch_bounds__(NW * 64) void k_gemm_xs(GemmArgs a, int units) {
-  constexpr bool BF = (VAR & 4) != 0;
   __shared__ bf16x8 xlo[NW][KPW][64];
-  __shared__ float part[BF ? 2 : 1][NW][2][16][17];
+  __shared__ float part[NW][2][16][17];
   __shared__ float rstd_s[16];
-  __shared__ int arr_s[2], gen_s[2];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   constexpr int KS = NW * KPW;
   const int ub = (int)((long)units * blockIdx.x / gridDim.x);
@@ -1071,8 +1039,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemm_xs(GemmArgs a, int units) {
   auto issue = [&](bf16x8 (&w)[KPW], int tile) {
 #pragma unroll
     for (int j = 0; j < KPW; ++j)
-      w[j] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(srd, voff, (tile * KS + j) * 1024,
-                                                                               (VAR & 2) ? 0 : 2));
+      w[j] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(srd, voff, (tile * KS + j) * 1024, 2));
   };
   issue(w0, ub < ue ? 2 * ub : a.ntiles);
   issue(w1, ub < ue ? 2 * ub + 1 : a.ntiles);
@@ -1125,13 +1092,6 @@ __global__ __launch_bounds__(NW * 64) void k_gemm_xs(GemmArgs a, int units) {
       if (lane == 0) rstd_s[rr] = rsqrtf(v / (float)a.K + a.reps);
     }
   }
-  if constexpr (BF) {
-    if (threadIdx.x < 2) {
-      arr_s[threadIdx.x] = 0;
-      gen_s[threadIdx.x] = 0;
-    }
-    __syncthreads();   // rstd_s and the counters, once (the only workgroup barrier of this form)
-  }
   auto compute = [&](bf16x8 (&w)[KPW]) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1150,70 +1110,21 @@ __global__ __launch_bounds__(NW * 64) void k_gemm_xs(GemmArgs a, int units) {
     issue(w0, nxt);
     const f32x4 c1 = compute(w1);
     issue(w1, nxt + (u + 1 < ue ? 1 : 0));
-    if constexpr ((VAR & 1) != 0) {   // probe: no cross-wave reduction (the barrier-free bound; wrong results)
-      if (wave == 0 && lane < 16)
-        for (int i = 0; i < 4; ++i)
-          if (4 * 0 + i < a.M) epilogue_store(a, true, i, u * 16 + lane, c0[i], c1[i]);
-      continue;
-    }
-    if constexpr (BF) {
-      const int k = u - ub, sl = k & 1;
-      // the slot's previous unit (k - 2) must have been reduced: its reducer bumps gen_s[sl] once done reading
-      if (k >= 2) {
-        while (__hip_atomic_load(&gen_s[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < (k >> 1))
-          __builtin_amdgcn_s_sleep(1);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        part[sl][wave][0][4 * (lane >> 4) + i][lane & 15] = c0[i];
-        part[sl][wave][1][4 * (lane >> 4) + i][lane & 15] = c1[i];
-      }
-      // LDS only: a wave's ds operations execute in order, so its partial writes land before its counter add; the
-      // asm orders the compiler and waits for them (no vmcnt wait: the weight loads stay in flight)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      int old = 0;
-      if (lane == 0) old = __hip_atomic_fetch_add(&arr_s[sl], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      old = __builtin_amdgcn_readfirstlane(old);
-      if (old != NW - 1) continue;   // another wave reduces this unit
-      asm volatile("" ::: "memory");
-      if (lane == 0) __hip_atomic_store(&arr_s[sl], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      // this wave: the unit's 16 x 16 outputs, 4 per lane (rows 4 (lane >> 4) .. + 3, column lane & 15)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int rr = 4 * (lane >> 4) + i, c = lane & 15;
-        float x1 = 0.f, x2 = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-          x1 += part[sl][w][0][rr][c];
-          x2 += part[sl][w][1][rr][c];
-        }
-        if (a.rstats) {
-          x1 *= rstd_s[rr];
-          x2 *= rstd_s[rr];
-        }
-        const int n = u * 16 + c;
-        if (rr < a.M && n < a.N) epilogue_store(a, true, rr, n, x1, x2);
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the partial reads are done: the slot is free
-      if (lane == 0) __hip_atomic_fetch_add(&gen_s[sl], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      continue;
-    } else {
     __syncthreads();  // the previous unit's epilogue has read part[]
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      part[0][wave][0][4 * (lane >> 4) + i][lane & 15] = c0[i];
-      part[0][wave][1][4 * (lane >> 4) + i][lane & 15] = c1[i];
+      part[wave][0][4 * (lane >> 4) + i][lane & 15] = c0[i];
+      part[wave][1][4 * (lane >> 4) + i][lane & 15] = c1[i];
     }
     __syncthreads();
-    }
     const int e = threadIdx.x;
     if (e < 256) {
       const int rr = e >> 4, c = e & 15;
       float x1 = 0.f, x2 = 0.f;
 #pragma unroll
       for (int w = 0; w < NW; ++w) {
-        x1 += part[0][w][0][rr][c];
-        x2 += part[0][w][1][rr][c];
+        x1 += part[w][0][rr][c];
+        x2 += part[w][1][rr][c];
       }
       if (a.rstats) {
         x1 *= rstd_s[rr];
@@ -1223,164 +1134,6 @@ __global__ __launch_bounds__(NW * 64) void k_gemm_xs(GemmArgs a, int units) {
       if (rr < a.M && n < a.N) epilogue_store(a, true, rr, n, x1, x2);
     }
   }
-}
-
-// ---- probe (verdict r04 item 4: where a persistent layer would win or lose): the o -> gate/up seam of a Qwen2 layer
-// at <= 16 rows as ONE launch.  Workgroups [0, n_o) are the o projection (one tile pair each, 8 waves x 14 k-steps
-// over K = 3584, + residual, writing Y, yg = Y * gamma_next and the row's sum of squares per pair), then publish
-// (release fence + relaxed add on `ready`); workgroups [n_o, n_o + G) are k_gemm_xs's gate/up stream: they issue
-// their first two tiles' weights, then wave 0 polls `ready` (acquire; a bounded poll: past ~0.1 s the launch
-// proceeds and flags *ready_timeout, so a broken producer cannot hang the GPU), then the X slice (yg) and the rstd
-// from the o workgroups' partials, and the unit loop.  The dispatcher places workgroups in id order, so every o
-// workgroup is resident before any gate/up workgroup waits, and none of them waits on anything: the poll always ends.
-// Per-workgroup wall clocks (trc[4 w + 0..3]: start, weights of the first units issued / o reduced, ready seen /
-// o stored, end).  Same math as the two launches (o reduced in a different K order: ~1 ulp differences).
-__global__ __launch_bounds__(512) void k_seam_o_gu(GemmArgs ao, GemmArgs ag, int n_o, int units, int G, int* ready,
-                                                   int* ready_timeout, unsigned long long* trc) {
-  constexpr int NW = 8, KPW = 14, KS = NW * KPW;
-  __shared__ bf16x8 xlo[NW][KPW][64];
-  __shared__ float part[NW][2][16][17];
-  __shared__ float rstd_s[16];
-  __shared__ float rs_s[16][2];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int wg = blockIdx.x;
-  unsigned long long* tr = trc ? trc + (size_t)wg * 4 : nullptr;
-  if (tr && threadIdx.x == 0) tr[0] = wall_clock64();
-  const bool is_o = wg < n_o;
-  const GemmArgs& a = is_o ? ao : ag;
-  const unsigned long long wbase = (unsigned long long)a.Wp;
-  const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(
-      reinterpret_cast<void*>(((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(wbase >> 32)) << 32) |
-                              (unsigned)__builtin_amdgcn_readfirstlane((unsigned)wbase)),
-      (short)0, __builtin_amdgcn_readfirstlane(a.ntiles * KS * 1024), 0x00020000);
-  const int voff = (wave * KPW * 64 + lane) * 16;
-  bf16x8 w0[KPW], w1[KPW];
-  auto issue = [&](bf16x8 (&w)[KPW], int tile) {
-#pragma unroll
-    for (int j = 0; j < KPW; ++j)
-      w[j] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(srd, voff, (tile * KS + j) * 1024, 2));
-  };
-  const int gj = wg - n_o;
-  const int ub = is_o ? wg : (int)((long)units * gj / G);
-  const int ue = is_o ? wg + 1 : (int)((long)units * (gj + 1) / G);
-  issue(w0, ub < ue ? 2 * ub : a.ntiles);
-  issue(w1, ub < ue ? 2 * ub + 1 : a.ntiles);
-  if (!is_o) {   // wait for every o workgroup's stores (bounded)
-    if (threadIdx.x == 0) {
-      long spins = 0;
-      while (__hip_atomic_load(ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < n_o) {
-        __builtin_amdgcn_s_sleep(2);
-        if (++spins > (1l << 22)) {
-          *ready_timeout = 1;
-          break;
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      if (tr) tr[2] = wall_clock64();
-    }
-    __syncthreads();
-  }
-  // X slice of this wave's k-steps (o: the attention output; gate/up: yg), hi in VGPRs, lo in LDS
-  bf16x8 xh[KPW];
-  {
-    const int row = min(lane & 15, a.M - 1);
-    const float* xp = reinterpret_cast<const float*>(a.X) + (size_t)row * a.ldx + 8 * (lane >> 4) + (size_t)wave * KPW * 32;
-#pragma unroll
-    for (int j = 0; j < KPW; ++j) {
-      const float4 p0 = reinterpret_cast<const float4*>(xp + j * 32)[0];
-      const float4 p1 = reinterpret_cast<const float4*>(xp + j * 32)[1];
-      const float f[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
-      bf16x8 lo;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const __bf16 h = (__bf16)f[i];
-        xh[j][i] = h;
-        lo[i] = (__bf16)(f[i] - (float)h);
-      }
-      xlo[wave][j][lane] = lo;
-    }
-  }
-  if (!is_o) {   // rstd of each row from the o workgroups' partial sums of squares
-    for (int rr = wave; rr < 16; rr += NW) {
-      const int m = min(rr, a.M - 1);
-      float v = 0.f;
-      for (int j = lane; j < a.rgroups; j += 64) v += a.rstats[(size_t)m * a.rgroups + j];
-      v = wave_sum(v);
-      if (lane == 0) rstd_s[rr] = rsqrtf(v / (float)a.K + a.reps);
-    }
-  }
-  auto compute = [&](bf16x8 (&w)[KPW]) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < KPW; ++j) {
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[j], w[j], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xlo[wave][j][lane], w[j], acc, 0, 0, 0);
-    }
-    return acc;
-  };
-  for (int u = ub; u < ue; ++u) {
-    const int nxt = u + 1 < ue ? 2 * (u + 1) : a.ntiles;
-    const f32x4 c0 = compute(w0);
-    issue(w0, nxt);
-    const f32x4 c1 = compute(w1);
-    issue(w1, nxt + (u + 1 < ue ? 1 : 0));
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      part[wave][0][4 * (lane >> 4) + i][lane & 15] = c0[i];
-      part[wave][1][4 * (lane >> 4) + i][lane & 15] = c1[i];
-    }
-    __syncthreads();
-    if (is_o && tr && threadIdx.x == 0) tr[1] = wall_clock64();
-    const int e = threadIdx.x;
-    if (e < 512) {
-      const int t = e >> 8, rr = (e >> 4) & 15, c = e & 15;   // o: both tiles of the pair; gate/up: the SwiGLU pair
-      float x1 = 0.f, x2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        x1 += part[w][is_o ? t : 0][rr][c];
-        x2 += part[w][1][rr][c];
-      }
-      if (is_o) {
-        const int n = (2 * u + t) * 16 + c;
-        float y = 0.f;
-        if (rr < a.M && n < a.N) {
-          const size_t o = (size_t)rr * a.ldy + n;
-          y = x1 + (a.bias ? a.bias[n] : 0.f) + reinterpret_cast<float*>(a.Y)[o];
-          reinterpret_cast<float*>(a.Y)[o] = y;
-          a.yg[o] = y * a.gnext[n];
-        }
-        // the row's sum of squares over this pair's 32 columns: 16 lanes of each tile's row, then the two tiles
-        float q = y * y;
-#pragma unroll
-        for (int off = 8; off > 0; off >>= 1) q += __shfl_xor(q, off, 16);
-        if (c == 0) rs_s[rr][t] = q;
-      } else if (e < 256) {
-        if (a.rstats) {
-          x1 *= rstd_s[rr];
-          x2 *= rstd_s[rr];
-        }
-        const int n = u * 16 + c;
-        if (rr < a.M && n < a.N) epilogue_store(a, true, rr, n, x1, x2);
-      }
-    }
-    if (is_o) {
-      __syncthreads();
-      if (threadIdx.x < 16 && (int)threadIdx.x < a.M)
-        a.sout[(size_t)threadIdx.x * n_o + wg] = rs_s[threadIdx.x][0] + rs_s[threadIdx.x][1];
-    }
-  }
-  if (is_o) {   // publish
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      if (tr) tr[2] = wall_clock64();
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_fetch_add(ready, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  if (tr && threadIdx.x == 0) tr[3] = wall_clock64();
 }
 
 // X-stationary weight stream for 17..64 fp32 rows (RB = 2..4 row blocks): k_gemm_xs's design with the K range
@@ -1535,8 +1288,8 @@ __global__ __launch_bounds__(NW * 64) void k_gemm_xsk(GemmArgs a, int units, int
 // (wave w: row blocks RPW w .. RPW w + RPW - 1; shipped: 8 waves x 1 row block) and share each k-step's weight
 // fragments through LDS, so there is no cross-wave reduction and each weight byte is read from HBM once:
 //  * one LDS-DMA loader ring per workgroup (global_load_lds_dwordx4, issued by every wave for its share): DW k-steps
-//    of the workgroup's NTC weight tiles ahead, DX k-steps of its fp32 X rows ahead (X comes from L2; XL = 1: each X
-//    load fetches 8 whole rows, laid out so the consumers' reads stay conflict-free);
+//    of the workgroup's NTC weight tiles ahead, DX k-steps of its fp32 X rows ahead (X comes from L2; each X load
+//    fetches 8 whole rows, laid out so the consumers' reads stay conflict-free);
 //  * per k-step: one s_waitcnt on this wave's own DMA (the count of the DX - 1 younger k-steps' loads, fixed by
 //    padding every k-step to the same number of loads), one workgroup barrier (every wave's loads landed, and every
 //    wave is past the slot the next loads overwrite), then the wave's X fragment split into bf16 hi / lo and
@@ -1544,7 +1297,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemm_xsk(GemmArgs a, int units, int
 //  * workgroups = S K-splits x G tile groups (XCD-aware as k_gemm_xsk); each writes its fp32 partial tiles to split
 //    sp's slab and k_gemm_reduce (the next launch) sums the slabs in split order and runs every epilogue (SwiGLU, the
 //    RMSNorm rstd, residual, row statistics).  A workgroup's X over its K range passes through the CU beside its
-//    weights, so the host splits K until the two are comparable (gemm_impl: gate/up thirds, down 16 slices).
+//    weights, so the host splits K until the two are comparable (plan_rows: gate/up thirds, down 16 slices).
 // The loads are asm (the compiler's own wait placement treats an LDS-DMA as aliasing every later LDS read and drains
 // the whole ring before each one); nothing else in the loop touches vector memory, so the manual counts are exact.
 // (dma16 / lds_addr / wait_vm: fo_common.h)
@@ -1555,15 +1308,11 @@ __device__ __forceinline__ void wait_vm_barrier() {
   asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"i"(N) : "memory");
 }
 
-// PROBE (fo_gemm_set_rows 4 / 5, WRONG results, timing bounds): 1 = no X loads (the weight stream alone), 2 = no loads
-// XL: the X DMA's lane -> (row, 16-B chunk) map.  0: lane l fetches row l & 15, chunks 2 (l >> 4) + h of the k-step
-// (each load touches 16 rows x half a line); 1: load h fetches rows 8 h .. 8 h + 7 whole (8 full 128-B lines), lane
+// The X DMA's lane -> (row, 16-B chunk) map: load h fetches rows 8 h .. 8 h + 7 whole (8 full 128-B lines), lane
 // f = 8 c + (r & 7) + 8 h (mod 64) holding chunk c of row r, which keeps the consumer's two ds_read_b128 free of
-// bank conflicts (its 16-lane groups read 16 consecutive 16-B slots)
-// CM: the consumer map.  0: wave w computes row block w (RPW of them) for every tile; 1 (8 waves, RPW 1): wave w
-// computes row blocks 2 (w & 3) and 2 (w & 3) + 1 for half the tiles (w >> 2) -- each weight fragment is read from LDS
-// by 4 waves instead of 8 (the loads are distributed as for CM 0)
-template <int NWV, int RPW, int NTC, int DW, int DX, bool WNT = false, int PROBE = 0, int XL = 0, int CM = 0>
+// bank conflicts (its 16-lane groups read 16 consecutive 16-B slots).  Wave w computes row block w (RPW of them) for
+// every tile.
+template <int NWV, int RPW, int NTC, int DW, int DX>
 __global__ __launch_bounds__(NWV * 64) void k_gemm_rows(GemmArgs a, int G, int tiles_per) {
   constexpr int RB = NWV * RPW;
   constexpr int LPW = (NTC + NWV - 1) / NWV;   // weight loads per wave per k-step (tile t: wave t % NWV)
@@ -1590,21 +1339,13 @@ __global__ __launch_bounds__(NWV * 64) void k_gemm_rows(GemmArgs a, int G, int t
   for (int r = 0; r < RPW; ++r)
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
-      if constexpr (XL == 0) {
-        const int row = min((wave * RPW + r) * 16 + (lane & 15), a.M - 1);
-        xrow[r][hf] = xbase + (size_t)row * a.ldx + 8 * (lane >> 4) + 4 * hf;
-      } else {
-        const int row = min((wave * RPW + r) * 16 + 8 * hf + (lane & 7), a.M - 1);
-        const int c = ((lane >> 3) - hf) & 7;
-        xrow[r][hf] = xbase + (size_t)row * a.ldx + 4 * c;
-      }
+      const int row = min((wave * RPW + r) * 16 + 8 * hf + (lane & 7), a.M - 1);
+      const int c = ((lane >> 3) - hf) & 7;
+      xrow[r][hf] = xbase + (size_t)row * a.ldx + 4 * c;
     }
   // the consumer's two LDS slots (16-B lanes of the two loads' images)
   int xs0, xs1, xh0;
-  if constexpr (XL == 0) {
-    xh0 = 0;
-    xs0 = xs1 = lane;
-  } else {
+  {
     const int r = lane & 15, q = lane >> 4, h = r >> 3;
     xh0 = h;
     xs0 = (16 * q + (r & 7) + 8 * h) & 63;
@@ -1614,20 +1355,18 @@ __global__ __launch_bounds__(NWV * 64) void k_gemm_rows(GemmArgs a, int G, int t
   const void* dummy_g = wbase + (size_t)lane * 16;
   // weights of k-step i (relative to kb) into ring slot i % PW: this wave's tiles wave, wave + NWV, ...
   auto issue_w = [&](int i) {
-    if constexpr (PROBE == 2) return;
 #pragma unroll
     for (int q = 0; q < LPW; ++q) {
       const int t = q * NWV + wave;
       if (i < nk && t < nt && t < NTC) {
         const void* src = wbase + ((size_t)(tb + t) * KS + (kb + i)) * 1024 + (size_t)lane * 16;
-        dma16<WNT>(src, __builtin_amdgcn_readfirstlane(lds_addr(&wr[i % PW][t][0])));
+        dma16(src, __builtin_amdgcn_readfirstlane(lds_addr(&wr[i % PW][t][0])));
       } else {
         dma16(dummy_g, dummy_l);
       }
     }
   };
   auto issue_x = [&](int i) {
-    if constexpr (PROBE != 0) return;
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
       const int rb = wave * RPW + r;
@@ -1642,16 +1381,12 @@ __global__ __launch_bounds__(NWV * 64) void k_gemm_rows(GemmArgs a, int G, int t
       }
     }
   };
-  static_assert(CM == 0 || (NWV == 8 && RPW == 1), "k_gemm_rows: the split consumer map is for 8 waves x 1 block");
-  constexpr int RBW = CM ? 2 : RPW;                 // row blocks a wave computes
-  constexpr int NTW = CM ? (NTC + 1) / 2 : NTC;     // tiles a wave computes
-  const int rbw0 = CM ? 2 * (wave & 3) : wave * RPW;
-  const int tw0 = CM ? (wave >> 2) * NTW : 0;
-  f32x4 acc[NTW][RBW];
+  const int rb0 = wave * RPW;   // the wave's first row block
+  f32x4 acc[NTC][RPW];
 #pragma unroll
-  for (int t = 0; t < NTW; ++t)
+  for (int t = 0; t < NTC; ++t)
 #pragma unroll
-    for (int r = 0; r < RBW; ++r) acc[t][r] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int r = 0; r < RPW; ++r) acc[t][r] = f32x4{0.f, 0.f, 0.f, 0.f};
   // prologue in the loop's issue order (k-step j - DW's weights, then k-step j - DX's X, for j = 0 .. DW - 1) so every
   // k-step's wait below sees the same number of younger loads; X of negative k-steps: padding loads
   for (int j = 0; j < DW; ++j) {
@@ -1659,32 +1394,26 @@ __global__ __launch_bounds__(NWV * 64) void k_gemm_rows(GemmArgs a, int G, int t
     if (j - (DW - DX) >= 0) issue_x(j - (DW - DX));
     else {
 #pragma unroll
-      for (int q = 0; q < 2 * RPW; ++q)
-        if constexpr (PROBE == 0) dma16(dummy_g, dummy_l);
+      for (int q = 0; q < 2 * RPW; ++q) dma16(dummy_g, dummy_l);
     }
   }
   for (int i = 0; i < nk; ++i) {
     // this wave's loads of k-step i (weights and X) have landed; after the barrier every wave's have, and every wave
     // is done reading k-step i - 1's slots, which the loads below overwrite
-    wait_vm_barrier<PROBE == 0 ? (DX - 1) * OPS : (PROBE == 1 ? (DW - 1) * LPW : 0)>();
+    wait_vm_barrier<(DX - 1) * OPS>();
     issue_w(i + DW);
     issue_x(i + DX);
     // every read of the k-step issued before the first MFMA (one latency per k-step); tiles past the workgroup's nt
     // and row blocks past M are computed on whatever the slots hold and never stored (no branch in the loop)
-    float4 xp[RBW][2];
+    float4 xp[RPW][2];
 #pragma unroll
-    for (int r = 0; r < RBW; ++r) {
-      if constexpr (XL == 0) {
-        xp[r][0] = xr[i % PX][rbw0 + r][0][lane];
-        xp[r][1] = xr[i % PX][rbw0 + r][1][lane];
-      } else {
-        xp[r][0] = xr[i % PX][rbw0 + r][xh0][xs0];
-        xp[r][1] = xr[i % PX][rbw0 + r][xh0][xs1];
-      }
+    for (int r = 0; r < RPW; ++r) {
+      xp[r][0] = xr[i % PX][rb0 + r][xh0][xs0];
+      xp[r][1] = xr[i % PX][rb0 + r][xh0][xs1];
     }
-    bf16x8 xh[RBW], xl[RBW];
+    bf16x8 xh[RPW], xl[RPW];
 #pragma unroll
-    for (int r = 0; r < RBW; ++r) {
+    for (int r = 0; r < RPW; ++r) {
       const float f[8] = {xp[r][0].x, xp[r][0].y, xp[r][0].z, xp[r][0].w,
                           xp[r][1].x, xp[r][1].y, xp[r][1].z, xp[r][1].w};
 #pragma unroll
@@ -1696,24 +1425,24 @@ __global__ __launch_bounds__(NWV * 64) void k_gemm_rows(GemmArgs a, int G, int t
     }
     // the weight fragments in groups of TG (all of them up to 20 tiles: VGPRs), each group's hi products of every
     // (tile, row block) and then the lo ones: no accumulator is read right after it is written
-    constexpr int TG = NTW * RBW <= 20 ? NTW : (NTW + 1) / 2;
+    constexpr int TG = NTC * RPW <= 20 ? NTC : (NTC + 1) / 2;
 #pragma unroll
-    for (int t0 = 0; t0 < NTW; t0 += TG) {
+    for (int t0 = 0; t0 < NTC; t0 += TG) {
       bf16x8 wf[TG];
 #pragma unroll
       for (int t = 0; t < TG; ++t)
-        if (t0 + t < NTW) wf[t] = wr[i % PW][min(tw0 + t0 + t, NTC - 1)][lane];
+        if (t0 + t < NTC) wf[t] = wr[i % PW][t0 + t][lane];
 #pragma unroll
       for (int t = 0; t < TG; ++t)
-        if (t0 + t < NTW)
+        if (t0 + t < NTC)
 #pragma unroll
-          for (int r = 0; r < RBW; ++r)
+          for (int r = 0; r < RPW; ++r)
             acc[t0 + t][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[r], wf[t], acc[t0 + t][r], 0, 0, 0);
 #pragma unroll
       for (int t = 0; t < TG; ++t)
-        if (t0 + t < NTW)
+        if (t0 + t < NTC)
 #pragma unroll
-          for (int r = 0; r < RBW; ++r)
+          for (int r = 0; r < RPW; ++r)
             acc[t0 + t][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl[r], wf[t], acc[t0 + t][r], 0, 0, 0);
     }
   }
@@ -1722,111 +1451,15 @@ __global__ __launch_bounds__(NWV * 64) void k_gemm_rows(GemmArgs a, int G, int t
   const int ROWS = RB * 16;
   float* slab = a.ws + (size_t)sp * ROWS * Ncols;
 #pragma unroll
-  for (int t = 0; t < NTW; ++t)
-    if (tw0 + t < nt && tw0 + t < NTC)
+  for (int t = 0; t < NTC; ++t)
+    if (t < nt)
 #pragma unroll
-      for (int r = 0; r < RBW; ++r)
+      for (int r = 0; r < RPW; ++r)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const int row = (rbw0 + r) * 16 + 4 * (lane >> 4) + e;
-          if (row < a.M) slab[(size_t)row * Ncols + (tb + tw0 + t) * 16 + (lane & 15)] = acc[t][r][e];
+          const int row = (rb0 + r) * 16 + 4 * (lane >> 4) + e;
+          if (row < a.M) slab[(size_t)row * Ncols + (tb + t) * 16 + (lane & 15)] = acc[t][r][e];
         }
-}
-
-// ---- 33..128-row weight streams, second form (k_gemm_wrow): each wave owns ONE weight tile over the workgroup's K
-// range and streams its fragments straight into registers DW k-steps ahead (a register ring, compiler-counted loads,
-// ~DW KiB in flight per wave), while the X rows of the k-step are staged once per workgroup through LDS, already
-// split into bf16 hi / lo (row block r loaded and converted by wave r): per k-step a workgroup ingests its tiles' 1 KiB
-// fragments from HBM and ONE copy of the k-step's X from L2 -- k_gemm_rows (waves split the rows) pulled every tile
-// through an LDS-DMA ring of at most ~60 KiB in flight and read X fp32 per wave.  One barrier per k-step (the X slot
-// double-buffered); no cross-wave reduction; partial tiles into split sp's slab, k_gemm_reduce runs the epilogue.
-template <int NWV, int RB, int DW, int DXS>
-__global__ __launch_bounds__(NWV * 64) void k_gemm_wrow(GemmArgs a, int G) {
-  static_assert(DW % DXS == 0 && DW % 2 == 0 && RB <= NWV, "k_gemm_wrow: ring shapes");
-  __shared__ bf16x8 xhi[2][RB][64], xlo[2][RB][64];
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;   // (uniform: SGPR offsets)
-  const int KS = a.K >> 5;
-  const int total = a.S * G, per_x = (total + 7) >> 3;
-  const int wgi = (int)(blockIdx.x & 7) * per_x + (int)(blockIdx.x >> 3);
-  if (wgi >= total) return;
-  const int sp = wgi / G, gx = wgi - sp * G;
-  const int tile = gx * NWV + wave;
-  const bool live = tile < a.ntiles;
-  const int kb = (int)((long)KS * sp / a.S), ke = (int)((long)KS * (sp + 1) / a.S);
-  const int nk = ke - kb;
-  // weight fragments through a buffer descriptor: k-steps past the split or a tile past ntiles address beyond its
-  // range, which the hardware drops (zeros, no memory access)
-  const unsigned long long wbase = (unsigned long long)a.Wp;
-  const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(
-      reinterpret_cast<void*>(((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(wbase >> 32)) << 32) |
-                              (unsigned)__builtin_amdgcn_readfirstlane((unsigned)wbase)),
-      (short)0, __builtin_amdgcn_readfirstlane(a.ntiles * KS * 1024), 0x00020000);
-  const int voff = lane * 16;
-  const int beyond = a.ntiles * KS * 1024;
-  auto ldw = [&](int i) -> bf16x8 {
-    const int so = (live && i < nk) ? (tile * KS + kb + i) * 1024 : beyond;
-    return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(srd, voff, so, 2));
-  };
-  // X staging: wave r < RB loads row block r's fragment of each k-step (lane: row 16 r + (l & 15), 8 columns)
-  const bool stager = wave < RB;
-  const int xrow = min(wave * 16 + (lane & 15), a.M - 1);
-  const float* xp = reinterpret_cast<const float*>(a.X) + (size_t)xrow * a.ldx + 8 * (lane >> 4) + (size_t)kb * 32;
-  auto ldx2 = [&](int i, float4 (&q)[2]) {
-    if (stager && i < nk) {
-      q[0] = reinterpret_cast<const float4*>(xp + (size_t)i * 32)[0];
-      q[1] = reinterpret_cast<const float4*>(xp + (size_t)i * 32)[1];
-    }
-  };
-  bf16x8 wq[DW];
-  float4 xq[DXS][2];
-#pragma unroll
-  for (int j = 0; j < DW; ++j) wq[j] = ldw(j);
-#pragma unroll
-  for (int j = 0; j < DXS; ++j) ldx2(j, xq[j]);
-  f32x4 acc[RB];
-#pragma unroll
-  for (int r = 0; r < RB; ++r) acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int i0 = 0; i0 < nk; i0 += DW) {
-#pragma unroll
-    for (int j = 0; j < DW; ++j) {
-      const int i = i0 + j;
-      if (i < nk) {          // workgroup-uniform
-      const int sl = j & 1;  // (i0 is a multiple of DW, which is even)
-      if (stager) {          // X of k-step i, split once into bf16 hi / lo for every wave
-        const float4 q0 = xq[j % DXS][0], q1 = xq[j % DXS][1];
-        const float f[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-        bf16x8 h8, l8;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const __bf16 h = (__bf16)f[e];
-          h8[e] = h;
-          l8[e] = (__bf16)(f[e] - (float)h);
-        }
-        xhi[sl][wave][lane] = h8;
-        xlo[sl][wave][lane] = l8;
-      }
-      ldx2(i + DXS, xq[j % DXS]);
-      __syncthreads();   // k-step i's X visible; every wave is past k-step i - 2's reads of this slot
-      const bf16x8 w = wq[j];
-      wq[j] = ldw(i + DW);
-#pragma unroll
-      for (int r = 0; r < RB; ++r) {
-        acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xhi[sl][r][lane], w, acc[r], 0, 0, 0);
-        acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xlo[sl][r][lane], w, acc[r], 0, 0, 0);
-      }
-      }
-    }
-  }
-  if (!live) return;
-  const int Ncols = a.ntiles * 16;
-  float* slab = a.ws + (size_t)sp * (RB * 16) * Ncols;
-#pragma unroll
-  for (int r = 0; r < RB; ++r)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int row = r * 16 + 4 * (lane >> 4) + e;
-      if (row < a.M) slab[(size_t)row * Ncols + tile * 16 + (lane & 15)] = acc[r][e];
-    }
 }
 
 // in-launch split-K merge: 0 off, 1 every eligible split, 2 (default) splits of small weights only -- measured
@@ -1851,67 +1484,18 @@ inline bool xs_mode() {
   }
   return g_xs == 1;
 }
-// 65..128-row GEMMs on the split-K weight streams as two row halves (FO_GEMM_ROW_SPLIT=0: the 64-row tile kernels)
-const bool g_row_split = [] {
-  const char* e = getenv("FO_GEMM_ROW_SPLIT");
-  return !(e && e[0] == '0');
-}();
 // paged K / V appended by the RoPE epilogues rounded to bf16 (the values a bf16 cache would hold; storage stays fp32):
 // the A/B of a bf16 KV against the fp32 default (FO_KV_BF16=1 or fo_set_kv_bf16)
 int g_kv_bf16 = [] {
   const char* e = getenv("FO_KV_BF16");
   return (e && e[0] == '1') ? 1 : 0;
 }();
-// 65..128-row GEMMs on the >= 128 MB weight streams take k_gemm_rows (FO_GEMM_ROWS=0: the row halves above)
-// (probe, fo_gemm_set_rows: 2 = k_gemm_wrow, one tile per wave)
+// 65..128-row GEMMs on >= 16 MiB weights take k_gemm_rows (1); FO_GEMM_ROWS=0 / fo_gemm_set_rows(0): the row halves
 int g_rows = [] {
   const char* e = getenv("FO_GEMM_ROWS");
   return (e && e[0] == '0') ? 0 : 1;
 }();
-// weights of at least this many MiB take the 17..64-row split-K stream (fo_gemm_set_xsk_min_mb: probes)
-int g_xsk_min_mb = [] {
-  const char* e = getenv("FO_XSK_MIN_MB");
-  return e ? atoi(e) : 128;
-}();
-// 33..48-row split-K stream shape: 5 k-steps per wave and 2 units in flight (K split 3 ways on the Qwen2 gate/up
-// instead of 4, 15 on the down instead of 19: a quarter fewer partial-slab bytes); FO_XSK_RB3=4: the round-4 shape
-// (4 k-steps, 3 units).  Measured (scripts/gemm_mid_probe.py, profiles/r05ze_xsk_rb3_ab.txt): gate/up at 40 / 48
-// rows 73.0 / 74.8 -> 69.6 / 70.0 us, down 40.8 / 41.9 -> 38.9 / 40.3 us
-const int g_xsk_rb3 = [] {
-  const char* e = getenv("FO_XSK_RB3");
-  return e ? atoi(e) : 5;
-}();
-int g_xsk = -1;  // X-stationary split-K kernel for eligible 17..64-row GEMMs: -1 = FO_GEMM_XSK (default on)
-inline bool xsk_mode() {
-  if (g_xsk < 0) {
-    const char* e = getenv("FO_GEMM_XSK");
-    g_xsk = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_xsk == 1;
-}
-// K split of the 8-tile long-K weight stream (Qwen2 down: 28 column groups x S workgroups); -1 = FO_DOWN_S
-// (4-16) decides at first use, default 8 (224 workgroups)
-int g_down_s = -1;
-inline int down_split() {
-  if (g_down_s < 0) {
-    const char* e = getenv("FO_DOWN_S");
-    const int v = e ? atoi(e) : 0;
-    g_down_s = (v >= 4 && v <= 16) ? v : 8;
-  }
-  return g_down_s;
-}
-// tiles per workgroup of that stream: 7 (default: 32 column groups x 8 = 256 workgroups, one per CU) or 8 (28
-// groups, 224 workgroups); FO_DOWN_NT.  r03s (one call): down alone 30.1 -> 29.8 us at 16 rows, the LLM stage
-// 3264 -> 3256 us, the bench 193.0 / 192.9x -> 194.3 / 195.2x; 8 x 9 (252 workgroups) and 7 x 9 (288) are slower
-// (31.3, 40.9 us; profiles/r03s_down_tiles_ab.txt)
-int g_down_nt = -1;
-inline int down_tiles() {
-  if (g_down_nt < 0) {
-    const char* e = getenv("FO_DOWN_NT");
-    g_down_nt = (e && atoi(e) == 8) ? 8 : 7;
-  }
-  return g_down_nt;
-}
+
 int g_num_cus = 0;
 inline int num_cus() {
   if (!g_num_cus) {
@@ -1955,6 +1539,592 @@ __global__ void k_pack(const void* W, int src_bf16, int N, int K, int ldw, bf16_
   }
 }
 
+// ---- host dispatch: one fo_gemm* call -> the kernel family its shape takes ----
+
+// One call as the extern "C" wrappers fill it (by field name; what a wrapper does not offer keeps its default).
+struct GemmCall {
+  const void* X = nullptr;   // [M][ldx], bf16 or fp32 (x_f32)
+  int x_f32 = 0, ldx = 0, M = 0, K = 0;
+  const void* Wp = nullptr;  // packed weight (fo_pack_weight)
+  int N = 0, swiglu = 0;
+  const float* bias = nullptr;
+  const float* scale = nullptr;
+  const float* shift = nullptr;
+  void* Y = nullptr;
+  int ldy = 0, out_bf16 = 0, act = 0, residual = 0;
+  float* ws = nullptr;   // split-K slabs
+  long long ws_floats = 0;
+  int* counters = nullptr;   // in-launch merge tickets
+  int splitk = 0;            // > 0: forced K split
+  const float* rstats = nullptr;   // RMSNorm / LayerNorm consumer (GemmArgs)
+  int rgroups = 0;
+  float reps = 0.f;
+  float* sout = nullptr;           // statistics producer (GemmArgs)
+  const float* gnext = nullptr;
+  float* yg = nullptr;
+  int* sgroups = nullptr;          // out: statistics groups per row the launch wrote
+  const GemmArgs* rope = nullptr;  // fo_gemm_qkv_rope: the r* fields
+  const float* lnw = nullptr;      // fo_gemm_ln: LayerNorm on load
+  const float* lnb = nullptr;
+  float lneps = 0.f;
+  float* sout1 = nullptr;          // fo_gemm_rowstats: partial sums of Y
+  const float* rstats1 = nullptr;  // fo_gemm_ln: the producer's partial sums
+  hipStream_t stream = nullptr;
+};
+
+// The packed weight of a call.  Every size threshold of the dispatcher is a byte count of this image.
+struct WeightDesc {
+  int ntiles;        // 16-column tiles (a SwiGLU gate/up pair counts two)
+  long long bytes;   // ntiles x 16 rows x K bf16
+};
+constexpr long long MiB = 1ll << 20;
+constexpr long long W_STREAM = 128 * MiB;       // the Qwen2 gate/up and down: the X-stationary streams (xs, xsk)
+constexpr long long W_STREAM_LONGK = 32 * MiB;  // ... also from here when K >= 8192 (xsk)
+constexpr long long W_LARGE = 64 * MiB;         // k_gemm_wstream, the pipelining policy; below it: merged splits, TTS gate/up
+constexpr long long W_ROWS = 16 * MiB;          // 65..128 rows: k_gemm_rows
+constexpr long long W_MID_BIG = 16 * MiB;       // 17..64 rows: 4-tile column groups
+constexpr long long W_HALVES_PLAIN = 8 * MiB;   // 65..128 rows as two halves: plain projections
+constexpr int DOWN_SPLIT = 8;                   // K split of the 7 / 8-tile long-K stream (Qwen2 down: 256 / 224 workgroups)
+
+// the packed buffers armed for a launch (one launch each)
+struct Packs {
+  PackArm x, y, y32, x32;
+};
+
+int check_call(const GemmCall& c, const Packs& pk) {
+  FO_REQUIRE(c.M > 0 && c.N > 0 && c.K > 0, "fo_gemm: bad shape M=%d N=%d K=%d", c.M, c.N, c.K);
+  FO_PACK_FITS(pk.x, c.K, c.M, "fo_gemm (packed X)");
+  FO_PACK_FITS(pk.x32, c.K, c.M, "fo_gemm (fp32 packed X)");
+  FO_PACK_FITS(pk.y, c.N, c.M, "fo_gemm (packed output)");
+  FO_PACK_FITS(pk.y32, c.N, c.M, "fo_gemm (fp32 packed output)");
+  FO_REQUIRE(!c.rstats || c.rgroups > 0, "fo_gemm: row statistics without a group count");
+  FO_REQUIRE(!c.sout || (!c.swiglu && !c.out_bf16 && (!c.yg || c.gnext)),
+             "fo_gemm: row statistics need fp32 non-SwiGLU output");
+  FO_REQUIRE((c.K & 31) == 0, "fo_gemm: K=%d must be a multiple of 32", c.K);
+  FO_REQUIRE(c.ldx >= c.K, "fo_gemm: ldx=%d < K=%d", c.ldx, c.K);
+  FO_REQUIRE(c.ldy >= c.N, "fo_gemm: ldy=%d < N=%d", c.ldy, c.N);
+  FO_REQUIRE(!(c.swiglu && (c.bias || c.scale)), "fo_gemm: swiglu with bias/affine unsupported");
+  FO_REQUIRE(!c.scale == !c.shift, "fo_gemm: scale and shift go together");
+  FO_REQUIRE(!pk.x32.p0 || (c.lnw && c.M <= 64), "fo_gemm: the fp32 packed X is read by LayerNorm-on-load launches only");
+  FO_REQUIRE(!pk.y32.p0 || (c.M <= 64 && !c.swiglu && !c.rope), "fo_gemm: fp32 packed output needs <= 64 plain rows");
+  FO_REQUIRE(!pk.x.p0 || (c.x_f32 && c.M <= 64 && !c.lnw), "fo_gemm: packed X needs fp32 X of <= 64 rows");
+  FO_REQUIRE(!pk.y.p0 || (c.M <= 64 && !c.swiglu && !c.rope), "fo_gemm: packed output needs <= 64 plain rows");
+  FO_REQUIRE(!c.sout1 || c.sout, "fo_gemm: row sums come with the sums of squares");
+  if (c.lnw) {
+    FO_REQUIRE(c.lnb && c.x_f32 && c.M <= 64 && !c.swiglu && c.rstats && c.rstats1 && c.rgroups > 0 &&
+               c.rgroups <= 64 && !c.rope && c.ldx % 4 == 0,
+               "fo_gemm_ln: fp32 X, M <= 64, producer statistics, plain epilogue only (M=%d K=%d)", c.M, c.K);
+  }
+  if (c.rope) {
+    FO_REQUIRE(!c.swiglu && !c.sout && !c.residual && !c.out_bf16 && c.act == 0 && !c.scale,
+               "fo_gemm_qkv_rope: plain epilogue only");
+    FO_REQUIRE(c.rope->rhd % 32 == 0 && c.N == (c.rope->rH + 2 * c.rope->rKVH) * c.rope->rhd,
+               "fo_gemm_qkv_rope: N=%d != (H + 2 KVH) * hd with hd %% 32 == 0", c.N);
+  }
+  return 0;
+}
+
+GemmArgs fill_args(const GemmCall& c, const Packs& pk, const WeightDesc& w) {
+  GemmArgs a{};
+  a.X = c.X;
+  a.Wp = (const bf16_t*)c.Wp;
+  a.bias = c.bias;
+  a.scale = c.scale;
+  a.shift = c.shift;
+  a.Y = c.Y;
+  a.ws = c.ws;
+  a.counters = c.counters;
+  a.ldx = c.ldx;
+  a.ldy = c.ldy;
+  a.M = c.M;
+  a.K = c.K;
+  a.N = c.N;
+  a.ntiles = w.ntiles;
+  a.S = 1;
+  a.act = c.act;
+  a.out_bf16 = c.out_bf16;
+  a.residual = c.residual;
+  a.sout = c.sout;
+  a.gnext = c.gnext;
+  a.yg = c.yg;
+  a.rstats = c.rstats;
+  a.rgroups = c.rgroups;
+  a.reps = c.reps;
+  if (c.rope) {
+    a.rpos = c.rope->rpos;
+    a.rslot = c.rope->rslot;
+    a.rcos = c.rope->rcos;
+    a.rsin = c.rope->rsin;
+    a.rq = c.rope->rq;
+    a.rk = c.rope->rk;
+    a.rv = c.rope->rv;
+    a.rH = c.rope->rH;
+    a.rKVH = c.rope->rKVH;
+    a.rhd = c.rope->rhd;
+    a.rPS = c.rope->rPS;
+    a.rkvb = g_kv_bf16;
+  }
+  a.lnw = c.lnw;
+  a.lnb = c.lnb;
+  a.lneps = c.lneps;
+  a.sout1 = c.sout1;
+  a.rstats1 = c.rstats1;
+  a.trc = g_trc;
+  a.xph = reinterpret_cast<const bf16x8*>(pk.x.p0);
+  a.xpl = reinterpret_cast<const bf16x8*>(pk.x.p1);
+  a.ypkh = reinterpret_cast<bf16_t*>(const_cast<void*>(pk.y.p0));
+  a.ypkl = reinterpret_cast<bf16_t*>(const_cast<void*>(pk.y.p1));
+  a.yp32 = reinterpret_cast<float*>(const_cast<void*>(pk.y32.p0));
+  a.xp32 = reinterpret_cast<const float*>(pk.x32.p0);
+  a.prb = (c.M + 15) / 16;
+  return a;
+}
+
+// every path below but the grid kernels: fp32 rows on the policy's own shapes (no LayerNorm on load, no forced
+// split, no fo_gemm_tune sweep) whose float4 loads are aligned
+inline bool stream_call(const GemmCall& c) {
+  return c.x_f32 && !c.lnw && c.splitk <= 1 && !g_force_nt && !g_force_nw && c.ldx % 4 == 0;
+}
+
+// ---- 65..128 rows on >= 16 MiB weights: k_gemm_rows (the weights once) when its split-K slabs fit the workspace.
+// (>= 16 MiB: the Qwen2 q|k|v -- RoPE + paged-KV append in the reduce -- and o too, which at 128 rows ran 64-row
+// tiles re-reading the weights per row tile (q|k|v 80 us, r06q) or two row halves (o 2 x 22.8 us))
+struct RowsPlan {
+  int S = 1, tiles_per = 0, G = 0;   // K splits, tiles per workgroup, tile groups
+};
+bool plan_rows(const GemmCall& c, const Packs& pk, const WeightDesc& w, RowsPlan& p) {
+  if (!(g_rows && c.M > 64 && c.M <= 128 && stream_call(c) && !c.sout1 && !c.rstats1 && w.bytes >= W_ROWS &&
+        ((unsigned long long)c.X & 15) == 0 && !pk.x.p0 && !pk.x32.p0 && (!c.swiglu || w.ntiles % 2 == 0)))
+    return false;
+  // The workgroup's X (all rows over its K range) comes through the CU beside its weights, so K is split until a
+  // workgroup's tiles carry about as many bytes as its X: gate/up 3 K thirds x 14 (gate, up) pairs (28 tiles), one
+  // round of <= 256 workgroups; down 16 K slices x 14 tiles (profiles/r06o_gemm_rows_split.txt, r06p: gate/up at 128
+  // rows 129.4 us on one K pass of 10 tiles, 102.7-110.0 on K halves of 20, 101.9 on thirds; down 68.9 on 8 slices
+  // of 7 tiles, 59.6-63.9)
+  const int cus = num_cus();
+  if (c.swiglu) {
+    const int ks = 3;   // K thirds
+    const int units = w.ntiles / 2, per = (ks * units + cus - 1) / cus;
+    p.tiles_per = 2 * per;
+    p.G = (units + per - 1) / per;
+    p.S = ks;
+  } else {
+    p.tiles_per = w.ntiles % 14 == 0 ? 14 : 16;
+    p.G = (w.ntiles + p.tiles_per - 1) / p.tiles_per;
+    p.S = max(1, min(16, cus / p.G));
+  }
+  const long long need = (long long)p.S * 128 * w.ntiles * 16;
+  return p.tiles_per <= (c.swiglu ? 30 : 16) && need <= c.ws_floats && c.ws != nullptr && (c.K >> 5) >= p.S;
+}
+int launch_rows(const GemmCall& c, GemmArgs& a, const RowsPlan& p) {
+  a.S = p.S;
+  a.counters = nullptr;
+  if (c.sgroups) *c.sgroups = (c.N + 255) / 256;
+  const int total = p.S * p.G;
+  const dim3 grid(8 * ((total + 7) / 8));
+  // (instantiated tile counts: the Qwen2 gate/up's 14 pairs and down's 14 tiles per workgroup, else the next size)
+#define FO_ROWS(NTC_, DW_, DX_) \
+  hipLaunchKernelGGL((k_gemm_rows<8, 1, NTC_, DW_, DX_>), grid, dim3(512), 0, c.stream, a, p.G, p.tiles_per)
+  if (c.swiglu && p.tiles_per > 20) {
+    // the weights and X the same number of k-steps ahead: vmcnt retires in order, so the wait for a k-step's X also
+    // waits for every weight load issued before it -- an X lead shorter than the weights' caps their depth at it
+    // (r06w: 7 or 11 k-steps of weights alone, 85 us either way; with X 1 ahead the ring held ~1 k-step)
+    FO_ROWS(30, 2, 2);
+  } else if (c.swiglu) {
+    FO_ROWS(20, 3, 3);
+  } else if (p.tiles_per == 14) {
+    FO_ROWS(14, 4, 4);
+  } else {
+    FO_ROWS(16, 3, 3);
+  }
+#undef FO_ROWS
+  int rc = fo::check_launch("fo_gemm/rows");
+  if (rc) return rc;
+  launch_reduce(a, c.swiglu, 128, c.N, c.M, c.stream);
+  fo::count_launch(FO_L_GEMM_ROWS);
+  fo::count_launch(FO_L_GEMM_REDUCE);
+  return fo::check_launch("fo_gemm/rows reduce");
+}
+
+// weights that take the 17..64-row X-stationary split-K stream (k_gemm_xsk): >= 128 MiB (Qwen2 gate/up, down) or
+// long-K >= 32 MiB (the speech encoder's subsampling output linear, 19,456 x 1024 = 40 MB: 48.8 us per chunk on the
+// split-K grid kernel, r04i); on the 26-33 MB q|k|v / o the one-row-tile kernels are faster (r04d probe: o 14.8 vs
+// 18.5 us, q|k|v 19.2 vs 24.4 us at 32 rows)
+inline bool xsk_weight(const GemmCall& c, const WeightDesc& w) {
+  return w.bytes >= W_STREAM || (c.K >= 8192 && w.bytes >= W_STREAM_LONGK);
+}
+
+// ---- 65..128 rows on the large weight streams without k_gemm_rows (FO_GEMM_ROWS=0, or its slabs do not fit; a duplex
+// tick whose sessions start a turn: the 5-token chat prefix on top of the 4 chunk rows; 8 x 9 = 72 rows): two
+// launches on the two row halves (33..64 rows each) instead of 64-row tiles, which stream the whole weight once per
+// row tile at ~1.4-2.5 TB/s (r05i duplex table: gate/up 193.8 us, down 110.4 us per layer at 72 rows).  Both halves
+// take k_gemm_xsk -- or, for the plain >= 8 MiB projections (the Qwen2 o: 57.0 us on 64-row tiles at 72 rows), the
+// one-row-tile split-K kernels + k_gemm_reduce -- so their row statistics have the same group count
+// ((N + 255) / 256) and the halves' rows tile the [M][groups] layout.
+bool row_halves_call(const GemmCall& c, const Packs& pk, const WeightDesc& w) {
+  return c.M > 64 && c.M <= 128 && stream_call(c) && !c.rope && !c.sout1 && !c.rstats1 &&
+         (xsk_weight(c, w) || (!c.swiglu && w.bytes >= W_HALVES_PLAIN)) && !pk.x.p0 && !pk.y.p0 && !pk.y32.p0 &&
+         !pk.x32.p0 && (c.K >> 5) >= 56 && w.ntiles % 2 == 0;
+}
+int gemm_impl(const GemmCall& c);
+int launch_row_halves(const GemmCall& c) {
+  const int M0 = (c.M + 1) / 2, grp = (c.N + 255) / 256;
+  int sg = 0;
+  for (int h = 0; h < 2; ++h) {
+    const int r0 = h ? M0 : 0;
+    int sgh = 0;
+    GemmCall hc = c;   // the half's rows of everything indexed by row
+    hc.M = h ? c.M - M0 : M0;
+    hc.X = static_cast<const char*>(c.X) + (size_t)r0 * c.ldx * 4;
+    hc.Y = static_cast<char*>(c.Y) + (size_t)r0 * c.ldy * (c.out_bf16 ? 2 : 4);
+    if (c.rstats) hc.rstats = c.rstats + (size_t)r0 * c.rgroups;
+    if (c.sout) hc.sout = c.sout + (size_t)r0 * grp;
+    if (c.yg) hc.yg = c.yg + (size_t)r0 * c.ldy;
+    hc.sgroups = &sgh;
+    const int rc = gemm_impl(hc);
+    if (rc) return rc;
+    FO_REQUIRE(!c.sout || sgh == grp, "fo_gemm: row halves wrote %d statistics groups, expected %d", sgh, grp);
+    sg = sgh;
+  }
+  if (c.sgroups) *c.sgroups = sg;
+  return 0;
+}
+
+// ---- X-stationary persistent weight stream (k_gemm_xs) for the M <= 16 rows of a listen chunk / text step on
+// K = 3584 layers: no split, no LayerNorm-on-load.
+// Measured (scripts/gemm_xs_ab.py, graph-replayed over weight copies beyond the Infinity Cache): gate/up
+// + SwiGLU 56.1 -> 48.4 us at 16 rows, 47.4 -> 45.5 us at 8; lm_head equal (169.5 vs 169.9 us); the
+// 26-33 MB o and q|k|v projections slower (one unit per workgroup: 12.3 -> 15.1, 18.7 -> 20.4 us), so
+// only the SwiGLU pair takes this path.
+bool xs_call(const GemmCall& c, const WeightDesc& w) {
+  return c.M <= 16 && stream_call(c) && c.K == XS_NW * XS_KPW * 32 && w.ntiles % 2 == 0 && xs_mode() && c.swiglu &&
+         w.bytes >= W_STREAM;
+}
+int launch_xs(const GemmCall& c, GemmArgs& a) {
+  const int units = a.ntiles / 2;
+  // as many workgroups as it takes for every one to get the same (ceil) number of units: 1184 gate/up
+  // pairs -> 237 x 5 (not 256 with 4 or 5: the 5-unit CUs would set the time); a CU can pull more than
+  // its 1/256 share of the HBM stream, so the idle CUs cost nothing
+  const int per = (units + num_cus() - 1) / num_cus();
+  const int G = (units + per - 1) / per;
+  a.S = 1;
+  if (c.sgroups) *c.sgroups = units;
+  hipLaunchKernelGGL((k_gemm_xs<XS_NW, XS_KPW>), dim3(G), dim3(XS_NW * 64), 0, c.stream, a, units);
+  fo::count_launch(FO_L_GEMM_XS);
+  if (a.xph) fo::count_launch(FO_L_GEMM_XP);
+  return fo::check_launch("fo_gemm/xs");
+}
+
+// ---- 17..64 rows on the weight streams (xsk_weight; duplex ticks: 8 sessions x 4 framing-B tokens, the assistant
+// prefix 8 x 5, prefixed first chunks): the X-stationary stream with K split over workgroups (k_gemm_xsk) +
+// k_gemm_reduce
+bool xsk_call(const GemmCall& c, const WeightDesc& w) {
+  return c.M > 16 && c.M <= 64 && stream_call(c) && w.ntiles % 2 == 0 && xsk_weight(c, w) && !c.sout1 &&
+         (c.K >> 5) >= 56;
+}
+int launch_xsk(const GemmCall& c, GemmArgs& a) {
+  const int RB = (c.M + 15) / 16;
+  // 8 waves x KPW k-steps of X per split (hi in VGPRs, lo in LDS: KPW shrinks as the row blocks grow), UA units of
+  // weights in flight per wave (~28 KiB, k_gemm_xs's depth); every split has work (K >= 56 k-steps).
+  // 33..48 rows: 5 k-steps per wave and 2 units in flight (K split 3 ways on the Qwen2 gate/up, 15 on the down) --
+  // against round 4's 4 k-steps x 3 units (4 and 19 splits: a quarter more partial-slab bytes), measured
+  // (scripts/gemm_mid_probe.py, profiles/r05ze_xsk_rb3_ab.txt): gate/up at 40 / 48 rows 73.0 / 74.8 -> 69.6 / 70.0 us,
+  // down 40.8 / 41.9 -> 38.9 / 40.3 us
+  const int NW = 8, KPW = RB == 2 ? 7 : (RB == 3 ? 5 : 3);
+  const int KS = c.K >> 5;
+  const int S = (KS + NW * KPW - 1) / (NW * KPW);
+  const int units = a.ntiles / 2;
+  const int per_split = max(1, num_cus() / S);
+  const int per = (units + per_split - 1) / per_split;
+  const int G = (units + per - 1) / per;
+  const long long need = (long long)S * RB * 16 * a.ntiles * 16;
+  FO_REQUIRE(c.ws && need <= c.ws_floats, "fo_gemm/xsk: split-K workspace too small (%lld > %lld)", need, c.ws_floats);
+  a.S = S;
+  a.counters = nullptr;
+  if (c.sgroups) *c.sgroups = (c.N + 255) / 256;
+  const dim3 grid(8 * ((S * G + 7) / 8));
+  if (RB == 2) hipLaunchKernelGGL((k_gemm_xsk<8, 7, 2, 2>), grid, dim3(512), 0, c.stream, a, units, G);
+  else if (RB == 3) hipLaunchKernelGGL((k_gemm_xsk<8, 5, 3, 2>), grid, dim3(512), 0, c.stream, a, units, G);
+  else hipLaunchKernelGGL((k_gemm_xsk<8, 3, 4, 4>), grid, dim3(512), 0, c.stream, a, units, G);
+  int rc = fo::check_launch("fo_gemm/xsk");
+  if (rc) return rc;
+  launch_reduce(a, c.swiglu, RB * 16, c.N, c.M, c.stream);
+  fo::count_launch(FO_L_GEMM_XSK);
+  fo::count_launch(FO_L_GEMM_REDUCE);
+  if (a.ypkh) fo::count_launch(FO_L_GEMM_YPACK);
+  if (a.yp32) fo::count_launch(FO_L_GEMM_YPACK32);
+  return fo::check_launch("fo_gemm/xsk reduce");
+}
+
+// ---- the grid kernels: (column groups, row tiles, K splits) workgroups of gemm_body
+struct GridPlan {
+  bool mid = false;       // 17..64 fp32 rows as ONE row tile of ceil(M/16) row blocks
+  int RB = 1, mt = 1;     // 16-row blocks per row tile, row tiles
+  int NT = 1, groups = 0; // packed tiles per workgroup, column groups
+  int S = 1;              // K split across workgroups
+  int pipe = 0;           // software pipelining of the one-row-tile fp32-X launch (launch_gemm)
+  int nw1 = 0, nw4 = 0;   // waves the policy prefers for the one-row-tile / 64-row-tile kernels (0: by grid size)
+  bool rope4 = false;     // RoPE q|k|v in 4-tile column groups, its epilogue in the reduce
+};
+int plan_grid(const GemmCall& c, const WeightDesc& w, GridPlan& p) {
+  const int M = c.M, K = c.K, KS = K >> 5, ntiles = w.ntiles;
+  const bool swiglu = c.swiglu != 0;
+  // mid-size row counts on large weights (the Qwen2 prefills of a turn: assistant prefix, the first
+  // chunk with its chat prefix, the system prompt; 17..64 rows): one row tile of ceil(M/16) row blocks
+  // against 4-tile column groups, so X (fp32, re-read by every column group) costs about what the
+  // weights do, and no grid of 64-row tiles streams X four times per weight byte
+  // (small weights with 33..64 rows -- the duplex encoder at 8 sessions x 7 frames -- take the same
+  // one-row-tile kernels with single-tile column groups instead of 64-row tiles on 64 workgroups)
+  const bool big_w = w.bytes >= W_MID_BIG;
+  p.mid = c.x_f32 && !c.lnw && M > 16 && M <= 64 && (big_w || M > 32);
+  p.RB = p.mid ? (M + 15) / 16 : (M <= 16 ? 1 : (M <= 32 ? 2 : 4));
+  p.mt = (M + p.RB * 16 - 1) / (p.RB * 16);
+  // tiles per workgroup: the activation rows are re-read by every workgroup, so workgroups that
+  // cover more output columns read X fewer times per weight byte (measured, gemm_sweep.py)
+  int NT = swiglu ? 2 : 1;
+  int S_auto = 0;
+  if (p.mid) {
+    NT = big_w ? (ntiles % 4 == 0 ? 4 : 2) : (swiglu ? 2 : 1);
+  } else if (p.RB == 1) {
+    // measured policy (gemm_sweep.py, gemm_graph_sweep.py): wide layers (>= 1024 tiles: Qwen2 gate/up, lm_head) take 4
+    // tiles per workgroup; long-K layers (Qwen2 down) 7 or 8 tiles and an 8-way K split; mid-size grids
+    // (> 256 tiles: Qwen2 qkv) 2 tiles; small ones 1
+    if (ntiles >= 1024) NT = 4;
+    // Qwen2 down (592 k-steps, 224 tiles): 7 tiles x 8-way K split, pipelined (32 x 8 = 256 workgroups, one per CU;
+    // 8 tiles: 28 x 8 = 224): the activation rows are read by a quarter as many column groups as with 4 tiles x 4
+    // ways; 31.7 -> 29.7 us at 16 rows, 29.7 -> 28.7 us at 8, reduce launch included (profiles/r03g_down_sweep.txt).
+    // 7 over 8 tiles, r03s (one call): down alone 30.1 -> 29.8 us at 16 rows, the LLM stage 3264 -> 3256 us, the
+    // bench 193.0 / 192.9x -> 194.3 / 195.2x; 8 x 9 (252 workgroups) and 7 x 9 (288) are slower (31.3, 40.9 us;
+    // profiles/r03s_down_tiles_ab.txt)
+    else if (KS >= 256 && ntiles >= 128) {
+      NT = ntiles % 8 == 0 ? 8 : 4;
+      if (ntiles % 7 == 0) NT = 7;
+      S_auto = NT >= 7 ? DOWN_SPLIT : 4;
+    }
+    else if (KS >= 128 && ntiles <= 64) S_auto = 4;  // narrow long-K (TTS down): 10.9 -> 8.2 us in a graph
+    else if (ntiles > 256) NT = 2;
+    // small SwiGLU pairs over 512+ tiles (the TTS gate/up, 608 tiles, 17.4 MB): 2 pairs per workgroup on 8
+    // waves keeps the grid within one round of the 256 CUs (152 instead of 304 workgroups): 7.83 -> 7.16 us
+    // graph-replayed (profiles/r02s_tts_gemm_sweep.txt)
+    if (swiglu && ntiles >= 512 && ntiles < 1024 && w.bytes < W_LARGE && ntiles % 4 == 0) {
+      NT = 4;
+      p.nw1 = 8;
+    }
+    // Pipelined weight stream, 2-step groups (policy measured in the turn bench, A/B twice in one
+    // call: 388-390 -> 383-386 ms/turn, p50 first PCM 50 -> 48.5 ms).  Isolated (scripts/
+    // gemm_gu_sweep.py, gemm_pipe_ab.py; two alternating weight copies): gate/up at <= 8 rows on 2
+    // tiles x 8 waves 50.5 -> 44.4 us, down 32.0 -> 29.5 us, lm_head 177 -> 172 us.  Gate/up at 9-16
+    // rows keeps the plain 4-tile loop: pipelined with a 2-way K split it is faster alone (53.8 ->
+    // 51.2 us) but made the pipelined listen stage slower (turn 388 -> 408 ms).
+    const int pm = pipe_mode();
+    if (c.x_f32 && (pm == 1 || pm == 2)) {
+      p.pipe = pm;   // sweeps: every one-row-tile fp32-X GEMM
+    } else if (c.x_f32 && pm == 3 && w.bytes >= W_LARGE) {
+      if (!swiglu || M <= 8) p.pipe = 2;
+      if (swiglu && M <= 8 && !g_force_nt && !g_force_nw) {
+        NT = 2;
+        p.nw1 = 8;
+      }
+    }
+    if (g_force_nt) NT = g_force_nt;
+    FO_REQUIRE(NT == 1 || NT == 2 || NT == 4 || NT == 8 || (NT == 7 && !swiglu), "fo_gemm: tiles per workgroup %d", NT);
+    FO_REQUIRE(!swiglu || NT >= 2, "fo_gemm: swiglu needs tile pairs");
+    if (ntiles % NT) NT = swiglu ? 2 : 1;
+  } else if (p.RB == 2) {
+    // speech-encoder shapes (M = 32): narrow long-K layers (FFN w_2, subsampling out) split K 4 ways
+    if (!swiglu && ntiles <= 64 && KS >= 96) S_auto = 4;
+    if (g_force_nt == 1 || g_force_nt == 2) NT = swiglu ? 2 : g_force_nt;
+    if (ntiles % NT) NT = swiglu ? 2 : 1;
+  }
+  if (p.RB == 4 && g_force_nt && c.x_f32 && !c.lnw && !c.rope) {   // sweeps (fo_gemm_tune): forced tiles per workgroup
+    NT = g_force_nt;
+    if (swiglu && NT < 2) NT = 2;
+    if (ntiles % NT) NT = swiglu ? 2 : 1;
+  } else if (p.RB == 4 && !p.mid && c.x_f32 && !c.lnw && M > 64) {
+    // 64-row tiles (prefills of 65+ rows: the AR decoder's sentence prefill at 8 sessions x 32-40 sub-token rows, the
+    // speech encoder's im2col convolutions).  Measured (scripts/gemm_big_sweep.py, profiles/r04q_gemm_big_sweep.txt):
+    // 8 waves splitting K inside the workgroup everywhere but the K = 32 conv1 (4); 4 column tiles per X read when
+    // that still gives >= 128 workgroups or K is long (then split K over workgroups until the grid nears 256); else
+    // one tile (pair) per workgroup.  AR prefill down 67.8 -> 26.3 us, gate/up 56.2 -> 40.3 us, q|k|v 20.3 -> 16.4,
+    // o 12.2 -> 10.4; conv2 130.9 -> 89.6 us, conv1 28.5 -> 15.3 us
+    p.nw4 = KS <= 2 ? 4 : 8;
+    const int wg4 = ntiles / 4 * p.mt;
+    if (ntiles % 4 == 0 && KS > 2 && (wg4 >= 128 || KS >= 128)) {
+      NT = 4;
+      if (KS >= 128) S_auto = (KS >= 256 || wg4 * 4 <= 256) ? 4 : (wg4 * 2 <= 256 ? 2 : 1);
+    } else {
+      NT = swiglu ? 2 : 1;
+    }
+  }
+  // the epilogue rotates the (i, i + hd/2) tile pair a workgroup holds; a 17..64-row RoPE projection on large
+  // weights (the Qwen2 q|k|v of a duplex tick or a prefill) keeps the 4-tile column groups of the plain path and
+  // always splits K, so k_gemm_reduce (which pairs the tiles itself) runs that epilogue: one X read per 4 tiles
+  // instead of per pair (r04g trace: the 2-tile split q|k|v 33.9 + 5 us at 33..48 rows)
+  p.rope4 = c.rope && p.mid && NT == 4 && c.splitk <= 1 && !g_force_nt;
+  if (c.rope && !p.rope4) NT = 2;
+  if (c.lnw && NT > 2) NT = 2;
+  p.NT = NT;
+  p.groups = ntiles / NT;
+  if (p.mid) {  // split K: 2 ways on wide layers (Qwen2 gate/up), until the grid covers the chip on narrow ones
+    S_auto = p.groups >= 192 ? (big_w ? 2 : 1) : (256 + p.groups - 1) / p.groups;
+    if (S_auto > 4) S_auto = 4;
+    if (S_auto > KS / 16) S_auto = KS / 16 > 0 ? KS / 16 : 1;
+  }
+  int S = c.splitk > 0 ? c.splitk
+                       : (S_auto && !g_force_nt ? S_auto : (p.mid ? 1 : fo_gemm_pick_split(M, p.groups, K)));
+  if (c.rstats && !c.lnw && !p.mid) S = 1;  // (split RMSNorm consumers: k_gemm_reduce applies the rstd)
+  if (S > KS) S = KS;
+  if (p.rope4 && S < 2) S = 2;   // the pair epilogue needs the reduce launch
+  p.S = S;
+  return 0;
+}
+
+void launch_grid_ln(const GridPlan& p, dim3 grid, long long wgs, const GemmArgs& a, hipStream_t stream) {
+  const int nw = wgs <= 128 ? 16 : 8;
+  dim3 blk(nw * 64);
+#define FO_LN(NT_, RB_, NW_) hipLaunchKernelGGL((k_gemm_ln<NT_, RB_, NW_>), grid, blk, 0, stream, a)
+  if (p.RB == 1) {
+    if (p.NT == 2) { if (nw == 16) FO_LN(2, 1, 16); else FO_LN(2, 1, 8); }
+    else { if (nw == 16) FO_LN(1, 1, 16); else FO_LN(1, 1, 8); }
+  } else if (p.RB == 2) {
+    if (p.NT == 2) { if (nw == 16) FO_LN(2, 2, 16); else FO_LN(2, 2, 8); }
+    else { if (nw == 16) FO_LN(1, 2, 16); else FO_LN(1, 2, 8); }
+  } else {   // 33..64 rows (the duplex encoder: 8 sessions x 7 framing-B frames): 2 k-steps in flight per wave
+    if (p.NT == 2) hipLaunchKernelGGL((k_gemm_ln<2, 4, 8, 2>), grid, dim3(512), 0, stream, a);
+    else hipLaunchKernelGGL((k_gemm_ln<1, 4, 8, 4>), grid, dim3(512), 0, stream, a);
+  }
+#undef FO_LN
+}
+void launch_grid_mid(const GridPlan& p, bool swiglu, dim3 grid, long long wgs, const GemmArgs& a, hipStream_t stream) {
+  // 2 k-steps in flight per wave keep the RB x NT accumulators and fragments within 4 waves / SIMD
+  const int nw = (p.NT == 4 || wgs >= 384) ? 4 : 8;
+  const int RB = p.RB, NT = p.NT;
+#define FO_MID(NT_, RB_, NW_, SW_) launch_mid<NT_, RB_, NW_, SW_>(grid, a, stream)
+#define FO_MID_RB(NT_, NW_, SW_) { if (RB == 2) FO_MID(NT_, 2, NW_, SW_); else if (RB == 3) FO_MID(NT_, 3, NW_, SW_); else FO_MID(NT_, 4, NW_, SW_); }
+  if (swiglu) {
+    if (NT == 4) FO_MID_RB(4, 4, true) else if (nw == 4) FO_MID_RB(2, 4, true) else FO_MID_RB(2, 8, true)
+  } else if (NT == 1) {
+    if (nw == 4) FO_MID_RB(1, 4, false) else FO_MID_RB(1, 8, false)
+  } else {
+    if (NT == 4) FO_MID_RB(4, 4, false) else if (nw == 4) FO_MID_RB(2, 4, false) else FO_MID_RB(2, 8, false)
+  }
+#undef FO_MID_RB
+#undef FO_MID
+}
+void launch_grid_rb1(const GridPlan& p, bool swiglu, bool wstream, bool x_f32, dim3 grid, long long wgs,
+                     const GemmArgs& a, hipStream_t stream) {
+  // measured (scripts/gemm_sweep.py, MI355X): one workgroup per CU wants 16 waves, a couple per
+  // CU 8, many 4; 4 k-steps in flight per wave is the sweet spot everywhere on the hot path
+  const int NT = p.NT;
+  int nw = wgs <= 160 ? 16 : (wgs <= 256 ? (NT == 1 ? 16 : 8) : ((NT == 4 || wgs >= 1024) ? 4 : 8));
+  if (p.nw1) nw = p.nw1;
+  if (g_force_nw) nw = g_force_nw;
+  if (swiglu) {
+    if (NT == 8) launch_nw<8, 1, true>(nw, p.pipe, wstream, x_f32, grid, a, stream);
+    else if (NT == 4) launch_nw<4, 1, true>(nw, p.pipe, wstream, x_f32, grid, a, stream);
+    else launch_nw<2, 1, true>(nw, p.pipe, wstream, x_f32, grid, a, stream);
+  } else {
+    if (NT == 8) launch_nw<8, 1, false>(nw, p.pipe, wstream, x_f32, grid, a, stream);
+    else if (NT == 7) launch_nw<7, 1, false>(nw, p.pipe, wstream, x_f32, grid, a, stream);
+    else if (NT == 4) launch_nw<4, 1, false>(nw, p.pipe, wstream, x_f32, grid, a, stream);
+    else if (NT == 2) launch_nw<2, 1, false>(nw, p.pipe, wstream, x_f32, grid, a, stream);
+    else launch_nw<1, 1, false>(nw, p.pipe, wstream, x_f32, grid, a, stream);
+  }
+}
+void launch_grid_rb2(const GridPlan& p, bool swiglu, bool wstream, bool x_f32, dim3 grid, long long wgs,
+                     const GemmArgs& a, hipStream_t stream) {
+  int nw = wgs <= 128 ? 16 : 8;
+  if (g_force_nw) nw = g_force_nw;
+  if (swiglu) launch_nw<2, 2, true>(nw, 0, wstream, x_f32, grid, a, stream);
+  else if (p.NT == 2) launch_nw<2, 2, false>(nw, 0, wstream, x_f32, grid, a, stream);
+  else launch_nw<1, 2, false>(nw, 0, wstream, x_f32, grid, a, stream);
+}
+void launch_grid_rb4(const GridPlan& p, bool swiglu, bool wstream, bool x_f32, dim3 grid, const GemmArgs& a,
+                     hipStream_t stream) {
+  const int NT = p.NT;
+  if (x_f32) {
+    // 64-row tiles (prefills of 65+ rows, im2col convolutions): waves split K inside the workgroup (nw4), the
+    // column tiles per workgroup share each X read; fo_gemm_tune forces (waves, tiles) for sweeps
+    int nw4 = p.nw4 ? p.nw4 : 4;
+    if (g_force_nw) nw4 = g_force_nw;
+#define FO_B4(NT_, NW_, SW_) launch_gemm<NT_, 4, NW_, 2, SW_>(0, wstream, x_f32, grid, a, stream)
+    if (swiglu) {
+      if (NT == 8) FO_B4(8, 4, true);
+      else if (NT == 4) { if (nw4 >= 8) FO_B4(4, 8, true); else FO_B4(4, 4, true); }
+      else { if (nw4 >= 16) FO_B4(2, 16, true); else if (nw4 == 8) FO_B4(2, 8, true); else FO_B4(2, 4, true); }
+    } else if (NT == 8) FO_B4(8, 4, false);
+    else if (NT == 4) { if (nw4 >= 8) FO_B4(4, 8, false); else FO_B4(4, 4, false); }
+    else if (NT == 2) { if (nw4 >= 16) FO_B4(2, 16, false); else if (nw4 == 8) FO_B4(2, 8, false); else FO_B4(2, 4, false); }
+    else { if (nw4 >= 16) FO_B4(1, 16, false); else if (nw4 == 8) FO_B4(1, 8, false); else FO_B4(1, 4, false); }
+#undef FO_B4
+  } else {
+    if (swiglu) launch_gemm<2, 4, 4, 4, true>(0, wstream, x_f32, grid, a, stream);
+    else if (NT == 4) launch_gemm<4, 4, 4, 4, false>(0, wstream, x_f32, grid, a, stream);
+    else if (NT == 2) launch_gemm<2, 4, 4, 4, false>(0, wstream, x_f32, grid, a, stream);
+    else launch_gemm<1, 4, 4, 4, false>(0, wstream, x_f32, grid, a, stream);
+  }
+}
+
+int launch_grid(const GemmCall& c, GemmArgs& a, const WeightDesc& w) {
+  GridPlan p;
+  if (int rc = plan_grid(c, w, p)) return rc;
+  const bool swiglu = c.swiglu != 0, x_f32 = c.x_f32 != 0;
+  const int RB = p.RB, S = p.S;
+  a.S = S;
+  if (S > 1) {
+    const long long need = (long long)S * p.mt * RB * 16 * a.ntiles * 16;
+    FO_REQUIRE(c.ws && need <= c.ws_floats, "fo_gemm: split-K workspace too small (%lld > %lld)", need, c.ws_floats);
+  }
+  dim3 grid(p.groups, p.mt, S);
+  // one-row-tile plain splits merge inside the launch (last split to arrive sums and finishes; tickets in
+  // the caller's zeroed counters, left zeroed); otherwise k_gemm_reduce follows
+  const bool merged = S > 1 && c.counters && RB == 1 && !a.sout1 && !swiglu && !c.lnw && !p.mid &&
+                      (merge_mode() == 1 || (merge_mode() == 2 && w.bytes < W_LARGE));
+  a.counters = merged ? c.counters : nullptr;
+  if (merged) FO_REQUIRE((long long)p.groups * p.mt <= (1 << 20), "fo_gemm: too many tiles for the merge tickets");
+  if (c.sgroups) *c.sgroups = (S > 1 && !merged) ? (c.N + 255) / 256 : p.groups;
+  const bool wstream = w.bytes >= W_LARGE;
+  const long long wgs = (long long)p.groups * p.mt * S;
+  if (c.lnw) launch_grid_ln(p, grid, wgs, a, c.stream);
+  else if (p.mid) launch_grid_mid(p, swiglu, grid, wgs, a, c.stream);
+  else if (RB == 1) launch_grid_rb1(p, swiglu, wstream, x_f32, grid, wgs, a, c.stream);
+  else if (RB == 2) launch_grid_rb2(p, swiglu, wstream, x_f32, grid, wgs, a, c.stream);
+  else launch_grid_rb4(p, swiglu, wstream, x_f32, grid, a, c.stream);
+  const bool pipe_k = RB == 1 && x_f32 && p.pipe;
+  fo::count_launch(c.lnw ? FO_L_GEMM_LN : (p.mid ? FO_L_GEMM_MID : (pipe_k ? FO_L_GEMM_PIPE : FO_L_GEMM_OTHER)));
+  if (c.lnw && a.xp32) fo::count_launch(FO_L_GEMM_XP32);
+  if (a.xph && x_f32 && !c.lnw && !swiglu && !pipe_k) fo::count_launch(FO_L_GEMM_XP);
+  if (p.rope4) fo::count_launch(FO_L_GEMM_ROPE4);
+  if (a.ypkh) fo::count_launch(FO_L_GEMM_YPACK);
+  if (a.yp32) fo::count_launch(FO_L_GEMM_YPACK32);
+  if (S > 1 && !merged) {
+    int rc = fo::check_launch("fo_gemm/split");
+    if (rc) return rc;
+    launch_reduce(a, swiglu, p.mt * RB * 16, c.N, c.M, c.stream);
+    fo::count_launch(FO_L_GEMM_REDUCE);
+  }
+  return fo::check_launch("fo_gemm");
+}
+
+// Y = act(X @ W^T + bias) (+Y if residual).  X bf16 or fp32 [M][ldx], K % 32 == 0.
+// swiglu != 0: Wp holds interleaved (gate, up) tile pairs, Y[m][n] = silu(gate) * up, n < N.
+int gemm_impl(const GemmCall& c) {
+  // the packed buffers armed for this launch are consumed whatever happens below (one launch each)
+  const Packs pk{g_xpk, g_ypk, g_yp32k, g_xp32k};
+  g_xpk = g_ypk = g_yp32k = g_xp32k = PackArm{};
+  if (int rc = check_call(c, pk)) return rc;
+  WeightDesc w;
+  w.ntiles = (c.swiglu ? 2 : 1) * ((c.N + 15) / 16);
+  w.bytes = (long long)w.ntiles * 16 * c.K * 2;
+  GemmArgs a = fill_args(c, pk, w);
+  RowsPlan rows;
+  if (plan_rows(c, pk, w, rows)) return launch_rows(c, a, rows);
+  if (row_halves_call(c, pk, w)) return launch_row_halves(c);
+  if (xs_call(c, w)) return launch_xs(c, a);
+  if (xsk_call(c, w)) return launch_xsk(c, a);
+  return launch_grid(c, a, w);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1975,546 +2145,64 @@ int fo_gemm_pick_split(int M, int N_tiles_groups, int K) {
   return S;
 }
 
-long long fo_gemm_workspace_floats(int M, int N, int K, int swiglu) {
-  const int ntiles = swiglu ? 2 * ((N + 15) / 16) : (N + 15) / 16;
-  const int NT = swiglu ? 2 : 1;
-  const int S = fo_gemm_pick_split(M, ntiles / NT, K);
-  const int RB = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
-  const int mt = (M + RB * 16 - 1) / (RB * 16);
-  return S > 1 ? (long long)S * mt * RB * 16 * ntiles * 16 : 0;
-}
-
-// Y = act(X @ W^T + bias) (+Y if residual).  X bf16 [M][ldx], K % 32 == 0.
-// swiglu != 0: Wp holds interleaved (gate, up) tile pairs, Y[m][n] = silu(gate) * up, n < N.
-static int gemm_impl(const void* X, int x_f32, int ldx, int M, int K, const void* Wp, int N, int swiglu,
-                     const float* bias, const float* scale, const float* shift, void* Y, int ldy, int out_bf16,
-                     int act, int residual, float* ws, long long ws_floats, int* counters, int splitk,
-                     const float* rstats, int rgroups, float reps, float* sout, const float* gnext, float* yg,
-                     int* sgroups, const GemmArgs* rope, hipStream_t stream, const float* lnw = nullptr,
-                     const float* lnb = nullptr, float lneps = 0.f, float* sout1 = nullptr,
-                     const float* rstats1 = nullptr) {
-  // the packed buffers armed for this launch are consumed whatever happens below (one launch each)
-  const PackArm xpk = g_xpk, ypk = g_ypk, yp32k = g_yp32k, xp32k = g_xp32k;
-  g_xpk = g_ypk = g_yp32k = g_xp32k = PackArm{};
-  FO_REQUIRE(M > 0 && N > 0 && K > 0, "fo_gemm: bad shape M=%d N=%d K=%d", M, N, K);
-  FO_PACK_FITS(xpk, K, M, "fo_gemm (packed X)");
-  FO_PACK_FITS(xp32k, K, M, "fo_gemm (fp32 packed X)");
-  FO_PACK_FITS(ypk, N, M, "fo_gemm (packed output)");
-  FO_PACK_FITS(yp32k, N, M, "fo_gemm (fp32 packed output)");
-  FO_REQUIRE(!rstats || rgroups > 0, "fo_gemm: row statistics without a group count");
-  FO_REQUIRE(!sout || (!swiglu && !out_bf16 && (!yg || gnext)), "fo_gemm: row statistics need fp32 non-SwiGLU output");
-  FO_REQUIRE((K & 31) == 0, "fo_gemm: K=%d must be a multiple of 32", K);
-  FO_REQUIRE(ldx >= K, "fo_gemm: ldx=%d < K=%d", ldx, K);
-  FO_REQUIRE(ldy >= N, "fo_gemm: ldy=%d < N=%d", ldy, N);
-  FO_REQUIRE(!(swiglu && (bias || scale)), "fo_gemm: swiglu with bias/affine unsupported");
-  FO_REQUIRE(!scale == !shift, "fo_gemm: scale and shift go together");
-  // 65..128 rows on the large weight streams (a duplex tick whose sessions start a turn: the 5-token chat prefix on
-  // top of the 4 chunk rows; 8 x 9 = 72 rows): two X-stationary split-K launches on the two row halves (33..64 rows
-  // each) instead of 64-row tiles, which stream the whole weight once per row tile at ~1.4-2.5 TB/s (r05i duplex
-  // table: gate/up 193.8 us, down 110.4 us per layer at 72 rows).  Both halves take k_gemm_xsk, so their row
-  // statistics have the same group count ((N + 255) / 256) and the halves' rows tile the [M][groups] layout.
-  // 65..128 rows on the large weight streams: k_gemm_rows (the weights once) when its split-K slabs fit the workspace
-  bool rows_ok = false;
-  int rows_S = 1, rows_tp = 0, rows_G = 0;
-  {
-    const int nt_all = (swiglu ? 2 : 1) * ((N + 15) / 16);
-    const long long wb = (long long)nt_all * 16 * K * 2;
-    // (>= 16 MiB: the Qwen2 q|k|v -- RoPE + paged-KV append in the reduce -- and o too, which at 128 rows ran 64-row
-    // tiles re-reading the weights per row tile (q|k|v 80 us, r06q) or two row halves (o 2 x 22.8 us))
-    if (g_rows && M > (g_rows == 4 ? 32 : 64) && M <= 128 && x_f32 && !lnw && !sout1 && !rstats1 && splitk <= 1 &&
-        wb >= (16ll << 20) && (ldx % 4) == 0 && ((unsigned long long)X & 15) == 0 && !xpk.p0 && !xp32k.p0 &&
-        !g_force_nt &&
-        !g_force_nw && (!swiglu || nt_all % 2 == 0)) {
-      const int cus = num_cus();
-      if (g_rows >= 5) {   // (probes 5 / 6) the one-K-pass 10-tile partition
-        const int units = nt_all / 2, per = (units + cus - 1) / cus;
-        rows_tp = 2 * per;
-        rows_G = (units + per - 1) / per;
-        rows_S = 1;
-      } else if (g_rows != 2) {   // k_gemm_rows: the waves split the rows.  The workgroup's X (all rows over its K range)
-        // comes through the CU beside its weights, so K is split until a workgroup's tiles carry about as many bytes
-        // as its X: gate/up 3 K thirds x 14 (gate, up) pairs (28 tiles), one round of <= 256 workgroups; down 16 K
-        // slices x 14 tiles (profiles/r06o_gemm_rows_split.txt, r06p: gate/up at 128 rows 129.4 us on one K pass of
-        // 10 tiles, 102.7-110.0 on K halves of 20, 101.9 on thirds; down 68.9 on 8 slices of 7 tiles, 59.6-63.9)
-        const int ks = M <= 64 ? 2 : 3;
-        if (swiglu) {
-          const int units = nt_all / 2, per = (ks * units + cus - 1) / cus;
-          rows_tp = 2 * per;
-          rows_G = (units + per - 1) / per;
-          rows_S = ks;
-        } else {
-          rows_tp = nt_all % 14 == 0 ? 14 : 16;
-          rows_G = (nt_all + rows_tp - 1) / rows_tp;
-          rows_S = max(1, min(16, cus / rows_G));
-        }
-      } else {             // (probe) k_gemm_wrow: one tile per wave; gate/up 10 waves (5 pairs), one K pass; long-K 14 / 8
-        rows_tp = swiglu ? ((nt_all / 2) % 5 == 0 ? 10 : 8) : (nt_all % 14 == 0 ? 14 : 8);
-        rows_G = (nt_all + rows_tp - 1) / rows_tp;
-        rows_S = swiglu ? 1 : max(1, min(16, cus / rows_G));
-      }
-      const long long need = (long long)rows_S * 128 * nt_all * 16;
-      rows_ok = rows_tp <= (swiglu ? 30 : 16) && need <= ws_floats && ws != nullptr &&
-                (K >> 5) >= rows_S;
-    }
-  }
-  {
-    const long long wb = (long long)(swiglu ? 2 : 1) * ((N + 15) / 16) * 16 * K * 2;
-    const bool big = wb >= ((long long)g_xsk_min_mb << 20) || (K >= 8192 && wb >= (32ll << 20));
-    // (and the plain >= 8 MB projections -- the Qwen2 o: 57.0 us on 64-row tiles at 72 rows -- whose halves take
-    // the one-row-tile split-K kernels + k_gemm_reduce, the same statistics groups)
-    const bool mid_w = !swiglu && wb >= (8ll << 20);
-    if (!rows_ok && M > 64 && M <= 128 && x_f32 && !lnw && !rope && !sout1 && !rstats1 && splitk <= 1 && (big || mid_w) &&
-        xsk_mode() && !g_force_nt && !g_force_nw && !xpk.p0 && !ypk.p0 && !yp32k.p0 && !xp32k.p0 && (K >> 5) >= 56 &&
-        (ldx % 4) == 0 && ((swiglu ? 2 : 1) * ((N + 15) / 16)) % 2 == 0 && g_row_split) {
-      const int M0 = (M + 1) / 2, grp = (N + 255) / 256;
-      int sg = 0;
-      for (int h = 0; h < 2; ++h) {
-        const int r0 = h ? M0 : 0, Mh = h ? M - M0 : M0;
-        const size_t yb = (size_t)r0 * ldy * (out_bf16 ? 2 : 4);
-        int sgh = 0;
-        const int rc = gemm_impl(static_cast<const char*>(X) + (size_t)r0 * ldx * 4, x_f32, ldx, Mh, K, Wp, N, swiglu,
-                                 bias, scale, shift, static_cast<char*>(Y) + yb, ldy, out_bf16, act, residual, ws,
-                                 ws_floats, counters, splitk, rstats ? rstats + (size_t)r0 * rgroups : nullptr, rgroups,
-                                 reps, sout ? sout + (size_t)r0 * grp : nullptr, gnext,
-                                 yg ? yg + (size_t)r0 * ldy : nullptr, &sgh, nullptr, stream);
-        if (rc) return rc;
-        FO_REQUIRE(!sout || sgh == grp, "fo_gemm: row halves wrote %d statistics groups, expected %d", sgh, grp);
-        sg = sgh;
-      }
-      if (sgroups) *sgroups = sg;
-      return 0;
-    }
-  }
-  GemmArgs a;
-  a.X = X;
-  a.scale = scale;
-  a.shift = shift;
-  a.Wp = (const bf16_t*)Wp;
-  a.bias = bias;
-  a.Y = Y;
-  a.ws = ws;
-  a.counters = counters;
-  a.ldx = ldx;
-  a.ldy = ldy;
-  a.M = M;
-  a.K = K;
-  a.N = N;
-  a.act = act;
-  a.out_bf16 = out_bf16;
-  a.residual = residual;
-  a.sout = sout;
-  a.gnext = gnext;
-  a.yg = yg;
-  a.rstats = rstats;
-  a.rgroups = rgroups;
-  a.reps = reps;
-  a.ntiles = (swiglu ? 2 : 1) * ((N + 15) / 16);
-  a.rpos = a.rslot = nullptr;
-  a.rcos = a.rsin = nullptr;
-  a.rq = a.rk = a.rv = nullptr;
-  a.rH = a.rKVH = a.rhd = a.rPS = 0;
-  a.rkvb = 0;
-  a.lnw = lnw;
-  a.lnb = lnb;
-  a.lneps = lneps;
-  a.sout1 = sout1;
-  a.rstats1 = rstats1;
-  a.trc = g_trc;
-  a.xph = reinterpret_cast<const bf16x8*>(xpk.p0);
-  a.xpl = reinterpret_cast<const bf16x8*>(xpk.p1);
-  a.ypkh = reinterpret_cast<bf16_t*>(const_cast<void*>(ypk.p0));
-  a.ypkl = reinterpret_cast<bf16_t*>(const_cast<void*>(ypk.p1));
-  a.yp32 = reinterpret_cast<float*>(const_cast<void*>(yp32k.p0));
-  a.xp32 = reinterpret_cast<const float*>(xp32k.p0);
-  FO_REQUIRE(!a.xp32 || (lnw && M <= 64), "fo_gemm: the fp32 packed X is read by LayerNorm-on-load launches only");
-  FO_REQUIRE(!a.yp32 || (M <= 64 && !swiglu && !rope), "fo_gemm: fp32 packed output needs <= 64 plain rows");
-  a.prb = (M + 15) / 16;
-  FO_REQUIRE(!a.xph || (x_f32 && M <= 64 && !lnw), "fo_gemm: packed X needs fp32 X of <= 64 rows");
-  FO_REQUIRE(!a.ypkh || (M <= 64 && !swiglu && !rope), "fo_gemm: packed output needs <= 64 plain rows");
-  FO_REQUIRE(!sout1 || sout, "fo_gemm: row sums come with the sums of squares");
-  if (lnw) {
-    FO_REQUIRE(lnb && x_f32 && M <= 64 && !swiglu && rstats && rstats1 && rgroups > 0 && rgroups <= 64 && !rope &&
-               ldx % 4 == 0,
-               "fo_gemm_ln: fp32 X, M <= 64, producer statistics, plain epilogue only (M=%d K=%d)", M, K);
-  }
-  if (rope) {
-    FO_REQUIRE(!swiglu && !sout && !residual && !out_bf16 && act == 0 && !scale, "fo_gemm_qkv_rope: plain epilogue only");
-    FO_REQUIRE(rope->rhd % 32 == 0 && N == (rope->rH + 2 * rope->rKVH) * rope->rhd,
-               "fo_gemm_qkv_rope: N=%d != (H + 2 KVH) * hd with hd %% 32 == 0", N);
-    a.rpos = rope->rpos;
-    a.rslot = rope->rslot;
-    a.rcos = rope->rcos;
-    a.rsin = rope->rsin;
-    a.rq = rope->rq;
-    a.rk = rope->rk;
-    a.rv = rope->rv;
-    a.rH = rope->rH;
-    a.rKVH = rope->rKVH;
-    a.rhd = rope->rhd;
-    a.rPS = rope->rPS;
-    a.rkvb = g_kv_bf16;
-  }
-  if (rows_ok) {
-    a.S = rows_S;
-    a.counters = nullptr;
-    if (sgroups) *sgroups = (N + 255) / 256;
-    const int total = rows_S * rows_G;
-    const dim3 grid(8 * ((total + 7) / 8));
-    // (instantiated tile counts: the Qwen2 gate/up's 14 pairs and down's 14 tiles per workgroup, else the next size)
-#define FO_ROWS(NWV_, RPW_, NTC_, DW_, DX_, PR_, XL_)                                                                  \
-  do {                                                                                                                \
-    if (g_rows == 3 && PR_ == 0) /* (probe 3: the split consumer map, r06y: 79.3 vs 76.8 us, kept off) */            \
-      hipLaunchKernelGGL((k_gemm_rows<NWV_, RPW_, NTC_, DW_, DX_, false, PR_, XL_, 1>), grid, dim3(NWV_ * 64), 0,       \
-                         stream, a, rows_G, rows_tp);                                                                 \
-    else                                                                                                              \
-      hipLaunchKernelGGL((k_gemm_rows<NWV_, RPW_, NTC_, DW_, DX_, false, PR_, XL_, 0>), grid, dim3(NWV_ * 64), 0,       \
-                         stream, a, rows_G, rows_tp);                                                                 \
-  } while (0)
-#define FO_WROW(NWV_, DW_, DXS_) \
-  hipLaunchKernelGGL((k_gemm_wrow<NWV_, 8, DW_, DXS_>), grid, dim3(NWV_ * 64), 0, stream, a, rows_G)
-    if (g_rows >= 5) {   // (probes 5 / 6: the 10-tile gate/up without X loads -- WRONG results: the weight ring's
-                         // rate at 7 vs 11 k-steps of depth)
-      if (g_rows == 5) FO_ROWS(8, 1, 10, 7, 1, 1, 1);
-      else FO_ROWS(8, 1, 10, 11, 1, 1, 1);
-    } else if (g_rows == 2) {   // (probe) k_gemm_wrow
-      if (rows_tp == 10) FO_WROW(10, 12, 4);
-      else if (rows_tp == 14) FO_WROW(14, 8, 4);
-      else FO_WROW(8, 12, 4);
-    } else if (swiglu && rows_tp > 20) {
-      // the weights and X the same number of k-steps ahead: vmcnt retires in order, so the wait for a k-step's X also
-      // waits for every weight load issued before it -- an X lead shorter than the weights' caps their depth at it
-      // (r06w: 7 or 11 k-steps of weights alone, 85 us either way; with X 1 ahead the ring held ~1 k-step)
-      FO_ROWS(8, 1, 30, 2, 2, 0, 1);
-    } else if (swiglu) {
-      FO_ROWS(8, 1, 20, 3, 3, 0, 1);
-    } else if (rows_tp == 14) {
-      FO_ROWS(8, 1, 14, 4, 4, 0, 1);
-    } else {
-      FO_ROWS(8, 1, 16, 3, 3, 0, 1);
-    }
-#undef FO_WROW
-#undef FO_ROWS
-    int rc = fo::check_launch("fo_gemm/rows");
-    if (rc) return rc;
-    launch_reduce(a, swiglu, 128, N, M, stream);
-    fo::count_launch(FO_L_GEMM_ROWS);
-    fo::count_launch(FO_L_GEMM_REDUCE);
-    return fo::check_launch("fo_gemm/rows reduce");
-  }
-  // X-stationary persistent weight stream (k_gemm_xs) for the M <= 16 rows of a listen chunk / text step on
-  // K = 3584 layers (Qwen2 q|k|v, o, gate/up, lm_head): no split, no LayerNorm-on-load
-  // Measured (scripts/gemm_xs_ab.py, graph-replayed over weight copies beyond the Infinity Cache): gate/up
-  // + SwiGLU 56.1 -> 48.4 us at 16 rows, 47.4 -> 45.5 us at 8; lm_head equal (169.5 vs 169.9 us); the
-  // 26-33 MB o and q|k|v projections slower (one unit per workgroup: 12.3 -> 15.1, 18.7 -> 20.4 us), so
-  // only the SwiGLU pair takes this path.
-  if (x_f32 && M <= 16 && !lnw && K == XS_NW * XS_KPW * 32 && (a.ntiles % 2) == 0 && splitk <= 1 && xs_mode() &&
-      !g_force_nt && !g_force_nw && swiglu && (long long)a.ntiles * 16 * K >= (64ll << 20) && ldx % 4 == 0) {
-    const int units = a.ntiles / 2;
-    // as many workgroups as it takes for every one to get the same (ceil) number of units: 1184 gate/up
-    // pairs -> 237 x 5 (not 256 with 4 or 5: the 5-unit CUs would set the time); a CU can pull more than
-    // its 1/256 share of the HBM stream, so the idle CUs cost nothing
-    const int per = (units + num_cus() - 1) / num_cus();
-    const int G = (units + per - 1) / per;
-    a.S = 1;
-    if (sgroups) *sgroups = units;
-    if (sout) FO_REQUIRE(!swiglu && !rope, "fo_gemm: statistics with a paired epilogue");
-    switch (xs_variant()) {
-      case 1: hipLaunchKernelGGL((k_gemm_xs<XS_NW, XS_KPW, 1>), dim3(G), dim3(XS_NW * 64), 0, stream, a, units); break;
-      case 2: hipLaunchKernelGGL((k_gemm_xs<XS_NW, XS_KPW, 2>), dim3(G), dim3(XS_NW * 64), 0, stream, a, units); break;
-      case 3: hipLaunchKernelGGL((k_gemm_xs<8, 14>), dim3(G), dim3(8 * 64), 0, stream, a, units); break;
-      case 4: hipLaunchKernelGGL((k_gemm_xs<8, 14, 4>), dim3(G), dim3(8 * 64), 0, stream, a, units); break;
-      default: hipLaunchKernelGGL((k_gemm_xs<XS_NW, XS_KPW>), dim3(G), dim3(XS_NW * 64), 0, stream, a, units);
-    }
-    fo::count_launch(FO_L_GEMM_XS);
-    if (a.xph) fo::count_launch(FO_L_GEMM_XP);
-    return fo::check_launch("fo_gemm/xs");
-  }
-  // 17..64 rows on large weights (duplex ticks: 8 sessions x 4 framing-B tokens, the assistant prefix 8 x 5, prefixed
-  // first chunks): the X-stationary stream with K split over workgroups (k_gemm_xsk) + k_gemm_reduce
-  // only the weight streams: >= 64 MB (Qwen2 gate/up, down) or long-K >= 16 MB (the speech encoder's subsampling
-  // output linear, 19,456 x 1024 = 40 MB: 48.8 us per chunk on the split-K grid kernel, r04i); on the 26-33 MB
-  // q|k|v / o the one-row-tile kernels below are faster (r04d probe: o 14.8 vs 18.5 us, q|k|v 19.2 vs 24.4 us at 32 rows)
-  const long long wbytes0 = (long long)a.ntiles * 16 * K * 2;
-  const bool big_w0 = wbytes0 >= ((long long)g_xsk_min_mb << 20) || (K >= 8192 && wbytes0 >= (32ll << 20));
-  if (x_f32 && M > 16 && M <= 64 && !lnw && (a.ntiles % 2) == 0 && splitk <= 1 && xsk_mode() && !g_force_nt &&
-      !g_force_nw && big_w0 && ldx % 4 == 0 && !sout1 && (K >> 5) >= 56) {
-    const int RBk = (M + 15) / 16;
-    // 8 waves x KPW k-steps of X per split (hi in VGPRs, lo in LDS: KPW shrinks as the row blocks grow), UA units of
-    // weights in flight per wave (~28 KiB, k_gemm_xs's depth); every split has work (K >= 56 k-steps)
-    const int NWk = 8, KPWk = RBk == 2 ? 7 : (RBk == 3 ? (g_xsk_rb3 == 5 ? 5 : 4) : 3);
-    const int KSk = K >> 5;
-    const int S = (KSk + NWk * KPWk - 1) / (NWk * KPWk);
-    const int units = a.ntiles / 2;
-    const int per_split = max(1, num_cus() / S);
-    const int per = (units + per_split - 1) / per_split;
-    const int G = (units + per - 1) / per;
-    const long long need = (long long)S * RBk * 16 * a.ntiles * 16;
-    FO_REQUIRE(ws && need <= ws_floats, "fo_gemm/xsk: split-K workspace too small (%lld > %lld)", need, ws_floats);
-    a.S = S;
-    a.counters = nullptr;
-    if (sgroups) *sgroups = (N + 255) / 256;
-    const dim3 grid(8 * ((S * G + 7) / 8));
-    if (RBk == 2) hipLaunchKernelGGL((k_gemm_xsk<8, 7, 2, 2>), grid, dim3(512), 0, stream, a, units, G);
-    else if (RBk == 3 && KPWk == 5) hipLaunchKernelGGL((k_gemm_xsk<8, 5, 3, 2>), grid, dim3(512), 0, stream, a, units, G);
-    else if (RBk == 3) hipLaunchKernelGGL((k_gemm_xsk<8, 4, 3, 3>), grid, dim3(512), 0, stream, a, units, G);
-    else hipLaunchKernelGGL((k_gemm_xsk<8, 3, 4, 4>), grid, dim3(512), 0, stream, a, units, G);
-    int rc = fo::check_launch("fo_gemm/xsk");
-    if (rc) return rc;
-    launch_reduce(a, swiglu, RBk * 16, N, M, stream);
-    fo::count_launch(FO_L_GEMM_XSK);
-    fo::count_launch(FO_L_GEMM_REDUCE);
-    if (a.ypkh) fo::count_launch(FO_L_GEMM_YPACK);
-    if (a.yp32) fo::count_launch(FO_L_GEMM_YPACK32);
-    return fo::check_launch("fo_gemm/xsk reduce");
-  }
-  // mid-size row counts on large weights (the Qwen2 prefills of a turn: assistant prefix, the first
-  // chunk with its chat prefix, the system prompt; 17..64 rows): one row tile of ceil(M/16) row blocks
-  // against 4-tile column groups, so X (fp32, re-read by every column group) costs about what the
-  // weights do, and no grid of 64-row tiles streams X four times per weight byte
-  // (small weights with 33..64 rows -- the duplex encoder at 8 sessions x 7 frames -- take the same
-  // one-row-tile kernels with single-tile column groups instead of 64-row tiles on 64 workgroups)
-  const bool big_w = (long long)a.ntiles * 16 * K >= (8ll << 20);
-  const bool mid = x_f32 && !lnw && M > 16 && M <= 64 && (big_w || M > 32);
-  const int RB = mid ? (M + 15) / 16 : (M <= 16 ? 1 : (M <= 32 ? 2 : 4));
-  const int mt = (M + RB * 16 - 1) / (RB * 16);
-  // tiles per workgroup: the activation rows are re-read by every workgroup, so workgroups that
-  // cover more output columns read X fewer times per weight byte (measured, gemm_sweep.py)
-  int NT = swiglu ? 2 : 1;
-  int S_auto = 0;
-  int launch_pipe = 0, nw_pref = 0;
-  const int KS = K >> 5;
-  if (mid) {
-    NT = big_w ? (a.ntiles % 4 == 0 ? 4 : 2) : (swiglu ? 2 : 1);
-  } else if (RB == 1) {
-    // measured policy (gemm_sweep.py, gemm_graph_sweep.py): wide layers (>= 1024 tiles: Qwen2 gate/up, lm_head) take 4
-    // tiles per workgroup; long-K layers (Qwen2 down) 4 tiles and a 4-way K split; mid-size grids
-    // (> 256 tiles: Qwen2 qkv) 2 tiles; small ones 1
-    if (a.ntiles >= 1024) NT = 4;
-    // Qwen2 down (592 k-steps, 224 tiles): 7 tiles x 8-way K split, pipelined (32 x 8 = 256 workgroups; 8 tiles: 224): the
-    // activation rows are read by a quarter as many column groups as with 4 tiles x 4 ways; 31.7 -> 29.7 us at 16
-    // rows, 29.7 -> 28.7 us at 8, reduce launch included (profiles/r03g_down_sweep.txt)
-    else if (KS >= 256 && a.ntiles >= 128) {
-      NT = a.ntiles % 8 == 0 ? 8 : 4;
-      if (down_tiles() == 7 && a.ntiles % 7 == 0) NT = 7;
-      S_auto = NT >= 7 ? down_split() : 4;
-    }
-    else if (KS >= 128 && a.ntiles <= 64) S_auto = 4;  // narrow long-K (TTS down): 10.9 -> 8.2 us in a graph
-    else if (a.ntiles > 256) NT = 2;
-    // small SwiGLU pairs over 512+ tiles (the TTS gate/up, 608 tiles, 17.4 MB): 2 pairs per workgroup on 8
-    // waves keeps the grid within one round of the 256 CUs (152 instead of 304 workgroups): 7.83 -> 7.16 us
-    // graph-replayed (profiles/r02s_tts_gemm_sweep.txt)
-    if (swiglu && a.ntiles >= 512 && a.ntiles < 1024 && (long long)a.ntiles * 16 * K < (32ll << 20) &&
-        a.ntiles % 4 == 0) {
-      NT = 4;
-      nw_pref = 8;
-    }
-    // Pipelined weight stream, 2-step groups (policy measured in the turn bench, A/B twice in one
-    // call: 388-390 -> 383-386 ms/turn, p50 first PCM 50 -> 48.5 ms).  Isolated (scripts/
-    // gemm_gu_sweep.py, gemm_pipe_ab.py; two alternating weight copies): gate/up at <= 8 rows on 2
-    // tiles x 8 waves 50.5 -> 44.4 us, down 32.0 -> 29.5 us, lm_head 177 -> 172 us.  Gate/up at 9-16
-    // rows keeps the plain 4-tile loop: pipelined with a 2-way K split it is faster alone (53.8 ->
-    // 51.2 us) but made the pipelined listen stage slower (turn 388 -> 408 ms).
-    const int pm = pipe_mode();
-    if (x_f32 && pm != 0 && pm != 3) {
-      launch_pipe = pm;   // sweeps: every one-row-tile fp32-X GEMM
-    } else if (x_f32 && (long long)a.ntiles * 16 * K >= (32ll << 20) && pm != 0) {
-      if (pm != 3) launch_pipe = pm;
-      else if (!swiglu || M <= 8) launch_pipe = 2;
-      if (pm == 3 && swiglu && M <= 8 && !g_force_nt && !g_force_nw) {
-        NT = 2;
-        nw_pref = 8;
-      }
-    }
-    if (g_force_nt) NT = g_force_nt;
-    FO_REQUIRE(NT == 1 || NT == 2 || NT == 4 || NT == 8 || (NT == 7 && !swiglu), "fo_gemm: tiles per workgroup %d", NT);
-    FO_REQUIRE(!swiglu || NT >= 2, "fo_gemm: swiglu needs tile pairs");
-    if (a.ntiles % NT) NT = swiglu ? 2 : 1;
-  } else if (RB == 2) {
-    // speech-encoder shapes (M = 32): narrow long-K layers (FFN w_2, subsampling out) split K 4 ways
-    if (!swiglu && a.ntiles <= 64 && KS >= 96) S_auto = 4;
-    if (g_force_nt == 1 || g_force_nt == 2) NT = swiglu ? 2 : g_force_nt;
-    if (a.ntiles % NT) NT = swiglu ? 2 : 1;
-  }
-  int nw_pref4 = 0;
-  if (RB == 4 && g_force_nt && x_f32 && !lnw && !rope) {   // sweeps (fo_gemm_tune): forced tiles per workgroup
-    NT = g_force_nt;
-    if (swiglu && NT < 2) NT = 2;
-    if (a.ntiles % NT) NT = swiglu ? 2 : 1;
-  } else if (RB == 4 && !mid && x_f32 && !lnw && M > 64) {
-    // 64-row tiles (prefills of 65+ rows: the AR decoder's sentence prefill at 8 sessions x 32-40 sub-token rows, the
-    // speech encoder's im2col convolutions).  Measured (scripts/gemm_big_sweep.py, profiles/r04q_gemm_big_sweep.txt):
-    // 8 waves splitting K inside the workgroup everywhere but the K = 32 conv1 (4); 4 column tiles per X read when
-    // that still gives >= 128 workgroups or K is long (then split K over workgroups until the grid nears 256); else
-    // one tile (pair) per workgroup.  AR prefill down 67.8 -> 26.3 us, gate/up 56.2 -> 40.3 us, q|k|v 20.3 -> 16.4,
-    // o 12.2 -> 10.4; conv2 130.9 -> 89.6 us, conv1 28.5 -> 15.3 us
-    nw_pref4 = KS <= 2 ? 4 : 8;
-    const int wg4 = a.ntiles / 4 * mt;
-    if (a.ntiles % 4 == 0 && KS > 2 && (wg4 >= 128 || KS >= 128)) {
-      NT = 4;
-      if (KS >= 128) S_auto = (KS >= 256 || wg4 * 4 <= 256) ? 4 : (wg4 * 2 <= 256 ? 2 : 1);
-    } else {
-      NT = swiglu ? 2 : 1;
-    }
-  }
-  // the epilogue rotates the (i, i + hd/2) tile pair a workgroup holds; a 17..64-row RoPE projection on large
-  // weights (the Qwen2 q|k|v of a duplex tick or a prefill) keeps the 4-tile column groups of the plain path and
-  // always splits K, so k_gemm_reduce (which pairs the tiles itself) runs that epilogue: one X read per 4 tiles
-  // instead of per pair (r04g trace: the 2-tile split q|k|v 33.9 + 5 us at 33..48 rows)
-  const bool rope4 = rope && mid && NT == 4 && splitk <= 1 && !g_force_nt;
-  if (rope && !rope4) NT = 2;
-  if (lnw && NT > 2) NT = 2;
-  const int groups = a.ntiles / NT;
-  if (mid) {  // split K: 2 ways on wide layers (Qwen2 gate/up), until the grid covers the chip on narrow ones
-    S_auto = groups >= 192 ? (big_w ? 2 : 1) : (256 + groups - 1) / groups;
-    if (S_auto > 4) S_auto = 4;
-    if (S_auto > KS / 16) S_auto = KS / 16 > 0 ? KS / 16 : 1;
-  }
-  int S = splitk > 0 ? splitk : (S_auto && !g_force_nt ? S_auto : (mid ? 1 : fo_gemm_pick_split(M, groups, K)));
-  if (rstats && !lnw && !mid) S = 1;  // (split RMSNorm consumers: k_gemm_reduce applies the rstd)
-  if (S > (K >> 5)) S = K >> 5;
-  if (rope4 && S < 2) S = 2;   // the pair epilogue needs the reduce launch
-  a.S = S;
-  if (S > 1) {
-    const long long need = (long long)S * mt * RB * 16 * a.ntiles * 16;
-    FO_REQUIRE(ws && need <= ws_floats, "fo_gemm: split-K workspace too small (%lld > %lld)", need, ws_floats);
-  }
-  dim3 grid(groups, mt, S);
-  // one-row-tile plain splits merge inside the launch (last split to arrive sums and finishes; tickets in
-  // the caller's zeroed counters, left zeroed); otherwise k_gemm_reduce follows
-  const bool small_w = (long long)a.ntiles * 16 * K < (32ll << 20);
-  const bool merged = S > 1 && counters && RB == 1 && !a.sout1 && !swiglu && !lnw && !mid &&
-                      (merge_mode() == 1 || (merge_mode() == 2 && small_w));
-  a.counters = merged ? counters : nullptr;
-  if (merged) FO_REQUIRE((long long)groups * mt <= (1 << 20), "fo_gemm: too many tiles for the merge tickets");
-  if (sgroups) *sgroups = (S > 1 && !merged) ? (N + 255) / 256 : groups;
-  const bool wstream = (long long)a.ntiles * 16 * K >= (32ll << 20);
-  const long long wgs = (long long)groups * mt * S;
-  if (lnw) {
-    const int nw = wgs <= 128 ? 16 : 8;
-    dim3 blk(nw * 64);
-#define FO_LN(NT_, RB_, NW_) hipLaunchKernelGGL((k_gemm_ln<NT_, RB_, NW_>), grid, blk, 0, stream, a)
-    if (RB == 1) {
-      if (NT == 2) { if (nw == 16) FO_LN(2, 1, 16); else FO_LN(2, 1, 8); }
-      else { if (nw == 16) FO_LN(1, 1, 16); else FO_LN(1, 1, 8); }
-    } else if (RB == 2) {
-      if (NT == 2) { if (nw == 16) FO_LN(2, 2, 16); else FO_LN(2, 2, 8); }
-      else { if (nw == 16) FO_LN(1, 2, 16); else FO_LN(1, 2, 8); }
-    } else {   // 33..64 rows (the duplex encoder: 8 sessions x 7 framing-B frames): 2 k-steps in flight per wave
-      if (NT == 2) hipLaunchKernelGGL((k_gemm_ln<2, 4, 8, 2>), grid, dim3(512), 0, stream, a);
-      else hipLaunchKernelGGL((k_gemm_ln<1, 4, 8, 4>), grid, dim3(512), 0, stream, a);
-    }
-#undef FO_LN
-  } else if (mid) {
-    // 2 k-steps in flight per wave keep the RB x NT accumulators and fragments within 4 waves / SIMD
-    const int nw = (NT == 4 || wgs >= 384) ? 4 : 8;
-#define FO_MID(NT_, RB_, NW_, SW_) launch_mid<NT_, RB_, NW_, SW_>(grid, a, stream)
-#define FO_MID_RB(NT_, NW_, SW_) { if (RB == 2) FO_MID(NT_, 2, NW_, SW_); else if (RB == 3) FO_MID(NT_, 3, NW_, SW_); else FO_MID(NT_, 4, NW_, SW_); }
-    if (swiglu) {
-      if (NT == 4) FO_MID_RB(4, 4, true) else if (nw == 4) FO_MID_RB(2, 4, true) else FO_MID_RB(2, 8, true)
-    } else if (NT == 1) {
-      if (nw == 4) FO_MID_RB(1, 4, false) else FO_MID_RB(1, 8, false)
-    } else {
-      if (NT == 4) FO_MID_RB(4, 4, false) else if (nw == 4) FO_MID_RB(2, 4, false) else FO_MID_RB(2, 8, false)
-    }
-#undef FO_MID_RB
-#undef FO_MID
-  } else if (RB == 1) {
-    // measured (scripts/gemm_sweep.py, MI355X): one workgroup per CU wants 16 waves, a couple per
-    // CU 8, many 4; 4 k-steps in flight per wave is the sweet spot everywhere on the hot path
-    int nw = wgs <= 160 ? 16 : (wgs <= 256 ? (NT == 1 ? 16 : 8) : ((NT == 4 || wgs >= 1024) ? 4 : 8));
-    if (nw_pref) nw = nw_pref;
-    if (g_force_nw) nw = g_force_nw;
-    g_launch_pipe = launch_pipe;
-    g_launch_u = g_force_u ? g_force_u : 4;
-    if (swiglu) {
-      if (NT == 8) launch_nw<8, 1, true>(nw, wstream, x_f32, grid, a, stream);
-      else if (NT == 4) launch_nw<4, 1, true>(nw, wstream, x_f32, grid, a, stream);
-      else launch_nw<2, 1, true>(nw, wstream, x_f32, grid, a, stream);
-    } else {
-      if (NT == 8) launch_nw<8, 1, false>(nw, wstream, x_f32, grid, a, stream);
-      else if (NT == 7) launch_nw<7, 1, false>(nw, wstream, x_f32, grid, a, stream);
-      else if (NT == 4) launch_nw<4, 1, false>(nw, wstream, x_f32, grid, a, stream);
-      else if (NT == 2) launch_nw<2, 1, false>(nw, wstream, x_f32, grid, a, stream);
-      else launch_nw<1, 1, false>(nw, wstream, x_f32, grid, a, stream);
-    }
-  } else if (RB == 2) {
-    int nw = wgs <= 128 ? 16 : 8;
-    if (g_force_nw) nw = g_force_nw;
-    if (swiglu) launch_nw<2, 2, true>(nw, wstream, x_f32, grid, a, stream);
-    else if (NT == 2) launch_nw<2, 2, false>(nw, wstream, x_f32, grid, a, stream);
-    else launch_nw<1, 2, false>(nw, wstream, x_f32, grid, a, stream);
-  } else {
-    if (x_f32) {
-      // 64-row tiles (prefills of 65+ rows, im2col convolutions): waves split K inside the workgroup (nw4), the
-      // column tiles per workgroup share each X read; fo_gemm_tune forces (waves, tiles) for sweeps
-      int nw4 = nw_pref4 ? nw_pref4 : 4;
-      if (g_force_nw) nw4 = g_force_nw;
-#define FO_B4(NT_, NW_, SW_) launch_gemm<NT_, 4, NW_, 2, SW_>(wstream, x_f32, grid, a, stream)
-      if (swiglu) {
-        if (NT == 8) FO_B4(8, 4, true);
-        else if (NT == 4) { if (nw4 >= 8) FO_B4(4, 8, true); else FO_B4(4, 4, true); }
-        else { if (nw4 >= 16) FO_B4(2, 16, true); else if (nw4 == 8) FO_B4(2, 8, true); else FO_B4(2, 4, true); }
-      } else if (NT == 8) FO_B4(8, 4, false);
-      else if (NT == 4) { if (nw4 >= 8) FO_B4(4, 8, false); else FO_B4(4, 4, false); }
-      else if (NT == 2) { if (nw4 >= 16) FO_B4(2, 16, false); else if (nw4 == 8) FO_B4(2, 8, false); else FO_B4(2, 4, false); }
-      else { if (nw4 >= 16) FO_B4(1, 16, false); else if (nw4 == 8) FO_B4(1, 8, false); else FO_B4(1, 4, false); }
-#undef FO_B4
-    } else {
-      if (swiglu) launch_gemm<2, 4, 4, 4, true>(wstream, x_f32, grid, a, stream);
-      else if (NT == 4) launch_gemm<4, 4, 4, 4, false>(wstream, x_f32, grid, a, stream);
-      else if (NT == 2) launch_gemm<2, 4, 4, 4, false>(wstream, x_f32, grid, a, stream);
-      else launch_gemm<1, 4, 4, 4, false>(wstream, x_f32, grid, a, stream);
-    }
-  }
-  const bool pipe_k = RB == 1 && x_f32 && (launch_pipe || (g_launch_u != 4 && NT <= 2));
-  g_launch_pipe = 0;
-  g_launch_u = 4;
-  fo::count_launch(lnw ? FO_L_GEMM_LN : (mid ? FO_L_GEMM_MID : (pipe_k ? FO_L_GEMM_PIPE : FO_L_GEMM_OTHER)));
-  if (lnw && a.xp32) fo::count_launch(FO_L_GEMM_XP32);
-  if (a.xph && x_f32 && !lnw && !swiglu && !pipe_k) fo::count_launch(FO_L_GEMM_XP);
-  if (rope4) fo::count_launch(FO_L_GEMM_ROPE4);
-  if (a.ypkh) fo::count_launch(FO_L_GEMM_YPACK);
-  if (a.yp32) fo::count_launch(FO_L_GEMM_YPACK32);
-  if (S > 1 && !merged) {
-    int rc = fo::check_launch("fo_gemm/split");
-    if (rc) return rc;
-    launch_reduce(a, swiglu, mt * RB * 16, N, M, stream);
-    fo::count_launch(FO_L_GEMM_REDUCE);
-  }
-  return fo::check_launch("fo_gemm");
-}
-
 int fo_gemm(const void* X, int x_f32, int ldx, int M, int K, const void* Wp, int N, int swiglu, const float* bias,
             const float* scale, const float* shift, void* Y, int ldy, int out_bf16, int act, int residual, float* ws,
             long long ws_floats, int* counters, int splitk, hipStream_t stream) {
-  return gemm_impl(X, x_f32, ldx, M, K, Wp, N, swiglu, bias, scale, shift, Y, ldy, out_bf16, act, residual, ws,
-                   ws_floats, counters, splitk, nullptr, 0, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+  GemmCall c;
+  c.X = X, c.x_f32 = x_f32, c.ldx = ldx, c.M = M, c.K = K;
+  c.Wp = Wp, c.N = N, c.swiglu = swiglu;
+  c.bias = bias, c.scale = scale, c.shift = shift;
+  c.Y = Y, c.ldy = ldy, c.out_bf16 = out_bf16, c.act = act, c.residual = residual;
+  c.ws = ws, c.ws_floats = ws_floats, c.counters = counters, c.splitk = splitk;
+  c.stream = stream;
+  return gemm_impl(c);
 }
 
 int fo_gemm_rms(const void* X, int x_f32, int ldx, int M, int K, const void* Wp, int N, int swiglu, const float* bias,
                 void* Y, int ldy, int act, int residual, float* ws, long long ws_floats, int* counters, int splitk,
                 const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
                 int* sgroups, hipStream_t stream) {
-  return gemm_impl(X, x_f32, ldx, M, K, Wp, N, swiglu, bias, nullptr, nullptr, Y, ldy, 0, act, residual, ws,
-                   ws_floats, counters, splitk, rstats, rgroups, eps, sout, gnext, yg, sgroups, nullptr, stream);
+  GemmCall c;
+  c.X = X, c.x_f32 = x_f32, c.ldx = ldx, c.M = M, c.K = K;
+  c.Wp = Wp, c.N = N, c.swiglu = swiglu;
+  c.bias = bias;
+  c.Y = Y, c.ldy = ldy, c.act = act, c.residual = residual;
+  c.ws = ws, c.ws_floats = ws_floats, c.counters = counters, c.splitk = splitk;
+  c.rstats = rstats, c.rgroups = rgroups, c.reps = eps;
+  c.sout = sout, c.gnext = gnext, c.yg = yg, c.sgroups = sgroups;
+  c.stream = stream;
+  return gemm_impl(c);
 }
 
 int fo_gemm_ln(const float* X, int ldx, int M, int K, const void* Wp, int N, const float* bias, const float* lnw,
                const float* lnb, float eps, const float* rsum, const float* rsumsq, int rgroups, float* Y, int ldy,
                int act, float* ws, long long ws_floats, int splitk, hipStream_t stream) {
   FO_REQUIRE(lnw && lnb && rsum && rsumsq, "fo_gemm_ln: LayerNorm weight, bias and row statistics required");
-  return gemm_impl(X, 1, ldx, M, K, Wp, N, 0, bias, nullptr, nullptr, Y, ldy, 0, act, 0, ws, ws_floats, nullptr,
-                   splitk, rsumsq, rgroups, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, stream, lnw, lnb, eps,
-                   nullptr, rsum);
+  GemmCall c;
+  c.X = X, c.x_f32 = 1, c.ldx = ldx, c.M = M, c.K = K;
+  c.Wp = Wp, c.N = N;
+  c.bias = bias;
+  c.Y = Y, c.ldy = ldy, c.act = act;
+  c.ws = ws, c.ws_floats = ws_floats, c.splitk = splitk;
+  c.rstats = rsumsq, c.rstats1 = rsum, c.rgroups = rgroups;
+  c.lnw = lnw, c.lnb = lnb, c.lneps = eps;
+  c.stream = stream;
+  return gemm_impl(c);
 }
 
 int fo_gemm_rowstats(const void* X, int x_f32, int ldx, int M, int K, const void* Wp, int N, const float* bias,
                      float* Y, int ldy, int act, int residual, float* ws, long long ws_floats, int* counters,
                      int splitk, float* rsum, float* rsumsq, int* sgroups, hipStream_t stream) {
   FO_REQUIRE(rsum && rsumsq, "fo_gemm_rowstats: statistics buffers required");
-  return gemm_impl(X, x_f32, ldx, M, K, Wp, N, 0, bias, nullptr, nullptr, Y, ldy, 0, act, residual, ws, ws_floats,
-                   counters, splitk, nullptr, 0, 0.f, rsumsq, nullptr, nullptr, sgroups, nullptr, stream, nullptr,
-                   nullptr, 0.f, rsum, nullptr);
+  GemmCall c;
+  c.X = X, c.x_f32 = x_f32, c.ldx = ldx, c.M = M, c.K = K;
+  c.Wp = Wp, c.N = N;
+  c.bias = bias;
+  c.Y = Y, c.ldy = ldy, c.act = act, c.residual = residual;
+  c.ws = ws, c.ws_floats = ws_floats, c.counters = counters, c.splitk = splitk;
+  c.sout = rsumsq, c.sout1 = rsum, c.sgroups = sgroups;
+  c.stream = stream;
+  return gemm_impl(c);
 }
 
 int fo_gemm_qkv_rope(const void* X, int x_f32, int ldx, int M, int K, const void* Wp, int N, const float* bias,
@@ -2523,7 +2211,7 @@ int fo_gemm_qkv_rope(const void* X, int x_f32, int ldx, int M, int K, const void
                      float* kc, float* vc, int H, int KVH, int hd, int PS, hipStream_t stream) {
   FO_REQUIRE(pos && slot && cos_t && sin_t && q_out && kc && vc && PS > 0 && H > 0 && KVH > 0,
              "fo_gemm_qkv_rope: missing rope/cache arguments");
-  GemmArgs r;
+  GemmArgs r{};
   r.rpos = pos;
   r.rslot = slot;
   r.rcos = cos_t;
@@ -2535,8 +2223,16 @@ int fo_gemm_qkv_rope(const void* X, int x_f32, int ldx, int M, int K, const void
   r.rKVH = KVH;
   r.rhd = hd;
   r.rPS = PS;
-  return gemm_impl(X, x_f32, ldx, M, K, Wp, N, 0, bias, nullptr, nullptr, q_out, N, 0, 0, 0, ws, ws_floats, counters,
-                   splitk, rstats, rgroups, eps, nullptr, nullptr, nullptr, nullptr, &r, stream);
+  GemmCall c;
+  c.X = X, c.x_f32 = x_f32, c.ldx = ldx, c.M = M, c.K = K;
+  c.Wp = Wp, c.N = N;
+  c.bias = bias;
+  c.Y = q_out, c.ldy = N;
+  c.ws = ws, c.ws_floats = ws_floats, c.counters = counters, c.splitk = splitk;
+  c.rstats = rstats, c.rgroups = rgroups, c.reps = eps;
+  c.rope = &r;
+  c.stream = stream;
+  return gemm_impl(c);
 }
 
 // Software-pipelining mode of the one-row-tile weight-stream GEMMs (k_gemm_wpipe): 0 off, 1 U k-steps,
@@ -2549,15 +2245,6 @@ int fo_gemm_set_pipe(int on) {
   return prev;
 }
 
-// X-stationary kernel switch for the eligible M <= 16 GEMMs (k_gemm_xs): 0 off, 1 on.  Process-global
-// (sweeps, A/B); returns the previous setting.  Unset, FO_GEMM_XS (default on) decides.
-int fo_gemm_set_xsk_min_mb(int mb) {
-  FO_REQUIRE(mb >= 0, "fo_gemm_set_xsk_min_mb: %d", mb);
-  const int prev = g_xsk_min_mb;
-  g_xsk_min_mb = mb;
-  return prev;
-}
-
 int fo_set_kv_bf16(int on) {
   FO_REQUIRE(on == 0 || on == 1, "fo_set_kv_bf16: 0 or 1");
   const int prev = g_kv_bf16;
@@ -2565,15 +2252,17 @@ int fo_set_kv_bf16(int on) {
   return prev;
 }
 
+// 65..128-row GEMMs on >= 16 MiB weights: 1 k_gemm_rows (default), 0 two row halves of the <= 64-row kernels.
+// Process-global (A/B, tests); returns the previous setting.  Unset, FO_GEMM_ROWS decides.
 int fo_gemm_set_rows(int on) {
-  FO_REQUIRE(on >= 0 && on <= 6,
-             "fo_gemm_set_rows: 0 (row halves), 1 (k_gemm_rows), probes 2 (k_gemm_wrow), 3 (split consumer map), "
-             "4 (from 33 rows), 5 / 6 (the weight ring alone)");
+  FO_REQUIRE(on == 0 || on == 1, "fo_gemm_set_rows: 0 (row halves) or 1 (k_gemm_rows)");
   const int prev = g_rows;
   g_rows = on;
   return prev;
 }
 
+// X-stationary kernel switch for the eligible M <= 16 GEMMs (k_gemm_xs): 0 off, 1 on.  Process-global
+// (sweeps, A/B); returns the previous setting.  Unset, FO_GEMM_XS (default on) decides.
 int fo_gemm_set_xs(int on) {
   FO_REQUIRE(on == 0 || on == 1, "fo_gemm_set_xs: 0 or 1");
   const int prev = xs_mode() ? 1 : 0;
@@ -2586,41 +2275,6 @@ int fo_gemm_set_merge(int on) {
   const int prev = merge_mode();
   g_merge = on;
   return prev;
-}
-
-int fo_gemm_set_xs_variant(int v) {
-  FO_REQUIRE(v >= 0 && v <= 4, "fo_gemm_set_xs_variant: 0 (shipped), 1 (no reduction: wrong results), 2 (default "
-             "cache policy), 3 (round 4's 8 waves x 14 k-steps), 4 (8 x 14, barrier-free reduction)");
-  const int prev = xs_variant();
-  g_xs_var = v;
-  return prev;
-}
-
-int fo_probe_seam(const float* xo, int M, const void* wo, const float* bo, float* x, const float* gnext, float* yg,
-                  float* sout, const void* wgu, int n_gu_out, float* h, float eps, int* ready, int* ready_timeout,
-                  void* trace, int mode, hipStream_t s) {
-  // mode 0: the seam launch (o + gate/up); 1: its o workgroups alone; 2: its gate/up workgroups alone (ready must
-  // already hold n_o)
-  constexpr int K = 3584, NO = 3584;
-  FO_REQUIRE(M >= 1 && M <= 16 && n_gu_out % 16 == 0 && mode >= 0 && mode <= 2 && ready && ready_timeout,
-             "fo_probe_seam: M=%d (1..16), gate/up outputs %d (a multiple of 16), mode %d", M, n_gu_out, mode);
-  GemmArgs ao{};
-  ao.X = xo; ao.Wp = reinterpret_cast<const bf16_t*>(wo); ao.bias = bo; ao.Y = x; ao.ldx = K; ao.ldy = NO;
-  ao.M = M; ao.K = K; ao.N = NO; ao.ntiles = NO / 16; ao.S = 1; ao.residual = 1; ao.gnext = gnext; ao.yg = yg;
-  ao.sout = sout;
-  GemmArgs ag{};
-  ag.X = yg; ag.Wp = reinterpret_cast<const bf16_t*>(wgu); ag.Y = h; ag.ldx = NO; ag.ldy = n_gu_out; ag.M = M;
-  ag.K = K; ag.N = n_gu_out; ag.ntiles = 2 * n_gu_out / 16; ag.S = 1; ag.rstats = sout; ag.rgroups = NO / 32;
-  ag.reps = eps;
-  const int n_o = NO / 32, units = n_gu_out / 16;
-  const int per = (units + num_cus() - 1) / num_cus(), G = (units + per - 1) / per;
-  unsigned long long* trc = reinterpret_cast<unsigned long long*>(trace);
-  if (mode == 0) hipLaunchKernelGGL(k_seam_o_gu, dim3(n_o + G), dim3(512), 0, s, ao, ag, n_o, units, G, ready,
-                                    ready_timeout, trc);
-  else if (mode == 1) hipLaunchKernelGGL(k_seam_o_gu, dim3(n_o), dim3(512), 0, s, ao, ag, n_o, units, G, ready,
-                                         ready_timeout, trc);
-  else hipLaunchKernelGGL(k_seam_o_gu, dim3(G), dim3(512), 0, s, ao, ag, 0, units, G, ready, ready_timeout, trc);
-  return fo::check_launch("fo_probe_seam");
 }
 
 int fo_gemm_set_trace(void* trace) {
@@ -2645,12 +2299,6 @@ int fo_gemm_set_xpack32(const void* p, int cols, int cap_rb) {
 
 int fo_gemm_set_ypack(void* hi, void* lo, int cols, int cap_rb) {
   return arm_pack(g_ypk, hi, lo, true, cols, cap_rb, "fo_gemm_set_ypack");
-}
-
-int fo_gemm_set_u(int u) {
-  FO_REQUIRE(u == 0 || u == 4 || u == 7 || u == 8, "fo_gemm_set_u: u must be 0/4/7/8");
-  g_force_u = u;
-  return 0;
 }
 
 int fo_gemm_tune(int nw, int nt) {
@@ -2678,3 +2326,4 @@ int fo_pack_weight(const void* W, int src_bf16, int N, int K, int ldw, void* out
 }
 
 }  // extern "C"
+

@@ -58,9 +58,7 @@ _SIGS = {
     "fo_event_elapsed_ms": (c_int, [c_vp, c_vp, ctypes.POINTER(c_float)]),
     "fo_event_destroy": (c_int, [c_vp]),
     "fo_gemm_tune": (c_int, [c_int, c_int]),
-    "fo_gemm_set_u": (c_int, [c_int]),
     "fo_gemm_set_xs": (c_int, [c_int]),
-    "fo_gemm_set_xs_variant": (c_int, [c_int]),
     "fo_gemm_set_merge": (c_int, [c_int]),
     "fo_gemm_set_trace": (c_int, [c_vp]),
     "fo_gemm_set_xpack": (c_int, [c_vp, c_vp, c_int, c_int]),
@@ -77,10 +75,7 @@ _SIGS = {
                                   c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_float, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "fo_enc_attn_out": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp,
                                 c_vp, c_vp, c_vp, c_float, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "fo_probe_seam": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_float, c_vp,
-                              c_vp, c_vp, c_int, c_vp]),
     "fo_attn_max_rows": (c_int, [c_int]),
-    "fo_gemm_set_xsk_min_mb": (c_int, [c_int]),
     "fo_gemm_set_rows": (c_int, [c_int]),
     "fo_set_kv_bf16": (c_int, [c_int]),
     "fo_conv_set_trace": (c_int, [c_vp]),
@@ -96,7 +91,6 @@ _SIGS = {
     "fo_gemm_w8_rows": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp,
                                 c_ll, c_vp, c_vp, c_int, c_float, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), c_vp]),
     "fo_gemm_pick_split": (c_int, [c_int, c_int, c_int]),
-    "fo_gemm_workspace_floats": (c_ll, [c_int, c_int, c_int, c_int]),
     "fo_gemm": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
                         c_int, c_int, c_vp, c_ll, c_vp, c_int, c_vp]),
     "fo_gemm_rms": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int,

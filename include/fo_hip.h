@@ -83,43 +83,24 @@ int fo_gemm_rowstats(const void* X, int x_f32, int ldx, int M, int K, const void
                      int splitk, float* rsum, float* rsumsq, int* sgroups, hipStream_t stream);
 /* sweep hook: force (waves, 16-column tiles per workgroup) of the M <= 16 GEMM kernels; 0 = automatic */
 int fo_gemm_tune(int nw, int nt);
-/* sweep hook: k-steps in flight per wave of the one-row-tile fp32-X grid kernel (0 = policy, 4, 7 on 16 waves, 8 on 8 waves) */
-int fo_gemm_set_u(int u);
-/* X-stationary persistent weight stream (k_gemm_xs) for the M <= 16 fp32-X GEMMs with K = 3584 (Qwen2 q|k|v,
- * o, gate/up, lm_head): 0 off, 1 on (default; FO_GEMM_XS=0 turns it off).  Process-global; returns the
- * previous setting. */
+/* X-stationary persistent weight stream (k_gemm_xs) for the M <= 16 fp32-X SwiGLU GEMMs with K = 3584 on >= 128 MiB
+ * of weights (the Qwen2 gate/up): 0 off (the grid kernels), 1 on (default; FO_GEMM_XS=0 turns it off).
+ * Process-global; returns the previous setting. */
 int fo_gemm_set_xs(int on);
-/* probe hook: variant of the k_gemm_xs launch (0 shipped; 1 no cross-wave reduction -- WRONG results, a timing
- * bound; 2 default-policy weight loads; 3 round 4's 8 waves x 14 k-steps; 4 8 x 14 with the barrier-free
- * reduction).  Process-global; returns the previous one. */
-int fo_gemm_set_xs_variant(int v);
-/* probe hook: the weight size (MiB) from which 17..64-row fp32 GEMMs take k_gemm_xsk (default 128; long-K >= 32 MiB
- * layers always).  Process-global; returns the previous value. */
-int fo_gemm_set_xsk_min_mb(int mb);
-/* probe hook: 65..128-row GEMMs on >= 16 MiB weights through k_gemm_rows (1, default: the waves split the rows, the
- * weights through an LDS-DMA ring) or as two row-half launches of the <= 64-row kernels (0); probes: 2 = k_gemm_wrow
- * (one tile per wave, X staged once per workgroup), 3 = k_gemm_rows with each wave computing two row blocks for half
- * the tiles, 4 = k_gemm_rows from 33 rows, 5 / 6 = its weight ring alone (no X loads: WRONG results, timing bounds).
- * Unset, FO_GEMM_ROWS decides.  Process-global; returns the previous setting. */
+/* A/B hook: 65..128-row GEMMs on >= 16 MiB weights through k_gemm_rows (1, default: the waves split the rows, the
+ * weights through an LDS-DMA ring) or as two row-half launches of the <= 64-row kernels (0).  Any other value is
+ * refused (-2).  Unset, FO_GEMM_ROWS decides.  Process-global; returns the previous setting. */
 int fo_gemm_set_rows(int on);
 /* A/B of a bf16 paged KV (verdict r05 item 6; the reference's k_proj / v_proj outputs under torch.autocast(bf16),
  * models/pipeline.py:67-68): 1 = the q|k|v RoPE epilogues round every appended K / V element to bf16 (storage stays
  * fp32, so the numerics are a bf16 cache's and the layout is unchanged), 0 = fp32 (default).  Unset, FO_KV_BF16
  * decides.  Process-global; returns the previous setting. */
 int fo_set_kv_bf16(int on);
-/* probe (scripts/seam_probe.py): the Qwen2 o -> gate/up seam at <= 16 rows as one launch (k_seam_o_gu); xo [M][3584]
- * attention output, wo / wgu packed o and SwiGLU-paired gate/up weights, x the residual stream (updated), yg / sout the
- * next norm's input and partial sums of squares ([M][112]), h the SwiGLU output [M][n_gu_out]; ready: a zeroed int
- * (left at 112), ready_timeout set when the bounded poll gave up; trace: 4 wall clocks per workgroup or NULL; mode 0
- * the seam, 1 its o workgroups alone, 2 its gate/up workgroups alone. */
-int fo_probe_seam(const float* xo, int M, const void* wo, const float* bo, float* x, const float* gnext, float* yg,
-                  float* sout, const void* wgu, int n_gu_out, float* h, float eps, int* ready, int* ready_timeout,
-                  void* trace, int mode, hipStream_t s);
 /* Split-K of the one-row-tile plain GEMMs (Qwen2 / TTS down, encoder FFN w2) merged inside the launch:
  * each split stores its partial tile write-through and takes the tile's ticket in `counters` (zeroed
  * ints, left zeroed); the last split sums every partial in split order (k_gemm_reduce's order, bit for
  * bit) and runs the epilogue, so no reduce launch follows.  0: slabs + k_gemm_reduce everywhere; 1: merge
- * every eligible split; 2 (default, FO_GEMM_MERGE overrides): merge splits of weights < 32 MB (the TTS
+ * every eligible split; 2 (default, FO_GEMM_MERGE overrides): merge splits of weights < 64 MiB (the TTS
  * down), where the reduce launch costs more than the write-through drain.  NULL counters always take the
  * two-launch form.  Process-global; returns the previous setting. */
 int fo_gemm_set_merge(int on);
@@ -224,7 +205,7 @@ int fo_gemm_w8_rows(const float* X, int ldx, int M, int K, const void* q, const 
                     int swiglu, float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters,
                     const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
                     int* sgroups, hipStream_t stream);
-/* Software-pipelined one-row-tile fp32-X weight-stream GEMMs (M <= 16, >= 32 MB of weights: the next
+/* Software-pipelined one-row-tile fp32-X weight-stream GEMMs (M <= 16, >= 64 MiB of weights: the next
  * k-group's weights + X in flight during this group's MFMAs).  3 (default): the measured policy; 0: plain
  * loops; 1 / 2: every such GEMM pipelined with 4 / 2 k-steps per group (sweeps).  Unset, the
  * FO_GEMM_PIPE environment variable (0-3) decides.  Process-global state (for sweeps and tests); returns the
@@ -234,7 +215,6 @@ long long fo_pack_weight_elems(int N, int K);
 int fo_pack_weight(const void* W, int src_bf16, int N, int K, int ldw, void* out, int tile_base, int tile_stride,
                    hipStream_t stream);
 int fo_gemm_pick_split(int M, int n_tile_groups, int K);
-long long fo_gemm_workspace_floats(int M, int N, int K, int swiglu);
 /* X: bf16 (x_f32=0) or fp32 (x_f32=1, split into bf16 hi+lo MFMA passes).  Epilogue order:
  * +bias, *scale+shift (per column), activation (0 none,1 relu,2 silu,3 gelu), +Y if residual. */
 int fo_gemm(const void* X, int x_f32, int ldx, int M, int K, const void* Wp, int N, int swiglu, const float* bias,

@@ -77,6 +77,22 @@ def test_attention_refuses_a_pack_that_does_not_fit():
     assert "fo_relpos_attention_fused: packed output" in err(), err()
 
 
+def test_rows_switch_takes_only_the_two_shipped_paths():
+    """fo_gemm_set_rows: 0 (row halves) and 1 (k_gemm_rows) round-trip; the former probe modes 2..6 are refused and
+    leave the setting as it was."""
+    lib, err = _lib()
+    start = lib.fo_gemm_set_rows(1)
+    assert start in (0, 1)
+    try:
+        assert lib.fo_gemm_set_rows(0) == 1
+        assert lib.fo_gemm_set_rows(1) == 0
+        for v in range(2, 7):
+            assert lib.fo_gemm_set_rows(v) == -2 and "fo_gemm_set_rows" in err(), v
+        assert lib.fo_gemm_set_rows(1) == 1   # the refusals changed nothing
+    finally:
+        lib.fo_gemm_set_rows(start)
+
+
 def test_launch_counters_exist_and_reset():
     lib, _ = _lib()
     n = lib.fo_launch_counts(None, 0)
