@@ -56,13 +56,9 @@ class CodecEngine:
         self.p_pre = ops.PackedConv(*self.conv_pre)
         self.p_ups = []
         for w, b, u, k in self.ups:
-            pad = (k - u) // 2
             phases = []
-            for r in range(u):
-                j0 = (r + pad) % u
-                pc = ops.PackedConv(w, b, transposed=(j0, u))
-                off = (r + pad - j0) // u
-                phases.append((r, pc, pc.K - 1 - off))  # (phase, weights, pad of the equivalent conv)
+            for r, j0, pad_r in self.polyphase(u, k):
+                phases.append((r, ops.PackedConv(w, b, transposed=(j0, u)), pad_r))  # (phase, weights, conv pad)
             self.p_ups.append(phases)
         self.use_graphs = os.environ.get("FO_CODEC_GRAPH", "1") != "0"
         # ResBlock1 stages as grouped launches (fo_conv_cl_multi): the u polyphase components of each upsampling
@@ -78,6 +74,20 @@ class CodecEngine:
         self._graphs = {}   # (B, T, stream) -> static buffers (+ captured graph), least recently used first
         self.p_res = [[(k, [(ops.PackedConv(c1[0], c1[1]), c1[2], None if c2 is None else ops.PackedConv(c2[0], c2[1]))
                             for c1, c2 in convs]) for k, convs in stage] for stage in self.res]
+
+    @staticmethod
+    def polyphase(u, k):
+        """ConvTranspose1d(stride u, kernel k, padding (k - u) // 2) as u stride-1 convolutions: [(r, j0, pad_r)] --
+        output phase r (time steps r, r + u, ...) meets taps j0, j0 + u, ... (PackedConv(transposed=(j0, u)) packs
+        them reversed) and is that conv with padding pad_r on the input."""
+        pad = (k - u) // 2
+        out = []
+        for r in range(u):
+            j0 = (r + pad) % u
+            K = (k - j0 + u - 1) // u
+            off = (r + pad - j0) // u
+            out.append((r, j0, K - 1 - off))
+        return out
 
     def flops(self, T):
         """Algorithmic FLOPs of one generator call on T tokens (2*Cin*Cout*K*Tout per conv)."""

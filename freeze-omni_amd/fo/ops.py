@@ -910,8 +910,18 @@ def conv_cl_multi(descs, B, Cin, Cout, device, summed=False):
 
 # channel counts that take fo_conv_pair_multi by default: 16 and 32 (r03l: the 16-channel stage 247 -> 173 us a
 # call, the 32-channel one 272 -> 233 us); at 64 channels the kernel needs 122 KB of LDS (one workgroup per CU)
-# and is slower than two launches (3 x 111 vs 6 x 43 us), so that stage keeps k_conv_cl
-PAIR_CHANNELS = (16, 32)
+# and is slower than two launches (3 x 111 vs 6 x 43 us), so that stage keeps k_conv_cl.  The pair kernel is built
+# for the default chunk widths only: under FO_CONV_CK=16 (fo_vocoder.hip pick_ck) fo_conv_pair_multi refuses 32
+# channels, so that stage keeps k_conv_cl too
+def _pair_channels():
+    try:
+        ck = int(os.environ.get("FO_CONV_CK", "32"))
+    except ValueError:
+        ck = 32
+    return (16,) if ck == 16 else (16, 32)
+
+
+PAIR_CHANNELS = _pair_channels()
 
 
 def conv_pair_multi(members, B, C, T, device, slope=0.1, summed=False, oscale=1.0, gadd=None):
