@@ -97,7 +97,9 @@ __global__ __launch_bounds__(256) void k_argmax_part(const float* logits, int ld
   const int i0 = c * AMAX_CH + threadIdx.x * 8;
   float best = -INFINITY;
   int besti = NOIDX, b = 0;
-  if (i0 + 8 <= V && (ld & 3) == 0) {
+  // 16-byte loads need the group's own address aligned: the row stride AND the base pointer (a column-offset view
+  // of a wider buffer reaches fo_sample with ld % 4 == 0 and a base that is only 4-byte aligned)
+  if (i0 + 8 <= V && (reinterpret_cast<uintptr_t>(lg + i0) & 15u) == 0) {
     const float4 p0 = reinterpret_cast<const float4*>(lg + i0)[0];
     const float4 p1 = reinterpret_cast<const float4*>(lg + i0)[1];
     const float f[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
@@ -435,16 +437,26 @@ __device__ int sample_row_general(const float* lg, int V, int k, float T, float 
   if (tid == 0) sm.si[2] = -1;
   __syncthreads();
   if (argmax_only) {
+    // The first token in this path's own order is the smallest index of the top KEY (Kp - 1 after a full descent):
+    // -0.0 sorts below +0.0 in every radix pass above, so a float comparison with m would take a -0.0 ahead of a
+    // +0.0 when the maximum is zero.  Rows flagged bad (NaN / +inf / -inf only: no meaningful Kp) keep lg == m.
+    constexpr int FLT = 1 << 30;  // rank of a float-only match: after every key match (V < 2^30)
+    const bool by_key = tp > 0.f && Kp != 0u && !*bad_out;
     int best = 0x7fffffff;
-    for (int i = tid; i < V; i += 1024)
-      if (i != ban && lg[i] == m && i < best) best = i;
+    for (int i = tid; i < V; i += 1024) {
+      if (i == ban) continue;
+      const float x = lg[i];
+      const uint32_t key = fkey(x);
+      if (by_key && key == Kp - 1u && kept_k(i, key)) best = min(best, i);
+      else if (x == m) best = min(best, i + FLT);
+    }
     sm.bi[tid] = best;
     __syncthreads();
     for (int o = 512; o > 0; o >>= 1) {
       if (tid < o) sm.bi[tid] = min(sm.bi[tid], sm.bi[tid + o]);
       __syncthreads();
     }
-    const int pick = sm.bi[0];
+    const int pick = sm.bi[0] == 0x7fffffff ? sm.bi[0] : (sm.bi[0] & (FLT - 1));
     if (probs)
       for (int i = tid; i < V; i += 1024) probs[i] = i == pick ? 1.f : 0.f;
     __syncthreads();
