@@ -82,7 +82,8 @@ constexpr int DEC_MAXK = MAXPG * 16;
 constexpr int DEC_NW = 8, DEC_NT = DEC_NW * 64;  // 8 waves: a key per thread up to 512 keys
 // One (work item, head) of the decode attention; the normalised output row is left in o_s[HD] (LDS, visible to
 // every thread after the call) and, unless to_lds_only, stored to out (+ the packed copy when armed).  Returns
-// false when the host contract is broken (the row is then NaN, stored and in o_s).
+// false when the host contract is broken (the row is then NaN, stored and in o_s).  h is the query head; its keys
+// and values are those of kv head h / (H / KVH) (H == KVH for the AR decoder: the same head).
 template <int HD>
 __device__ bool attn_decode_row(const AttnArgs& a, const int it, const int h, float* o_s, bool to_lds_only) {
   static_assert(HD % 4 == 0 && HD <= 128, "decode attention: head_dim");
@@ -114,12 +115,15 @@ __device__ bool attn_decode_row(const AttnArgs& a, const int it, const int h, fl
     return false;
   }
   __syncthreads();
-  const size_t page_sz = (size_t)a.KVH * a.PS * HD, head_off = (size_t)h * a.PS * HD;
+  const int kvh = h / (a.H / a.KVH);
+  const size_t page_sz = (size_t)a.KVH * a.PS * HD, head_off = (size_t)kvh * a.PS * HD;
   // P.V layout: HD/4 lanes per key (one float4 of the V row each), 64/(HD/4) keys per wave-instruction,
   // the waves on interleaved keys.  The first NPF rounds of V rows are loaded here, in flight together
-  // with the K rows, so the P.V pass after the softmax waits on no memory for up to 256-512 keys.
+  // with the K rows, so the P.V pass after the softmax waits on no memory for up to 224-512 keys.
   constexpr int LPK = HD / 4, KPW = 64 / LPK, VSTR = DEC_NW * KPW;
-  constexpr int NPF = 512 / VSTR < 16 ? 512 / VSTR : 16;
+  // (head_dim 128: 14 rounds, 224 keys -- with 16 the GQA launch below, which holds this body beside the multi-row
+  // one, spills a VGPR)
+  constexpr int NPF = HD == 128 ? 14 : (512 / VSTR < 16 ? 512 / VSTR : 16);
   const int sub = lane / LPK, l4 = lane % LPK;
   float4 vpf[NPF];
 #pragma unroll
@@ -208,6 +212,42 @@ template <int HD>
 __global__ __launch_bounds__(DEC_NT) void k_attn_decode(AttnArgs a) {
   __shared__ float o_s[HD];
   attn_decode_row<HD>(a, blockIdx.x, blockIdx.y, o_s, false);
+}
+
+// One-token GQA steps (the Qwen2 text step: 7 query heads per kv head, one token per session) on the grid of the
+// multi-row kernel, (items, kv heads, split slots), with the path chosen per item on the device from the item's own
+// key count -- a captured graph's launch serves a context as it grows:
+//   L <= GQA_DEC_KEYS: slot z runs the single-row body above for query heads kvh * G + z, + nsplit, ... and stores out
+//     (+ the packed copy) directly -- no MFMA layout staging, no partials, no ticket, and a result that does not
+//     depend on nsplit / keys_per_split.  The text step's 16 slots give one head per workgroup; slots >= G leave
+//     after the key count, as empty split slots do.
+//   otherwise: attn_rows_body and its in-launch merge, unchanged.
+// Every slot of an item reads the same L, so all of them take the same branch.  The two bodies' LDS sits side by
+// side (77 + 22 KB; either body alone already runs one workgroup per CU).
+// GQA_DEC_KEYS = 448, the measured crossover (scripts/attn_gqa_crossover.py, 8 sessions, 16 slots of 128 keys, graph
+// replays, against k_attn_mfma<128, 8, 1> before this launch existed; profiles/gqa_decode_crossover.txt): 150 keys
+// 7.3 against 13.9 us, 230 keys 9.1 / 14.0, 384 keys 12.4 / 14.6, 448 keys 14.4 / 15.0, 512 keys 15.7 / 15.2 -- the
+// single-row body grows by ~2.4 us per 100 keys (one CU pulls a head's whole K / V), the split body by ~0.4.
+constexpr int GQA_DEC_KEYS = 448;
+static_assert(GQA_DEC_KEYS <= DEC_NT, "the single-row body scores one key per thread");
+template <int HD>
+__global__ __launch_bounds__(DEC_NT) void k_attn_gqa_decode(AttnArgs a) {
+  static_assert(DEC_NW == 8, "shares the 8-wave multi-row body's block");
+  __shared__ float o_s[HD];
+  const int it = blockIdx.x, kvh = blockIdx.y, sp = blockIdx.z;
+  const int L = a.tok_nvis[a.items ? a.items[3 * it + 1] : it];
+  if (L <= GQA_DEC_KEYS) {
+    const int G = a.H / a.KVH;
+    for (int g = sp; g < G; g += a.nsplit) {
+      // (a per-iteration copy of the page size: the body's per-lane address arithmetic, all derived from it, is then
+      // computed inside the iteration; hoisted out of the loop it costs 54 spilled VGPRs)
+      AttnArgs b = a;
+      asm volatile("" : "+s"(b.PS));
+      attn_decode_row<HD>(b, it, kvh * G + g, o_s, false);
+    }
+    return;
+  }
+  attn_rows_body<HD, DEC_NW, 1, false>(a, it, kvh, sp);
 }
 
 // The AR speech decoder's attention fused with its o projection, residual add and the next RMSNorm's statistics
@@ -856,6 +896,18 @@ int fo_attention(const float* q, int T, const int* items, int n_items, int max_r
     return fo::check_launch("fo_attention/decode");
   }
   dim3 grid(n_items, KVH, nsplit);
+  // one token per item under GQA at head_dim 128 (the Qwen2 text step): the launch that picks the single-row body or
+  // the multi-row one per item on the device (k_attn_gqa_decode).  Static splits without tickets end in
+  // k_attn_combine, which would overwrite a directly stored row, so they keep the multi-row launch.
+  const int G = H / KVH;
+  const bool gqa_dec = hd == 128 && KVH < H && G <= 8 && max_rows == G && (items || T == n_items) &&
+                       (tickets || nsplit == 1) && attn_waves() == 8 && !a.trc;
+  if (gqa_dec) {
+    hipLaunchKernelGGL((k_attn_gqa_decode<128>), grid, dim3(DEC_NT), 0, s, a);
+    fo::count_launch(FO_L_ATTN_GQA_DECODE);
+    if (a.oph) fo::count_launch(FO_L_ATTN_OPACK);
+    return fo::check_launch("fo_attention/gqa_decode");
+  }
   // splits under 64 keys (the text step's short contexts spread over more CUs: a split's K / V arrive at one CU's
   // memory parallelism) take the 2-wave form with 32-key tiles
   const bool small = hd == 128 && tickets && keys_per_split < 64 && max_rows <= 16 && !a.trc;

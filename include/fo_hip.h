@@ -161,6 +161,8 @@ enum FoLaunchKind {
   FO_L_GEMM_W8 = 20,    /* k_w8: the general <= 16-row FP8-weight GEMM (fo_gemm_w8) */
   FO_L_GEMM_W8_XS = 21, /* k_w8_xs: the X-stationary FP8-weight gate/up stream (fo_gemm_w8, SwiGLU at K = 3584) */
   FO_L_GEMM_W8_ROWS = 22, /* k_w8_rows (+ its merge): the 17..64-row X-stationary split-K FP8-weight stream (fo_gemm_w8_rows) */
+  FO_L_ATTN_GQA_DECODE = 23, /* k_attn_gqa_decode: one-token GQA steps at head_dim 128 (the Qwen2 text step); per item the
+                                single-row fp32 body up to GQA_DEC_KEYS keys, the multi-row split body beyond */
   FO_LAUNCH_KINDS = 24
 };
 int fo_launch_counts(long long* out, int n);
@@ -273,7 +275,12 @@ int fo_rope_kv_write(const float* qkv, int ldq, int T, int H, int KVH, int hd, c
  * tok_nvis[t] keys of its sequence (causal: own cache index + 1, full/unmasked: all).  items
  * [n_items][3] = (sequence, first token, token count), token count * H/KVH <= max_rows <= 16;
  * items may be NULL when every sequence contributes one token (n_items == T: item b = sequence b = token b).
- * Split-KV (nsplit from fo_attn_nsplit) + combine. */
+ * Split-KV (nsplit from fo_attn_nsplit) + combine.
+ * One token per item under GQA at hd 128 (KVH < H, H/KVH <= 8, max_rows == H/KVH; with tickets, or nsplit == 1) runs
+ * k_attn_gqa_decode on the same grid: an item of at most GQA_DEC_KEYS (fo_attn.hip) visible keys takes the single-row
+ * fp32 body, one query head per split slot, stored directly (tickets and partials untouched, the result independent
+ * of nsplit and keys_per_split); a longer one the multi-row split body and its in-launch merge.  Chosen per item on
+ * the device from tok_nvis, so one captured launch serves a context as it grows. */
 int fo_attention(const float* q, int T, const int* items, int n_items, int max_rows, const int* tok_nvis,
                  const int* block_table, int maxb, int PS, const float* kc, const float* vc, int H, int KVH, int hd,
                  float scale, int nsplit, float* part_ml, float* part_o, float* out, int* tickets,
