@@ -242,8 +242,8 @@ extern "C" {
 
 int fo_fill_hash(void* out, int out_bf16, long long n, unsigned long long key, float center, float scale,
                  hipStream_t s) {
-  FO_REQUIRE(out && n >= 0, "fo_fill_hash: bad args");
-  if (n == 0) return 0;
+  FO_REQUIRE(n >= 0 && (out || n == 0), "fo_fill_hash: bad args");
+  if (n == 0) return 0;  // (an empty tensor's address is null)
   hipLaunchKernelGGL(k_fill_hash, dim3(grid_for(n)), dim3(256), 0, s, out, out_bf16, n, (uint64_t)key, center, scale);
   return fo::check_launch("fo_fill_hash");
 }
@@ -251,6 +251,11 @@ int fo_fill_hash(void* out, int out_bf16, long long n, unsigned long long key, f
 int fo_rmsnorm(const float* x, int ldx, int M, int D, const float* w, float eps, float* out, int ldo, int round_fp16,
                hipStream_t s) {
   FO_REQUIRE(M > 0 && D > 0 && (D & 3) == 0 && (ldx & 3) == 0 && (ldo & 3) == 0, "fo_rmsnorm: bad shape");
+  // the kernel reads x and w and writes out as float4: row strides that are multiples of 4 keep every row aligned
+  // only from an aligned base
+  FO_REQUIRE(x && w && out && (((uintptr_t)x | (uintptr_t)w | (uintptr_t)out) & 15) == 0,
+             "fo_rmsnorm: x %p, w %p and out %p must be 16-byte aligned (float4 loads and stores)", (const void*)x,
+             (const void*)w, (void*)out);
   hipLaunchKernelGGL(k_rmsnorm, dim3(M), dim3(256), 0, s, x, ldx, D, w, eps, out, ldo, round_fp16);
   return fo::check_launch("fo_rmsnorm");
 }

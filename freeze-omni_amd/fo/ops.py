@@ -623,13 +623,30 @@ def tcf_permute(x, B, T, F, C, out):
     return out
 
 
+def _check_stream_layout(what, cache, slots, x, B, KC, T, D):
+    """fo_im2col_conv1d and fo_conv_cache_update take no row stride for x or cache: x is [B * T][D] and cache
+    [pool][KC][D], both fp32 and dense."""
+    assert x.dtype == F32 and x.is_contiguous() and x.shape[-1] == D and x.numel() >= B * T * D, \
+        f"{what}: x {tuple(x.shape)} strides {x.stride()} is not a dense fp32 [{B} * {T}][{D}]"
+    if cache is not None:
+        assert cache.dtype == F32 and cache.is_contiguous() and cache.dim() == 3 and \
+            tuple(cache.shape[1:]) == (KC, D) and (slots is not None or cache.shape[0] >= B), \
+            f"{what}: cache {tuple(cache.shape)} strides {cache.stride()} is not a dense fp32 [>= {B}][{KC}][{D}]"
+    if slots is not None:
+        assert slots.dtype == I32 and slots.is_contiguous() and slots.numel() >= B, f"{what}: slots"
+
+
 def im2col_conv1d(cache, slots, x, B, KC, T, D, K, S, out):
+    _check_stream_layout("im2col_conv1d", cache, slots, x, B, KC, T, D)
+    assert out.dtype == F32 and out.stride(-1) == 1 and out.stride(0) >= D * K, "im2col_conv1d: out"
     _lib.call("fo_im2col_conv1d", ptr(cache), ptr(slots), x.data_ptr(), B, KC, T, D, K, S, out.data_ptr(),
               out.stride(0), stream(x.device))
     return out
 
 
 def conv_cache_update(cache, slots, x, B, KC, T, D):
+    assert cache is not None, "conv_cache_update: no cache"
+    _check_stream_layout("conv_cache_update", cache, slots, x, B, KC, T, D)
     _lib.call("fo_conv_cache_update", cache.data_ptr(), ptr(slots), x.data_ptr(), B, KC, T, D, stream(x.device))
 
 

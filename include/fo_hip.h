@@ -228,7 +228,8 @@ int fo_gemm(const void* X, int x_f32, int ldx, int M, int K, const void* Wp, int
 int fo_fill_hash(void* out, int out_bf16, long long n, unsigned long long key, float center, float scale,
                  hipStream_t s);
 /* Qwen2RMSNorm / LlamaRMSNorm (transformers, reached from models/audioLLM.py:482 and
- * models/decoder/decoder.py:299-311,343); round_fp16 mirrors the cast back to an fp16 input dtype. */
+ * models/decoder/decoder.py:299-311,343); round_fp16 mirrors the cast back to an fp16 input dtype.
+ * D, ldx and ldo are multiples of 4 and x, w and out 16-byte aligned (float4 access); anything else returns -2. */
 int fo_rmsnorm(const float* x, int ldx, int M, int D, const float* w, float eps, float* out, int ldo, int round_fp16,
                hipStream_t s);
 /* torch.nn.LayerNorm of the speech encoder (models/encoder/transformer.py:343-346,261,278,287) and of the
@@ -425,7 +426,7 @@ int fo_conv_post_cl(const float* x, int B, int T, int C, const void* w, const fl
 /* llm2TTS.find_min_sum_index window search (models/decoder/llm2tts.py:70-112): res = {min_sum, cut} */
 int fo_silence_cut(const float* x, int L, int N, float* res, hipStream_t s);
 /* the same search for `rows` rows of one vocoder call in one launch: row r at x + r * ld (ld >= L), its
-   (min window sum, cut index) at res + 2 r; each row is staged in LDS when it fits (<= ~37k samples) */
+   (min window sum, cut index) at res + 2 r; each row is staged in LDS when it fits (<= 36,798 samples) */
 int fo_silence_cut_rows(const float* x, long long ld, int rows, int L, int N, float* res, hipStream_t s);
 
 /* ---------------------------------------------------------------- codec encoder (fo_codec_enc.hip)
