@@ -52,6 +52,8 @@ def get_args(argv=None):
                    help="Qwen2 gate/up/down weights: bf16, or weight-only FP8 (e4m3 codes x a power of two per row)")
     p.add_argument("--llm_mlp_fp8_rows", type=int, choices=[16, 64], default=16,
                    help="with --llm_mlp_weights fp8: the most rows of a Qwen2 step that stream the FP8 codes")
+    p.add_argument("--llm_kv", choices=["fp32", "bf16"], default="fp32",
+                   help="Qwen2 paged KV cache element: fp32, or bf16 (half the memory and attention bytes)")
     p.add_argument("--role", default="You are a helpful assistant.")
     p.add_argument("--max_text_tokens", type=int, default=MAX_TEXT_TOKENS)
     args = p.parse_args(argv)

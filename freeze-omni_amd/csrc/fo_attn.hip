@@ -4,8 +4,9 @@
 //    decoder).  Reference: transformers Qwen2Attention/LlamaAttention reached from
 //    models/audioLLM.py:482 and models/decoder/decoder.py:294-312 (DynamicCache concat per layer).
 //    Here the cache is a pool of fixed-size pages per layer, laid out [page][kv_head][slot][hd]
-//    (fp32) so one head's keys in a page are contiguous; sequences own block tables, so a
-//    shared system prompt is shared pages and growth never copies.
+//    (fp32, or bf16 for the Qwen2 stack's opt-in llm_kv="bf16") so one head's keys in a page are
+//    contiguous; sequences own block tables, so a shared system prompt is shared pages and growth
+//    never copies.
 //    Ragged batch: every token carries (sequence, absolute position); causal mode lets a query
 //    see keys at positions <= its own, full mode (the reference's eager attention with
 //    attention_mask=None / all-ones masks, decoder.py:140,175,302) sees the whole sequence.
@@ -22,10 +23,17 @@
 
 namespace {
 
+// Element o of the paged cache `base`: kv16: f2bf(x) as a 2-byte element of a bf16 cache; else fp32, the
+// bf16 value under rkvb (fo_set_kv_bf16, as the q|k|v epilogues do).  One kernel serves both layouts, so the value
+// that is rounded is computed by the same instructions.
+__device__ __forceinline__ void kv_put(void* base, size_t o, float x, int kv16, int rkvb) {
+  if (kv16) reinterpret_cast<bf16_t*>(base)[o] = f2bf(x);
+  else reinterpret_cast<float*>(base)[o] = rkvb ? bf2f(f2bf(x)) : x;
+}
 __global__ __launch_bounds__(256) void k_rope_kv_write(const float* qkv, int ldq, int T, int H, int KVH, int hd,
                                                        const int* pos, const int* slot, const float* cos_t,
-                                                       const float* sin_t, float* q_out, float* kc, float* vc,
-                                                       int PS) {
+                                                       const float* sin_t, float* q_out, void* kc, void* vc,
+                                                       int PS, int kv16, int rkvb) {
   const int t = blockIdx.x;
   const int half = hd >> 1;
   const float* row = qkv + (size_t)t * ldq;
@@ -46,21 +54,21 @@ __global__ __launch_bounds__(256) void k_rope_kv_write(const float* qkv, int ldq
       q_out[(size_t)t * H * hd + (size_t)h * hd + i] = o1;
       q_out[(size_t)t * H * hd + (size_t)h * hd + i + half] = o2;
     } else {
-      float* d = kc + (((size_t)page * KVH + (h - H)) * PS + off) * hd;
-      d[i] = o1;
-      d[i + half] = o2;
+      const size_t d = (((size_t)page * KVH + (h - H)) * PS + off) * hd;
+      kv_put(kc, d + i, o1, kv16, rkvb);
+      kv_put(kc, d + i + half, o2, kv16, rkvb);
     }
   }
   const float* vsrc = row + (size_t)(H + KVH) * hd;
   for (int e = threadIdx.x; e < KVH * hd; e += blockDim.x) {
     const int h = e / hd, i = e % hd;
-    vc[(((size_t)page * KVH + h) * PS + off) * hd + i] = vsrc[e];
+    kv_put(vc, (((size_t)page * KVH + h) * PS + off) * hd + i, vsrc[e], kv16, rkvb);
   }
 }
 
 #include "fo_attn_rows.h"
 
-template <int HD, int NW = 4, int RT = 1, bool TR = false>
+template <int HD, int NW = 4, int RT = 1, bool TR = false, bool KV16 = false>
 __global__ __launch_bounds__(NW * 64) void k_attn_mfma(AttnArgs a) {
   if constexpr (TR) {
 #pragma nounroll
@@ -69,7 +77,7 @@ __global__ __launch_bounds__(NW * 64) void k_attn_mfma(AttnArgs a) {
       __syncthreads();
     }
   } else {
-    attn_rows_body<HD, NW, RT, TR>(a, blockIdx.x, blockIdx.y, blockIdx.z);
+    attn_rows_body<HD, NW, RT, TR, KV16>(a, blockIdx.x, blockIdx.y, blockIdx.z);
   }
 }
 
@@ -80,11 +88,37 @@ __global__ __launch_bounds__(NW * 64) void k_attn_mfma(AttnArgs a) {
 // more than 1/16 full here, and no split / merge round trip is needed at <= 4096 keys.
 constexpr int DEC_MAXK = MAXPG * 16;
 constexpr int DEC_NW = 8, DEC_NT = DEC_NW * 64;  // 8 waves: a key per thread up to 512 keys
+// 4 bf16 of a bf16 cache, widened
+__device__ __forceinline__ float4 bf4_to_f4(uint2 u) {
+  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                     __uint_as_float(u.y & 0xffff0000u));
+}
+// The decode body's two sums, spelled out: 4 elements of a key's score, and a lane's 4 outputs += p * v.  Contraction
+// is off, so the fmaf calls are the only fused operations and nothing is fused or regrouped around them -- every
+// instantiation of the body (fp32 or bf16 cache, any kernel it is inlined into) then rounds at the same places.
+__device__ __forceinline__ float dec_dot4(float s, const float* q, float4 k) {
+#pragma clang fp contract(off)
+  return s + fmaf(q[3], k.w, fmaf(q[2], k.z, fmaf(q[1], k.y, q[0] * k.x)));
+}
+__device__ __forceinline__ void dec_pv(float4& acc, float p, float4 v) {
+#pragma clang fp contract(off)
+  acc.x = fmaf(p, v.x, acc.x);
+  acc.y = fmaf(p, v.y, acc.y);
+  acc.z = fmaf(p, v.z, acc.z);
+  acc.w = fmaf(p, v.w, acc.w);
+}
 // One (work item, head) of the decode attention; the normalised output row is left in o_s[HD] (LDS, visible to
 // every thread after the call) and, unless to_lds_only, stored to out (+ the packed copy when armed).  Returns
 // false when the host contract is broken (the row is then NaN, stored and in o_s).  h is the query head; its keys
 // and values are those of kv head h / (H / KVH) (H == KVH for the AR decoder: the same head).
-template <int HD>
+// KV16: a bf16 cache.  A key row is read as 16-byte loads of 8 bf16 and a lane's 4 elements of a V row as
+// one 8-byte load, each widened to float; the sums are the fp32 form's own (dot4 / pv_add below, the same keys on the
+// same lanes in the same order), so on a cache of bf16-representable values the two forms give the same result bit
+// for bit.  dot4 / pv_add spell their multiply-adds out (dec_dot4 / dec_pv): left to the compiler, which products fuse
+// with which adds depends on how each instantiation's loads vectorise, and the two forms then differ in the last bit.
+// (16-byte V loads would halve the lanes per key and with them the key-to-lane interleave and the order of the
+// cross-lane adds: not taken.)
+template <int HD, bool KV16 = false>
 __device__ bool attn_decode_row(const AttnArgs& a, const int it, const int h, float* o_s, bool to_lds_only) {
   static_assert(HD % 4 == 0 && HD <= 128, "decode attention: head_dim");
   __shared__ float s_s[DEC_MAXK];
@@ -125,22 +159,38 @@ __device__ bool attn_decode_row(const AttnArgs& a, const int it, const int h, fl
   // one, spills a VGPR)
   constexpr int NPF = HD == 128 ? 14 : (512 / VSTR < 16 ? 512 / VSTR : 16);
   const int sub = lane / LPK, l4 = lane % LPK;
-  float4 vpf[NPF];
+  using kv_t = std::conditional_t<KV16, bf16_t, float>;
+  using v4_t = std::conditional_t<KV16, uint2, float4>;   // 4 elements of a V row as loaded
+  const kv_t* const kcp = reinterpret_cast<const kv_t*>(a.kc);
+  const kv_t* const vcp = reinterpret_cast<const kv_t*>(a.vc);
+  auto widen = [](v4_t v) {
+    if constexpr (KV16) return bf4_to_f4(v);
+    else return v;
+  };
+  v4_t vpf[NPF];
 #pragma unroll
   for (int i = 0; i < NPF; ++i) {
     const int j = wave * KPW + sub + i * VSTR;
     if (j < L)
-      vpf[i] = *reinterpret_cast<const float4*>(a.vc + (size_t)pg_s[j / a.PS] * page_sz + head_off +
-                                                (size_t)(j % a.PS) * HD + 4 * l4);
+      vpf[i] = *reinterpret_cast<const v4_t*>(vcp + (size_t)pg_s[j / a.PS] * page_sz + head_off +
+                                              (size_t)(j % a.PS) * HD + 4 * l4);
   }
+  auto dot4 = [&](float& s, int d, float4 k4) { s = dec_dot4(s, q_s + d, k4); };
   float mx = -INFINITY;
   for (int j = tid; j < L; j += DEC_NT) {
-    const float* kr = a.kc + (size_t)pg_s[j / a.PS] * page_sz + head_off + (size_t)(j % a.PS) * HD;
+    const kv_t* kr = kcp + (size_t)pg_s[j / a.PS] * page_sz + head_off + (size_t)(j % a.PS) * HD;
     float s = 0.f;
+    if constexpr (KV16) {
+      static_assert(HD % 8 == 0, "decode attention on a bf16 cache: head_dim");
 #pragma unroll
-    for (int d = 0; d < HD; d += 4) {
-      const float4 k4 = *reinterpret_cast<const float4*>(kr + d);
-      s += q_s[d] * k4.x + q_s[d + 1] * k4.y + q_s[d + 2] * k4.z + q_s[d + 3] * k4.w;
+      for (int d = 0; d < HD; d += 8) {
+        const uint4 k8 = *reinterpret_cast<const uint4*>(kr + d);
+        dot4(s, d, bf4_to_f4(make_uint2(k8.x, k8.y)));
+        dot4(s, d + 4, bf4_to_f4(make_uint2(k8.z, k8.w)));
+      }
+    } else {
+#pragma unroll
+      for (int d = 0; d < HD; d += 4) dot4(s, d, *reinterpret_cast<const float4*>(kr + d));
     }
     s_s[j] = s;
     mx = fmaxf(mx, s);
@@ -159,26 +209,17 @@ __device__ bool attn_decode_row(const AttnArgs& a, const int it, const int h, fl
   }
   sum = block_sum<DEC_NW>(sum, red_s);  // its barriers also publish s_s
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  auto pv_add = [&](float p, float4 v) { dec_pv(acc, p, v); };
 #pragma unroll
   for (int i = 0; i < NPF; ++i) {
     const int j = wave * KPW + sub + i * VSTR;
-    if (j < L) {
-      const float p = s_s[j];
-      acc.x += p * vpf[i].x;
-      acc.y += p * vpf[i].y;
-      acc.z += p * vpf[i].z;
-      acc.w += p * vpf[i].w;
-    }
+    if (j < L) pv_add(s_s[j], widen(vpf[i]));
   }
 #pragma unroll 8
   for (int j = wave * KPW + sub + NPF * VSTR; j < L; j += VSTR) {
     const float p = s_s[j];
-    const float4 v = *reinterpret_cast<const float4*>(a.vc + (size_t)pg_s[j / a.PS] * page_sz + head_off +
-                                                      (size_t)(j % a.PS) * HD + 4 * l4);
-    acc.x += p * v.x;
-    acc.y += p * v.y;
-    acc.z += p * v.z;
-    acc.w += p * v.w;
+    pv_add(p, widen(*reinterpret_cast<const v4_t*>(vcp + (size_t)pg_s[j / a.PS] * page_sz + head_off +
+                                                   (size_t)(j % a.PS) * HD + 4 * l4)));
   }
   // the wave's keys, lanes LPK apart (lane_xor: no LDS round trip)
   auto xadd = [&](auto off) {
@@ -208,10 +249,10 @@ __device__ bool attn_decode_row(const AttnArgs& a, const int it, const int h, fl
   return true;
 }
 
-template <int HD>
+template <int HD, bool KV16 = false>
 __global__ __launch_bounds__(DEC_NT) void k_attn_decode(AttnArgs a) {
   __shared__ float o_s[HD];
-  attn_decode_row<HD>(a, blockIdx.x, blockIdx.y, o_s, false);
+  attn_decode_row<HD, KV16>(a, blockIdx.x, blockIdx.y, o_s, false);
 }
 
 // One-token GQA steps (the Qwen2 text step: 7 query heads per kv head, one token per session) on the grid of the
@@ -230,7 +271,8 @@ __global__ __launch_bounds__(DEC_NT) void k_attn_decode(AttnArgs a) {
 // single-row body grows by ~2.4 us per 100 keys (one CU pulls a head's whole K / V), the split body by ~0.4.
 constexpr int GQA_DEC_KEYS = 448;
 static_assert(GQA_DEC_KEYS <= DEC_NT, "the single-row body scores one key per thread");
-template <int HD>
+// KV16 (a bf16 cache): both bodies' bf16 forms, 44 + 22 KB of LDS; the crossover is kept.
+template <int HD, bool KV16 = false>
 __global__ __launch_bounds__(DEC_NT) void k_attn_gqa_decode(AttnArgs a) {
   static_assert(DEC_NW == 8, "shares the 8-wave multi-row body's block");
   __shared__ float o_s[HD];
@@ -243,11 +285,11 @@ __global__ __launch_bounds__(DEC_NT) void k_attn_gqa_decode(AttnArgs a) {
       // computed inside the iteration; hoisted out of the loop it costs 54 spilled VGPRs)
       AttnArgs b = a;
       asm volatile("" : "+s"(b.PS));
-      attn_decode_row<HD>(b, it, kvh * G + g, o_s, false);
+      attn_decode_row<HD, KV16>(b, it, kvh * G + g, o_s, false);
     }
     return;
   }
-  attn_rows_body<HD, DEC_NW, 1, false>(a, it, kvh, sp);
+  attn_rows_body<HD, DEC_NW, 1, false, KV16>(a, it, kvh, sp);
 }
 
 // The AR speech decoder's attention fused with its o projection, residual add and the next RMSNorm's statistics
@@ -805,10 +847,13 @@ int fo_attention_set_opack(void* hi, void* lo, int cols, int cap_rb) {
 // + next-norm statistics (k_attn_decode_o above).  Arguments as fo_attention's decode form, plus: wo packed o weight
 // (N x H*hd), part >= T * H * N floats, tickets T zeroed ints (left zeroed), x [T][ldx] residual (updated), gnext
 // [N], yg [T][ldx], sout [T] (one statistics group per row).
-int fo_attention_o(const float* q, int T, const int* items, const int* tok_nvis, const int* block_table, int maxb,
-                   int PS, const float* kc, const float* vc, int H, int hd, float scale, const void* wo, int N,
-                   float* part, int* tickets, float* x, int ldx, const float* gnext, float* yg, float* sout,
-                   hipStream_t s) {
+int fo_attention_o_kv(const float* q, int T, const int* items, const int* tok_nvis, const int* block_table, int maxb,
+                      int PS, const void* kc, const void* vc, int H, int hd, float scale, const void* wo, int N,
+                      float* part, int* tickets, float* x, int ldx, const float* gnext, float* yg, float* sout,
+                      int kv_bytes, hipStream_t s) {
+  FO_REQUIRE(kv_bytes == 4 || kv_bytes == 2, "fo_attention_o: kv_bytes %d (4 = fp32, 2 = bf16)", kv_bytes);
+  FO_REQUIRE(kv_bytes == 4, "fo_attention_o: the attention fused with the o projection reads an fp32 cache only (no "
+                            "bf16 form of k_attn_decode_o)");
   FO_REQUIRE(T > 0 && H > 0 && hd == 64 && N > 0 && N <= 16 * AO_TILES * DEC_NW && ldx >= N,
              "fo_attention_o: T=%d H=%d hd=%d N=%d (N <= %d)", T, H, hd, N, 16 * AO_TILES * DEC_NW);
   FO_REQUIRE((long long)maxb * PS <= DEC_MAXK, "fo_attention_o: %d keys per sequence exceed %d", maxb * PS, DEC_MAXK);
@@ -820,6 +865,14 @@ int fo_attention_o(const float* q, int T, const int* items, const int* tok_nvis,
   hipLaunchKernelGGL((k_attn_decode_o<64>), dim3(grid), dim3(DEC_NT), 0, s, a, o);
   fo::count_launch(FO_L_ATTN_O);
   return fo::check_launch("fo_attention_o");
+}
+
+int fo_attention_o(const float* q, int T, const int* items, const int* tok_nvis, const int* block_table, int maxb,
+                   int PS, const float* kc, const float* vc, int H, int hd, float scale, const void* wo, int N,
+                   float* part, int* tickets, float* x, int ldx, const float* gnext, float* yg, float* sout,
+                   hipStream_t s) {
+  return fo_attention_o_kv(q, T, items, tok_nvis, block_table, maxb, PS, kc, vc, H, hd, scale, wo, N, part, tickets, x,
+                           ldx, gnext, yg, sout, 4, s);
 }
 
 int fo_attn_max_rows(int hd) { return attn_max_rows(hd); }
@@ -841,13 +894,20 @@ int fo_attn_nsplit(int max_keys, int n_items, int KVH) {
   return ns < 1 ? 1 : ns;
 }
 
+int fo_rope_kv_write_kv(const float* qkv, int ldq, int T, int H, int KVH, int hd, const int* pos, const int* slot,
+                        const float* cos_t, const float* sin_t, float* q_out, void* kc, void* vc, int PS, int kv_bytes,
+                        hipStream_t s) {
+  FO_REQUIRE(T > 0 && (hd % 2) == 0, "fo_rope_kv_write: bad shape");
+  FO_REQUIRE(kv_bytes == 4 || kv_bytes == 2, "fo_rope_kv_write: kv_bytes %d (4 = fp32, 2 = bf16)", kv_bytes);
+  hipLaunchKernelGGL(k_rope_kv_write, dim3(T), dim3(256), 0, s, qkv, ldq, T, H, KVH, hd, pos, slot, cos_t, sin_t,
+                     q_out, kc, vc, PS, kv_bytes == 2 ? 1 : 0, fo::kv_bf16_values());
+  return fo::check_launch("fo_rope_kv_write");
+}
+
 int fo_rope_kv_write(const float* qkv, int ldq, int T, int H, int KVH, int hd, const int* pos, const int* slot,
                      const float* cos_t, const float* sin_t, float* q_out, float* kc, float* vc, int PS,
                      hipStream_t s) {
-  FO_REQUIRE(T > 0 && (hd % 2) == 0, "fo_rope_kv_write: bad shape");
-  hipLaunchKernelGGL(k_rope_kv_write, dim3(T), dim3(256), 0, s, qkv, ldq, T, H, KVH, hd, pos, slot, cos_t, sin_t,
-                     q_out, kc, vc, PS);
-  return fo::check_launch("fo_rope_kv_write");
+  return fo_rope_kv_write_kv(qkv, ldq, T, H, KVH, hd, pos, slot, cos_t, sin_t, q_out, kc, vc, PS, 4, s);
 }
 
 // q [T][H*hd] -> out [T][H*hd].  items [n_items][3] (sequence, first token, tokens), or NULL for a uniform batch
@@ -860,6 +920,15 @@ int fo_attention(const float* q, int T, const int* items, int n_items, int max_r
                  const int* block_table, int maxb, int PS, const float* kc, const float* vc, int H, int KVH, int hd,
                  float scale, int nsplit, float* part_ml, float* part_o, float* out, int* tickets,
                  int keys_per_split, hipStream_t s) {
+  return fo_attention_kv(q, T, items, n_items, max_rows, tok_nvis, block_table, maxb, PS, kc, vc, H, KVH, hd, scale,
+                         nsplit, part_ml, part_o, out, tickets, keys_per_split, 4, s);
+}
+
+// fo_attention over a cache of kv_bytes-wide elements (4: fp32, 2: bf16 -- the KV16 instantiations)
+int fo_attention_kv(const float* q, int T, const int* items, int n_items, int max_rows, const int* tok_nvis,
+                    const int* block_table, int maxb, int PS, const void* kc, const void* vc, int H, int KVH, int hd,
+                    float scale, int nsplit, float* part_ml, float* part_o, float* out, int* tickets,
+                    int keys_per_split, int kv_bytes, hipStream_t s) {
   uint16_t *oph = g_oph, *opl = g_opl;   // the armed packed output is consumed by this launch whatever happens
   const int op_cols = g_op_cols, op_rb = g_op_rb;
   g_oph = g_opl = nullptr;
@@ -870,6 +939,12 @@ int fo_attention(const float* q, int T, const int* items, int n_items, int max_r
              H * hd, T);
   FO_REQUIRE(items || T % n_items == 0, "fo_attention: items NULL needs T / n_items tokens per item");
   FO_REQUIRE(hd == 32 || hd == 64 || hd == 128, "fo_attention: head_dim %d unsupported", hd);
+  FO_REQUIRE(kv_bytes == 4 || kv_bytes == 2, "fo_attention: kv_bytes %d (4 = fp32, 2 = bf16)", kv_bytes);
+  const bool kv16 = kv_bytes == 2;
+  // forms without a bf16 instantiation are refused by name, never run on the wrong element size
+  FO_REQUIRE(!kv16 || !g_attn_trc, "fo_attention: the traced launches (fo_attention_set_trace) read an fp32 cache only");
+  FO_REQUIRE(!kv16 || hd != 128 || attn_waves() == 8,
+             "fo_attention: FO_ATTN_NW=4 at head_dim 128 (k_attn_mfma<128, 4>) reads an fp32 cache only");
   // up to 32 query rows per item on the 8-wave head-dim-128 kernel (two row tiles share every K / V load: a duplex
   // tick's 4 tokens x 7 query heads per kv head read the session's keys once, not twice), 16 elsewhere
   const int rows_max = attn_max_rows(hd);
@@ -888,7 +963,10 @@ int fo_attention(const float* q, int T, const int* items, int n_items, int max_r
              "fo_attention: packed output needs <= 64 tokens and no combine launch");
   if (dec) {  // one query row per (session, head): decode kernel
     dim3 g1(n_items, H);
-    if (hd == 128) hipLaunchKernelGGL((k_attn_decode<128>), g1, dim3(DEC_NT), 0, s, a);
+    if (kv16 && hd == 128) hipLaunchKernelGGL((k_attn_decode<128, true>), g1, dim3(DEC_NT), 0, s, a);
+    else if (kv16 && hd == 64) hipLaunchKernelGGL((k_attn_decode<64, true>), g1, dim3(DEC_NT), 0, s, a);
+    else if (kv16) hipLaunchKernelGGL((k_attn_decode<32, true>), g1, dim3(DEC_NT), 0, s, a);
+    else if (hd == 128) hipLaunchKernelGGL((k_attn_decode<128>), g1, dim3(DEC_NT), 0, s, a);
     else if (hd == 64) hipLaunchKernelGGL((k_attn_decode<64>), g1, dim3(DEC_NT), 0, s, a);
     else hipLaunchKernelGGL((k_attn_decode<32>), g1, dim3(DEC_NT), 0, s, a);
     fo::count_launch(FO_L_ATTN_DECODE);
@@ -903,7 +981,8 @@ int fo_attention(const float* q, int T, const int* items, int n_items, int max_r
   const bool gqa_dec = hd == 128 && KVH < H && G <= 8 && max_rows == G && (items || T == n_items) &&
                        (tickets || nsplit == 1) && attn_waves() == 8 && !a.trc;
   if (gqa_dec) {
-    hipLaunchKernelGGL((k_attn_gqa_decode<128>), grid, dim3(DEC_NT), 0, s, a);
+    if (kv16) hipLaunchKernelGGL((k_attn_gqa_decode<128, true>), grid, dim3(DEC_NT), 0, s, a);
+    else hipLaunchKernelGGL((k_attn_gqa_decode<128>), grid, dim3(DEC_NT), 0, s, a);
     fo::count_launch(FO_L_ATTN_GQA_DECODE);
     if (a.oph) fo::count_launch(FO_L_ATTN_OPACK);
     return fo::check_launch("fo_attention/gqa_decode");
@@ -911,7 +990,14 @@ int fo_attention(const float* q, int T, const int* items, int n_items, int max_r
   // splits under 64 keys (the text step's short contexts spread over more CUs: a split's K / V arrive at one CU's
   // memory parallelism) take the 2-wave form with 32-key tiles
   const bool small = hd == 128 && tickets && keys_per_split < 64 && max_rows <= 16 && !a.trc;
-  if (small) hipLaunchKernelGGL((k_attn_mfma<128, 2>), grid, dim3(128), 0, s, a);
+  FO_REQUIRE(!kv16 || !small, "fo_attention: keys_per_split %d takes the 2-wave form (k_attn_mfma<128, 2>), which reads "
+                              "an fp32 cache only; a bf16 cache needs >= 64", keys_per_split);
+  if (kv16) {
+    if (hd == 128 && max_rows > 16) hipLaunchKernelGGL((k_attn_mfma<128, 8, 2, false, true>), grid, dim3(512), 0, s, a);
+    else if (hd == 128) hipLaunchKernelGGL((k_attn_mfma<128, 8, 1, false, true>), grid, dim3(512), 0, s, a);
+    else if (hd == 64) hipLaunchKernelGGL((k_attn_mfma<64, 4, 1, false, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_attn_mfma<32, 4, 1, false, true>), grid, dim3(256), 0, s, a);
+  } else if (small) hipLaunchKernelGGL((k_attn_mfma<128, 2>), grid, dim3(128), 0, s, a);
   else if (hd == 128 && attn_waves() == 8 && max_rows > 16) hipLaunchKernelGGL((k_attn_mfma<128, 8, 2>), grid, dim3(512), 0, s, a);
   else if (hd == 128 && attn_waves() == 8 && a.trc) hipLaunchKernelGGL((k_attn_mfma<128, 8, 1, true>), grid, dim3(512), 0, s, a);
   else if (hd == 128 && attn_waves() == 8) hipLaunchKernelGGL((k_attn_mfma<128, 8>), grid, dim3(512), 0, s, a);

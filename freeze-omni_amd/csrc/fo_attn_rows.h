@@ -8,8 +8,8 @@ struct AttnArgs {
   const int* items;        // [n_items][3]: sequence, first token, token count (a sequence's tokens are contiguous)
   const int* tok_nvis;     // keys visible to each query token (causal: own cache index + 1; full: all)
   const int* block_table;  // [S][maxb]
-  const float* kc;
-  const float* vc;
+  const void* kc;         // paged K / V, [page][kv head][slot][hd]: fp32, or bf16 (the KV16 instantiations)
+  const void* vc;
   float* part_ml;  // [T*H][nsplit][2]   (nsplit > 1)
   float* part_o;   // [T*H][nsplit][hd]  (nsplit > 1)
   float* out;      // [T][H*hd]
@@ -196,17 +196,30 @@ __device__ void attn_arrive_and_merge(const AttnArgs& a, int it, int kvh, int ns
 // softmax per row with the running max exchanged across the 4 waves through LDS.
 // RT: 16-row query tiles per item (2: up to 32 rows share the K / V loads); TR: the probe build with per-workgroup
 // clocks (a.trc) -- a compile-time switch: the runtime-null hook cost the product launches ~6 % (r05zz vs r05m)
-template <int HD, int NW, int RT = 1, bool TR = false>
+// KV16: the cache holds bf16 elements.  A lane's K slice of a d chunk is then one 16-byte load that is the
+// MFMA B fragment as it stands, V is staged to LDS as bf16 (half the tile) and read back as 16-bit elements, and each
+// product is two MFMAs, q_hi k + q_lo k and p_hi v + p_lo v: the fp32 form's three with the one against the (zero) low
+// half of k / v dropped, in the same order -- on a cache of bf16-representable values the two forms give the same
+// result bit for bit.  Everything else (tiles, ping-pong, softmax, splits, merge) is shared.
+template <int HD, int NW, int RT = 1, bool TR = false, bool KV16 = false>
 __device__ __forceinline__ void attn_rows_body(const AttnArgs& a, const int it, const int kvh, const int sp) {
+  static_assert(!(KV16 && TR), "the probe build reads an fp32 cache");
   constexpr int KT = 16 * NW;           // keys per tile: one 16-key column block per wave
   constexpr int NTH = NW * 64;
   constexpr int DC = HD / 32;            // 32-wide d chunks (score k-steps)
   constexpr int NTILE = HD / 16;         // 16-wide d tiles of the output
   constexpr int NTW = (NTILE + NW - 1) / NW;   // output tiles per wave
-  constexpr int VP = HD + 2;             // V row pitch: the 4 key groups of a B fragment hit distinct banks
-  constexpr int VL = KT * HD / 4 / NTH;  // float4 of V per thread per tile
+  // V row pitch: the 4 key groups of a B fragment hit distinct banks.  bf16: HD + 4 elements, rows 8-byte aligned for
+  // the staging stores; the fragment's 16-bit reads bank by dword mod 32 within a 32-lane half (two key groups x 16
+  // columns): the 16 columns of a group share 8 dwords, and the groups, 8 rows = 4 HD + 16 dwords apart, sit 16 banks
+  // apart (HD a multiple of 8) -- conflict-free
+  constexpr int VP = KV16 ? HD + 4 : HD + 2;
+  constexpr int VL = KT * HD / (KV16 ? 8 : 4) / NTH;  // 16-B pieces of V per thread per tile
+  constexpr int KN = KV16 ? DC : 2 * DC;              // 16-B pieces of a key's row per lane
   constexpr bool SC = NW == 8;           // one workgroup per CU: the fence-free split hand-off (attn_arrive_and_merge)
-  __shared__ float v_s[KT][VP];
+  using kv_t = std::conditional_t<KV16, bf16_t, float>;
+  using kv16B = std::conditional_t<KV16, uint4, float4>;   // 16 bytes of the cache: 8 bf16 or 4 floats
+  __shared__ kv_t v_s[KT][VP];
   // (at least 64 + 4 wide: attn_arrive_and_merge reuses it as its [16][64 + 4] weight table)
   __shared__ float p_s[16 * RT][(KT > 64 ? KT : 64) + 4];
   __shared__ float mx_s[NW][16 * RT];
@@ -335,22 +348,29 @@ __device__ __forceinline__ void attn_rows_body(const AttnArgs& a, const int it, 
 
   const size_t head_off = (size_t)kvh * a.PS * HD;
   const size_t page_sz = (size_t)a.KVH * a.PS * HD;
-  float4 kA[2 * DC], vA[VL], kB[2 * DC], vB[VL];   // two tiles' K / V in flight (ping-pong)
+  const kv_t* const kcp = reinterpret_cast<const kv_t*>(a.kc);
+  const kv_t* const vcp = reinterpret_cast<const kv_t*>(a.vc);
+  constexpr int VE = KV16 ? 8 : 4;                 // V elements per 16-B piece
+  kv16B kA[KN], vA[VL], kB[KN], vB[VL];            // two tiles' K / V in flight (ping-pong)
   // K: this lane's key (16 per wave) x its 8-wide d slices; V: cooperative 16-B rows for LDS
 #define FO_ATTN_LOAD(kreg, vreg, K0)                                                                      \
   {                                                                                                       \
     const int pk = min((K0) + 16 * wave + col, c1 - 1);                                                   \
-    const float* kr = a.kc + (size_t)pg_s[pk / a.PS - pb] * page_sz + head_off + (size_t)(pk % a.PS) * HD \
-                      + 8 * grp;                                                                          \
+    const kv_t* kr = kcp + (size_t)pg_s[pk / a.PS - pb] * page_sz + head_off + (size_t)(pk % a.PS) * HD   \
+                     + 8 * grp;                                                                           \
     _Pragma("unroll") for (int c = 0; c < DC; ++c) {                                                      \
-      kreg[2 * c] = *reinterpret_cast<const float4*>(kr + 32 * c);                                        \
-      kreg[2 * c + 1] = *reinterpret_cast<const float4*>(kr + 32 * c + 4);                                \
+      if constexpr (KV16) {                                                                               \
+        kreg[c] = *reinterpret_cast<const kv16B*>(kr + 32 * c);                                           \
+      } else {                                                                                            \
+        kreg[2 * c] = *reinterpret_cast<const kv16B*>(kr + 32 * c);                                       \
+        kreg[2 * c + 1] = *reinterpret_cast<const kv16B*>(kr + 32 * c + 4);                               \
+      }                                                                                                   \
     }                                                                                                     \
     _Pragma("unroll") for (int i = 0; i < VL; ++i) {                                                      \
-      const int e = tid + NTH * i, j = e / (HD / 4), d4 = e % (HD / 4);                                   \
+      const int e = tid + NTH * i, j = e / (HD / VE), dv = e % (HD / VE);                                 \
       const int pv = min((K0) + j, c1 - 1);                                                               \
-      vreg[i] = *reinterpret_cast<const float4*>(a.vc + (size_t)pg_s[pv / a.PS - pb] * page_sz + head_off \
-                                                 + (size_t)(pv % a.PS) * HD + d4 * 4);                    \
+      vreg[i] = *reinterpret_cast<const kv16B*>(vcp + (size_t)pg_s[pv / a.PS - pb] * page_sz + head_off   \
+                                                + (size_t)(pv % a.PS) * HD + dv * VE);                    \
     }                                                                                                     \
   }
 
@@ -372,20 +392,29 @@ __device__ __forceinline__ void attn_rows_body(const AttnArgs& a, const int it, 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (tr && tid == 0) tr[6] = wall_clock64();
   }
-  auto tile = [&](float4 (&kreg)[2 * DC], float4 (&vreg)[VL], const int k0) {
+  auto tile = [&](kv16B (&kreg)[KN], kv16B (&vreg)[VL], const int k0) {
     __syncthreads();  // the previous tile's p_s / v_s readers are done
 #pragma unroll
     for (int i = 0; i < VL; ++i) {
-      const int e = tid + NTH * i, j = e / (HD / 4), d4 = e % (HD / 4);
-      *reinterpret_cast<float2*>(&v_s[j][d4 * 4]) = make_float2(vreg[i].x, vreg[i].y);
-      *reinterpret_cast<float2*>(&v_s[j][d4 * 4 + 2]) = make_float2(vreg[i].z, vreg[i].w);
+      const int e = tid + NTH * i, j = e / (HD / VE), dv = e % (HD / VE);
+      if constexpr (KV16) {
+        *reinterpret_cast<uint2*>(&v_s[j][dv * 8]) = make_uint2(vreg[i].x, vreg[i].y);
+        *reinterpret_cast<uint2*>(&v_s[j][dv * 8 + 4]) = make_uint2(vreg[i].z, vreg[i].w);
+      } else {
+        *reinterpret_cast<float2*>(&v_s[j][dv * 4]) = make_float2(vreg[i].x, vreg[i].y);
+        *reinterpret_cast<float2*>(&v_s[j][dv * 4 + 2]) = make_float2(vreg[i].z, vreg[i].w);
+      }
     }
-    bf16x8 kh[DC], kl[DC];
+    bf16x8 kh[DC], kl[KV16 ? 1 : DC];   // (bf16: the loaded 16 bytes are the fragment; no low half)
 #pragma unroll
     for (int c = 0; c < DC; ++c) {
-      const float f[8] = {kreg[2 * c].x, kreg[2 * c].y, kreg[2 * c].z, kreg[2 * c].w,
-                          kreg[2 * c + 1].x, kreg[2 * c + 1].y, kreg[2 * c + 1].z, kreg[2 * c + 1].w};
-      split8(f, kh[c], kl[c]);
+      if constexpr (KV16) {
+        kh[c] = __builtin_bit_cast(bf16x8, kreg[c]);
+      } else {
+        const float f[8] = {kreg[2 * c].x, kreg[2 * c].y, kreg[2 * c].z, kreg[2 * c].w,
+                            kreg[2 * c + 1].x, kreg[2 * c + 1].y, kreg[2 * c + 1].z, kreg[2 * c + 1].w};
+        split8(f, kh[c], kl[c]);
+      }
     }
     if (tr && tid == 0 && k0 == c0) tr[7] = wall_clock64();
     if (k0 + 2 * KT < c1) FO_ATTN_LOAD(kreg, vreg, k0 + 2 * KT)
@@ -399,7 +428,7 @@ __device__ __forceinline__ void attn_rows_body(const AttnArgs& a, const int it, 
         const bf16x8 qhv = QL ? qf_s[QL ? rt : 0][QL ? c : 0][0][lane] : qh[QL ? 0 : rt][c];
         const bf16x8 qlv = QL ? qf_s[QL ? rt : 0][QL ? c : 0][1][lane] : ql[QL ? 0 : rt][c];
         s[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qhv, kh[c], s[rt], 0, 0, 0);
-        s[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qhv, kl[c], s[rt], 0, 0, 0);
+        if constexpr (!KV16) s[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qhv, kl[c], s[rt], 0, 0, 0);
         s[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qlv, kh[c], s[rt], 0, 0, 0);
       }
     }
@@ -462,15 +491,20 @@ __device__ __forceinline__ void attn_rows_body(const AttnArgs& a, const int it, 
       for (int n = 0; n < NTW; ++n) {
         const int dt = wave + NW * n;
         if (dt < NTILE) {
-          float f[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) f[e] = v_s[32 * kc + 8 * grp + e][16 * dt + col];
           bf16x8 vh, vl;
-          split8(f, vh, vl);
+          if constexpr (KV16) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) vh[e] = __builtin_bit_cast(__bf16, v_s[32 * kc + 8 * grp + e][16 * dt + col]);
+          } else {
+            float f[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f[e] = v_s[32 * kc + 8 * grp + e][16 * dt + col];
+            split8(f, vh, vl);
+          }
 #pragma unroll
           for (int rt = 0; rt < RT; ++rt) {
             acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph[rt], vh, acc[rt][n], 0, 0, 0);
-            acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph[rt], vl, acc[rt][n], 0, 0, 0);
+            if constexpr (!KV16) acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph[rt], vl, acc[rt][n], 0, 0, 0);
             acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pl[rt], vh, acc[rt][n], 0, 0, 0);
           }
         }

@@ -43,6 +43,8 @@ int check_launch(const char* what);
 // which kernel family a shape was routed to.  Counted when the launch is issued (a captured graph counts once,
 // at capture).
 void count_launch(int kind);
+// the fo_set_kv_bf16 / FO_KV_BF16 switch (fo_gemm.hip): K / V appended to an fp32 cache are rounded to bf16 values
+int kv_bf16_values();
 }  // namespace fo
 
 #define FO_REQUIRE(cond, ...)            \

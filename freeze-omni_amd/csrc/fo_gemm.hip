@@ -56,10 +56,11 @@ struct GemmArgs {
   const float* rcos;  // [pos][hd/2]
   const float* rsin;
   float* rq;
-  float* rk;
-  float* rv;
+  void* rk;   // the paged cache: fp32, or bf16 elements (rkv16)
+  void* rv;
   int rH, rKVH, rhd, rPS;
   int rkvb;   // K / V rounded to bf16 as they are appended (fo_set_kv_bf16: the reference's autocast k_proj / v_proj A/B)
+  int rkv16;  // the cache holds bf16: K / V stored as f2bf(x), 2-byte elements in the same page layout
   // LayerNorm on load (the pre-norm of a speech-encoder block, models/encoder/transformer.py:103-130):
   // X rows are normalised ((x - mean) * rstd * lnw + lnb) as they are loaded, before the bf16 hi/lo
   // split; mean and variance come from the producer GEMM's per-row partial sums of Y and Y^2
@@ -130,6 +131,19 @@ __device__ __forceinline__ float epilogue_store(const GemmArgs& a, bool sw, int 
   return v;
 }
 
+// Elements o and o + half of the paged cache `base`: f2bf(x) as 2-byte elements of a bf16 cache, else fp32 (the bf16
+// value under fo_set_kv_bf16 -- what the bf16 cache holds, widened).
+__device__ __forceinline__ void kv_store(const GemmArgs& a, void* base, size_t o, int half, float x1, float x2) {
+  if (a.rkv16) {
+    bf16_t* d = reinterpret_cast<bf16_t*>(base) + o;
+    d[0] = f2bf(x1);
+    d[half] = f2bf(x2);
+  } else {
+    float* d = reinterpret_cast<float*>(base) + o;
+    d[0] = a.rkvb ? bf2f(f2bf(x1)) : x1;
+    d[half] = a.rkvb ? bf2f(f2bf(x2)) : x2;
+  }
+}
 // Columns (n, n + hd/2) of one head, n < hd/2 within the head (transformers rotate_half RoPE, the
 // reference's Qwen2 / Llama attention reached from models/audioLLM.py:482, models/decoder/decoder.py:299-311).
 __device__ __forceinline__ void rope_store(const GemmArgs& a, int m, int n, float x1, float x2) {
@@ -145,18 +159,15 @@ __device__ __forceinline__ void rope_store(const GemmArgs& a, int m, int n, floa
     const int p = a.rpos[m];
     const float c = a.rcos[(size_t)p * half + i], sn = a.rsin[(size_t)p * half + i];
     float o1 = x1 * c - x2 * sn, o2 = x2 * c + x1 * sn;
-    if (a.rkvb && h >= a.rH) {
-      o1 = bf2f(f2bf(o1));
-      o2 = bf2f(f2bf(o2));
+    if (h < a.rH) {
+      float* d = a.rq + (size_t)m * a.rH * hd + (size_t)h * hd;
+      d[i] = o1;
+      d[i + half] = o2;
+    } else {
+      kv_store(a, a.rk, (((size_t)page * a.rKVH + (h - a.rH)) * a.rPS + off) * hd + i, half, o1, o2);
     }
-    float* d = h < a.rH ? a.rq + (size_t)m * a.rH * hd + (size_t)h * hd
-                        : a.rk + (((size_t)page * a.rKVH + (h - a.rH)) * a.rPS + off) * hd;
-    d[i] = o1;
-    d[i + half] = o2;
   } else {
-    float* d = a.rv + (((size_t)page * a.rKVH + (h - a.rH - a.rKVH)) * a.rPS + off) * hd;
-    d[i] = a.rkvb ? bf2f(f2bf(x1)) : x1;
-    d[i + half] = a.rkvb ? bf2f(f2bf(x2)) : x2;
+    kv_store(a, a.rv, (((size_t)page * a.rKVH + (h - a.rH - a.rKVH)) * a.rPS + off) * hd + i, half, x1, x2);
   }
 }
 // rope_store with the bias already added and the slot / cos / sin loaded ahead (gemm_body EPRE)
@@ -165,22 +176,20 @@ __device__ __forceinline__ void rope_store_pre(const GemmArgs& a, int m, int n, 
   const int hd = a.rhd, half = hd >> 1;
   const int h = n / hd, i = n - h * hd;
   const int page = sl / a.rPS, off = sl - page * a.rPS;
-  float* d;
   if (h < a.rH + a.rKVH) {
     const float o1 = x1 * c - x2 * sn, o2 = x2 * c + x1 * sn;
     x1 = o1;
     x2 = o2;
-    d = h < a.rH ? a.rq + (size_t)m * a.rH * hd + (size_t)h * hd
-                 : a.rk + (((size_t)page * a.rKVH + (h - a.rH)) * a.rPS + off) * hd;
+  }
+  if (h < a.rH) {
+    float* d = a.rq + (size_t)m * a.rH * hd + (size_t)h * hd;
+    d[i] = x1;
+    d[i + half] = x2;
+  } else if (h < a.rH + a.rKVH) {
+    kv_store(a, a.rk, (((size_t)page * a.rKVH + (h - a.rH)) * a.rPS + off) * hd + i, half, x1, x2);
   } else {
-    d = a.rv + (((size_t)page * a.rKVH + (h - a.rH - a.rKVH)) * a.rPS + off) * hd;
+    kv_store(a, a.rv, (((size_t)page * a.rKVH + (h - a.rH - a.rKVH)) * a.rPS + off) * hd + i, half, x1, x2);
   }
-  if (a.rkvb && h >= a.rH) {
-    x1 = bf2f(f2bf(x1));
-    x2 = bf2f(f2bf(x2));
-  }
-  d[i] = x1;
-  d[i + half] = x2;
 }
 // logical first column of rope tile pair P, column c
 __device__ __forceinline__ int rope_col(const GemmArgs& a, int P, int c) {
@@ -1663,6 +1672,7 @@ GemmArgs fill_args(const GemmCall& c, const Packs& pk, const WeightDesc& w) {
     a.rhd = c.rope->rhd;
     a.rPS = c.rope->rPS;
     a.rkvb = g_kv_bf16;
+    a.rkv16 = c.rope->rkv16;
   }
   a.lnw = c.lnw;
   a.lnb = c.lnb;
@@ -2209,8 +2219,18 @@ int fo_gemm_qkv_rope(const void* X, int x_f32, int ldx, int M, int K, const void
                      float* ws, long long ws_floats, int* counters, int splitk, const float* rstats, int rgroups,
                      float eps, const int* pos, const int* slot, const float* cos_t, const float* sin_t, float* q_out,
                      float* kc, float* vc, int H, int KVH, int hd, int PS, hipStream_t stream) {
+  return fo_gemm_qkv_rope_kv(X, x_f32, ldx, M, K, Wp, N, bias, ws, ws_floats, counters, splitk, rstats, rgroups, eps, pos,
+                             slot, cos_t, sin_t, q_out, kc, vc, H, KVH, hd, PS, 4, stream);
+}
+
+int fo_gemm_qkv_rope_kv(const void* X, int x_f32, int ldx, int M, int K, const void* Wp, int N, const float* bias,
+                        float* ws, long long ws_floats, int* counters, int splitk, const float* rstats, int rgroups,
+                        float eps, const int* pos, const int* slot, const float* cos_t, const float* sin_t,
+                        float* q_out, void* kc, void* vc, int H, int KVH, int hd, int PS, int kv_bytes,
+                        hipStream_t stream) {
   FO_REQUIRE(pos && slot && cos_t && sin_t && q_out && kc && vc && PS > 0 && H > 0 && KVH > 0,
              "fo_gemm_qkv_rope: missing rope/cache arguments");
+  FO_REQUIRE(kv_bytes == 4 || kv_bytes == 2, "fo_gemm_qkv_rope: kv_bytes %d (4 = fp32, 2 = bf16)", kv_bytes);
   GemmArgs r{};
   r.rpos = pos;
   r.rslot = slot;
@@ -2223,6 +2243,7 @@ int fo_gemm_qkv_rope(const void* X, int x_f32, int ldx, int M, int K, const void
   r.rKVH = KVH;
   r.rhd = hd;
   r.rPS = PS;
+  r.rkv16 = kv_bytes == 2;
   GemmCall c;
   c.X = X, c.x_f32 = x_f32, c.ldx = ldx, c.M = M, c.K = K;
   c.Wp = Wp, c.N = N;
@@ -2244,6 +2265,10 @@ int fo_gemm_set_pipe(int on) {
   g_pipe = on;
   return prev;
 }
+
+}  // extern "C"
+int fo::kv_bf16_values() { return g_kv_bf16; }
+extern "C" {
 
 int fo_set_kv_bf16(int on) {
   FO_REQUIRE(on == 0 || on == 1, "fo_set_kv_bf16: 0 or 1");

@@ -69,8 +69,12 @@ def make_source(cfg, synth, device, model_path=None, llm_path=None, receive=Fals
 class FreezeOmniEngine:
     def __init__(self, model_path, llm_path=None, device="cuda:0", max_sessions=64, llm_kv_tokens=None,
                  tts_kv_tokens=None, source=None, receive_weights=False, train_yaml=None, mlp_weights="bf16",
-                 mlp_fp8_rows=16):
-        """mlp_weights: "bf16" (default) or "fp8": the Qwen2 gate/up/down weights under weight-only FP8 (e4m3fn codes
+                 mlp_fp8_rows=16, llm_kv="fp32"):
+        """llm_kv: "fp32" (default) or "bf16": the element of the Qwen2 stack's paged KV.  "bf16" is the
+        cache the reference keeps: K after bias and RoPE and V after bias are rounded once to bf16 as they are
+        appended, stored as 2-byte elements and read as such by the attention; llm_kv_tokens keeps meaning tokens,
+        so the pool is half the bytes.  The speech decoder's pool, the encoder rings and the adapter caches stay fp32.
+        mlp_weights: "bf16" (default) or "fp8": the Qwen2 gate/up/down weights under weight-only FP8 (e4m3fn codes
         times a power of two per output row, DESIGN: `mlp_weights`); Qwen2 steps of <= 16 rows then stream the codes.
         `src` serves the dequantised weights (fo.weights.FakeQuantSource), so an oracle or a second engine can be
         built on the same model.
@@ -90,8 +94,11 @@ class FreezeOmniEngine:
             raise ValueError(f"mlp_fp8_rows must be 16 or 64, got {mlp_fp8_rows!r}")
         if mlp_fp8_rows == 64 and mlp_weights != "fp8":
             raise ValueError("mlp_fp8_rows=64 needs mlp_weights='fp8'")
+        if llm_kv not in ("fp32", "bf16"):
+            raise ValueError(f"llm_kv must be 'fp32' or 'bf16', got {llm_kv!r}")
         self.mlp_weights = mlp_weights
         self.mlp_fp8_rows = mlp_fp8_rows
+        self.llm_kv = llm_kv
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         self.cfg, self.synth, self.llm_path = load_model_dir(model_path, llm_path)
@@ -119,7 +126,7 @@ class FreezeOmniEngine:
         V = self.cfg["llm"]["vocab_size"]
         self.llm = LLMEngine(src, self.cfg["llm"], self.device,
                              kv_tokens=llm_kv_tokens or min(max_sessions * 4096, 1 << 17),
-                             mlp_w8=mlp_weights == "fp8", mlp_w8_rows=mlp_fp8_rows)
+                             mlp_w8=mlp_weights == "fp8", mlp_w8_rows=mlp_fp8_rows, kv_dtype=llm_kv)
         self.tts = TTSEngine(src, self.cfg["decoder_json"], self.device,
                              kv_tokens=tts_kv_tokens or min(max_sessions * 2048, 1 << 17))
         self.codec = CodecEngine(src, self.cfg["codec_json"], self.device)
@@ -165,7 +172,8 @@ class FreezeOmniEngine:
             self.llm = None   # release the old weights and pool first (15 GB at Qwen2-7B size)
             torch.cuda.empty_cache()
             self.llm = LLMEngine(src, self.cfg["llm"], self.device, kv_tokens=kv_tokens,
-                                 mlp_w8=self.mlp_weights == "fp8", mlp_w8_rows=self.mlp_fp8_rows)
+                                 mlp_w8=self.mlp_weights == "fp8", mlp_w8_rows=self.mlp_fp8_rows,
+                                 kv_dtype=self.llm_kv)
         elif "predictor_head.weight" in src:
             self.llm.head_w, self.llm.head_b = src.get("predictor_head.weight"), src.get("predictor_head.bias")
         self.src = FakeQuantSource(src) if fq else src

@@ -3,7 +3,8 @@
 The reference keeps one transformers DynamicCache per session and grows it with torch.cat on every
 chunk (models/audioLLM.py:416-419, models/decoder/decoder.py:321); sessions deep-copy the system
 prompt cache (bin/dialog_state_pred.py:110,218).  Here every layer's K/V live in one device pool of
-fixed-size pages ([layer][page][kv_head][slot][hd], fp32).  A sequence is a block list; `fork()`
+fixed-size pages ([layer][page][kv_head][slot][hd]; fp32, or bf16 for the Qwen2 stack's opt-in
+`llm_kv="bf16"`: the same layout in 2-byte elements).  A sequence is a block list; `fork()`
 shares full pages copy-on-write (refcounts), so N sessions forked from one system prompt store it
 once, and appending never moves existing keys.
 """
@@ -17,10 +18,15 @@ from . import ops
 
 
 class KVPool:
-    def __init__(self, n_layers, n_kv, hd, n_pages, page_size, device):
+    def __init__(self, n_layers, n_kv, hd, n_pages, page_size, device, dtype=torch.float32):
+        """dtype: torch.float32 (default) or torch.bfloat16 -- the element the append kernels store and the attention
+        kernels read (they take the layout from these tensors, ops.kv_bytes)."""
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"KVPool dtype must be torch.float32 or torch.bfloat16, got {dtype}")
         self.n_layers, self.n_kv, self.hd, self.PS = n_layers, n_kv, hd, page_size
         self.n_pages = n_pages
-        self.k = torch.empty(n_layers, n_pages, n_kv, page_size, hd, dtype=torch.float32, device=device)
+        self.dtype = dtype
+        self.k = torch.empty(n_layers, n_pages, n_kv, page_size, hd, dtype=dtype, device=device)
         self.v = torch.empty_like(self.k)
         self.ref = np.zeros(n_pages, dtype=np.int32)
         self.free = list(range(n_pages - 1, -1, -1))
@@ -31,7 +37,7 @@ class KVPool:
 
     @property
     def bytes_per_token(self):
-        return self.n_layers * self.n_kv * self.hd * 4 * 2
+        return self.n_layers * self.n_kv * self.hd * self.k.element_size() * 2
 
     def alloc(self):
         with self.lock:

@@ -14,7 +14,12 @@ from .stack import DecoderStack
 
 class LLMEngine:
     def __init__(self, src, llm_cfg, device, head_src=None, kv_tokens=65536, page_size=16, max_pos=None,
-                 mlp_w8=False, mlp_w8_rows=16):
+                 mlp_w8=False, mlp_w8_rows=16, kv_dtype="fp32"):
+        """kv_dtype: "fp32" (default) or "bf16" -- the paged KV's element: K / V rounded once to bf16
+        as they are appended and read as bf16 by the attention; kv_tokens keeps meaning tokens (half the bytes)."""
+        if kv_dtype not in ("fp32", "bf16"):
+            raise ValueError(f'kv_dtype must be "fp32" or "bf16", got {kv_dtype!r}')
+        self.kv_dtype = kv_dtype
         c = llm_cfg
         self.device = torch.device(device)
         self.D, self.V = c["hidden_size"], c["vocab_size"]
@@ -25,7 +30,8 @@ class LLMEngine:
         cos, sin = tables.rope_tables(c["rope_theta"], self.hd, max_pos, round_fp16=True)
         self.rope = (cos.to(self.device), sin.to(self.device))
         n_pages = (kv_tokens + page_size - 1) // page_size
-        self.pool = KVPool(c["num_hidden_layers"], self.KVH, self.hd, n_pages, page_size, self.device)
+        self.pool = KVPool(c["num_hidden_layers"], self.KVH, self.hd, n_pages, page_size, self.device,
+                           dtype=torch.bfloat16 if kv_dtype == "bf16" else torch.float32)
         self.stack = DecoderStack(src, "model.layers.", c["num_hidden_layers"], self.D, self.H, self.KVH, self.eps,
                                   True, self.rope, self.pool, first_fp16=True, mlp_w8=mlp_w8,
                                   mlp_w8_rows=mlp_w8_rows)

@@ -277,12 +277,13 @@ class PackedLinear:
         rst, rg, eps = (None, 0, 0.0) if norm is None else (norm[0].buf.data_ptr(), norm[0].groups, float(norm[1]))
         if norm is not None and rg <= 0:
             raise RuntimeError("RowStats consumed before any GEMM produced them")
+        kvb = kv_bytes(kc, vc)
         with _packed(xpack, None):
-            _lib.call("fo_gemm_qkv_rope", x.data_ptr(), 1 if x.dtype == F32 else 0, x.stride(0), M, self.Kp,
+            _lib.call("fo_gemm_qkv_rope_kv", x.data_ptr(), 1 if x.dtype == F32 else 0, x.stride(0), M, self.Kp,
                       self.packed.data_ptr(), self.N, ptr(self.bias), rt.ws.data_ptr(), rt.ws.numel(),
                       rt.counters.data_ptr(), splitk, rst, rg, eps, pos.data_ptr(), slot.data_ptr(), cos_t.data_ptr(),
                       sin_t.data_ptr(), q_out.data_ptr(), kc.data_ptr(), vc.data_ptr(), H, KVH, self.rope_hd, PS,
-                      stream(x.device))
+                      kvb, stream(x.device))
         return q_out
 
     def _call_norm(self, x, out, act, residual, out_dtype, splitk, M, norm, stats_out, xpack=None, ypack=None):
@@ -708,10 +709,18 @@ def attn_nsplit(max_keys, n_items, KVH):
     return _lib.load().fo_attn_nsplit(int(max_keys), int(n_items), int(KVH))
 
 
+def kv_bytes(kc, vc):
+    """Element width of one layer's paged K / V (the *_kv entries' kv_bytes): 4 for an fp32 pool, 2 for a bf16 one
+    (KVPool(dtype=torch.bfloat16)).  The launch takes its layout from the tensors it is given."""
+    if kc.dtype != vc.dtype or kc.dtype not in (F32, BF16):
+        raise ValueError(f"paged K / V must both be fp32 or both bf16, got {kc.dtype} / {vc.dtype}")
+    return 4 if kc.dtype == F32 else 2
+
+
 def rope_kv_write(qkv, T, H, KVH, hd, pos, slot, cos_t, sin_t, q_out, kc, vc, PS):
-    _lib.call("fo_rope_kv_write", qkv.data_ptr(), qkv.stride(0), T, H, KVH, hd, pos.data_ptr(), slot.data_ptr(),
+    _lib.call("fo_rope_kv_write_kv", qkv.data_ptr(), qkv.stride(0), T, H, KVH, hd, pos.data_ptr(), slot.data_ptr(),
               cos_t.data_ptr(), sin_t.data_ptr(), q_out.data_ptr(), kc.data_ptr(), vc.data_ptr(), PS,
-              stream(qkv.device))
+              kv_bytes(kc, vc), stream(qkv.device))
 
 
 # keys per split of the multi-row attention: 0 (default) = attn_keys_per_split() per launch; FO_ATTN_KPS fixes it
@@ -753,13 +762,14 @@ def attention(q, T, items, n_items, max_rows, tok_nvis, block_table, PS, kc, vc,
         raise ValueError("attention: items=None needs T / n_items tokens per sequence")
     if tickets is not None and tickets.numel() < n_items * KVH:
         raise ValueError("attention tickets buffer smaller than n_items * KVH")
+    kvb = kv_bytes(kc, vc)
     if opack is not None:
         _lib.call("fo_attention_set_opack", opack.hi.data_ptr(), opack.lo.data_ptr(), opack.K, opack.rb)
     try:
-        _lib.call("fo_attention", q.data_ptr(), T, ptr(items), n_items, max_rows, tok_nvis.data_ptr(),
+        _lib.call("fo_attention_kv", q.data_ptr(), T, ptr(items), n_items, max_rows, tok_nvis.data_ptr(),
                   block_table.data_ptr(), block_table.shape[1], PS, kc.data_ptr(), vc.data_ptr(), H, KVH, hd,
                   float(scale), nsplit, ptr(part_ml), ptr(part_o), out.data_ptr(), ptr(tickets), int(keys_per_split),
-                  stream(q.device))
+                  kvb, stream(q.device))
     except Exception:
         if opack is not None:   # the launch did not consume it: never leave it for the next one
             _lib.call("fo_attention_set_opack", None, None, 0, 0)
@@ -772,10 +782,10 @@ def attention_o(q, T, items, tok_nvis, block_table, PS, kc, vc, H, hd, scale, wo
     next RMSNorm's statistics (stats: RowStats filled with one group; yg = x * gnext) -- fo_attention_o."""
     if tickets.numel() < T or part.numel() < T * H * wo.N:
         raise ValueError("attention_o: tickets / partial buffers too small")
-    _lib.call("fo_attention_o", q.data_ptr(), T, ptr(items), tok_nvis.data_ptr(), block_table.data_ptr(),
+    _lib.call("fo_attention_o_kv", q.data_ptr(), T, ptr(items), tok_nvis.data_ptr(), block_table.data_ptr(),
               block_table.shape[1], PS, kc.data_ptr(), vc.data_ptr(), H, hd, float(scale), wo.packed.data_ptr(), wo.N,
               part.data_ptr(), tickets.data_ptr(), x.data_ptr(), x.stride(0), gnext.data_ptr(), yg.data_ptr(),
-              stats.buf.data_ptr(), stream(q.device))
+              stats.buf.data_ptr(), kv_bytes(kc, vc), stream(q.device))
     stats.groups = 1
     return x
 

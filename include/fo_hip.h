@@ -68,6 +68,17 @@ int fo_gemm_qkv_rope(const void* X, int x_f32, int ldx, int M, int K, const void
                      float* ws, long long ws_floats, int* counters, int splitk, const float* rstats, int rgroups,
                      float eps, const int* pos, const int* slot, const float* cos_t, const float* sin_t, float* q_out,
                      float* kc, float* vc, int H, int KVH, int hd, int PS, hipStream_t stream);
+/* fo_gemm_qkv_rope into a paged cache of kv_bytes-wide elements: 4 = fp32 (fo_gemm_qkv_rope itself), 2 = bf16, the
+ * cache dtype the reference keeps (its k_proj / v_proj outputs under torch.autocast(bf16), models/pipeline.py:67-68,
+ * concatenated by DynamicCache.update, models/audioLLM.py:416-419).  K after bias and RoPE and V after bias are
+ * computed in fp32 as for an fp32 cache, rounded once to bf16 (round to nearest even) and stored as 2-byte elements in
+ * the same page layout -- the values fo_set_kv_bf16(1) leaves in an fp32 cache.  q_out is unchanged.  The layout is a
+ * property of the launch (pools of both kinds live in one process); fo_set_kv_bf16 has no effect on a bf16 cache. */
+int fo_gemm_qkv_rope_kv(const void* X, int x_f32, int ldx, int M, int K, const void* Wp, int N, const float* bias,
+                        float* ws, long long ws_floats, int* counters, int splitk, const float* rstats, int rgroups,
+                        float eps, const int* pos, const int* slot, const float* cos_t, const float* sin_t,
+                        float* q_out, void* kc, void* vc, int H, int KVH, int hd, int PS, int kv_bytes,
+                        hipStream_t stream);
 /* Linear layer with the preceding LayerNorm applied to X as it is loaded (a speech-encoder block's
  * pre-norm + projection: norm1 -> linear_q/k/v and norm2 -> feed_forward.w_1,
  * models/encoder/transformer.py:103-130): Y = act(LN(X; lnw, lnb, eps) W^T + bias), X fp32, M <= 64.
@@ -94,7 +105,8 @@ int fo_gemm_set_rows(int on);
 /* A/B of a bf16 paged KV (verdict r05 item 6; the reference's k_proj / v_proj outputs under torch.autocast(bf16),
  * models/pipeline.py:67-68): 1 = the q|k|v RoPE epilogues round every appended K / V element to bf16 (storage stays
  * fp32, so the numerics are a bf16 cache's and the layout is unchanged), 0 = fp32 (default).  Unset, FO_KV_BF16
- * decides.  Process-global; returns the previous setting. */
+ * decides.  Process-global; returns the previous setting.  fp32 caches only: a bf16 cache (the *_kv entries with
+ * kv_bytes 2) always rounds, whatever this says. */
 int fo_set_kv_bf16(int on);
 /* Split-K of the one-row-tile plain GEMMs (Qwen2 / TTS down, encoder FFN w2) merged inside the launch:
  * each split stores its partial tile write-through and takes the tile's ticket in `counters` (zeroed
@@ -271,6 +283,11 @@ int fo_attn_nsplit(int max_keys, int n_items, int KVH);
 int fo_rope_kv_write(const float* qkv, int ldq, int T, int H, int KVH, int hd, const int* pos, const int* slot,
                      const float* cos_t, const float* sin_t, float* q_out, float* kc, float* vc, int PS,
                      hipStream_t s);
+/* fo_rope_kv_write into a cache of kv_bytes-wide elements (4 = fp32, 2 = bf16: as fo_gemm_qkv_rope_kv).  On an fp32
+ * cache the appended K / V are rounded to bf16 values under fo_set_kv_bf16(1), as in the q|k|v epilogues. */
+int fo_rope_kv_write_kv(const float* qkv, int ldq, int T, int H, int KVH, int hd, const int* pos, const int* slot,
+                        const float* cos_t, const float* sin_t, float* q_out, void* kc, void* vc, int PS, int kv_bytes,
+                        hipStream_t s);
 /* GQA attention over paged KV for a ragged batch (transformers sdpa/eager attention reached from
  * models/audioLLM.py:482 and models/decoder/decoder.py:142-153,299-311); token t sees the first
  * tok_nvis[t] keys of its sequence (causal: own cache index + 1, full/unmasked: all).  items
@@ -286,6 +303,17 @@ int fo_attention(const float* q, int T, const int* items, int n_items, int max_r
                  const int* block_table, int maxb, int PS, const float* kc, const float* vc, int H, int KVH, int hd,
                  float scale, int nsplit, float* part_ml, float* part_o, float* out, int* tickets,
                  int keys_per_split, hipStream_t s);
+/* fo_attention over a cache of kv_bytes-wide elements: 4 = fp32 (fo_attention itself), 2 = bf16 (the reference's
+ * cache dtype, models/pipeline.py:67-68; written by fo_gemm_qkv_rope_kv / fo_rope_kv_write_kv).  Only K and V are
+ * narrow: q, scores, softmax, P, the accumulators and the split partials stay fp32, and every sum runs in the fp32
+ * kernels' order, so the result equals fo_attention's on an fp32 cache holding the same (bf16-representable) values
+ * bit for bit.  A bf16 key or value is its own MFMA operand (no hi / lo split: two MFMAs per product, not three).
+ * Refused on a bf16 cache (-2): the 2-wave form (tickets with keys_per_split < 64 at hd 128), the traced launches
+ * (fo_attention_set_trace) and FO_ATTN_NW=4 at hd 128. */
+int fo_attention_kv(const float* q, int T, const int* items, int n_items, int max_rows, const int* tok_nvis,
+                    const int* block_table, int maxb, int PS, const void* kc, const void* vc, int H, int KVH, int hd,
+                    float scale, int nsplit, float* part_ml, float* part_o, float* out, int* tickets,
+                    int keys_per_split, int kv_bytes, hipStream_t s);
 /* Conv2dSubsampling4.infer up to its output Linear (models/encoder/subsampling.py:67-73) with GlobalCMVN
  * (models/encoder/cmvn.py:24-35): feats [B][R][F] fp32 -> z [B * H2][C * W2] (the Linear's input rows, the reference's
  * x.transpose(1, 2).view(b, t, c * f)), H1 = (R - 3) / 2 + 1, W1 = (F - 3) / 2 + 1, H2 / W2 likewise from H1 / W1.
@@ -307,6 +335,12 @@ int fo_attention_o(const float* q, int T, const int* items, const int* tok_nvis,
                    int PS, const float* kc, const float* vc, int H, int hd, float scale, const void* wo, int N,
                    float* part, int* tickets, float* x, int ldx, const float* gnext, float* yg, float* sout,
                    hipStream_t s);
+/* fo_attention_o with the cache's element width stated: 4 = fp32 (fo_attention_o itself); 2 = bf16 is refused (-2,
+ * nothing launched) -- the AR speech decoder's cache stays fp32 (the bf16 cache is the Qwen2 stack's). */
+int fo_attention_o_kv(const float* q, int T, const int* items, const int* tok_nvis, const int* block_table, int maxb,
+                      int PS, const void* kc, const void* vc, int H, int hd, float scale, const void* wo, int N,
+                      float* part, int* tickets, float* x, int ldx, const float* gnext, float* yg, float* sout,
+                      int kv_bytes, hipStream_t s);
 /* The attention half of a speech-encoder block in one launch (models/encoder/transformer.py:103-118 with
  * MultiHeadedAttention.infer, models/encoder/attention.py:407-459): x += linear_out(relpos_attention(linear_q|k|v(
  * LayerNorm1(x)), ring)) for B sessions x T rows, in place, plus the updated rows' sums / sums of squares (ssum, ssq:
