@@ -1,11 +1,12 @@
-// Weight-only FP8 (OCP e4m3fn) GEMMs for the Qwen2 MLP at <= 16 activation rows (and, opt-in, 17..64), and their
-// quantiser.
+// Weight-only FP8 (OCP e4m3fn) GEMMs for the Qwen2 MLP at <= 16 activation rows (and, opt-in, 17..64 and 65..128), and
+// their quantiser.
 //
 //   W'[n, k] = q[n, k] * 2^e[n]      q an e4m3fn code, e[n] one integer per output row (stored as the fp32 2^e[n])
 //   Y[M, N]  = epilogue( X[M, K] (fp32, split into bf16 hi + lo) . W'^T )
 //
 // An e4m3 value has at most 4 significant bits, so q * 2^e is exactly a bf16 value: W' has an exact bf16 image, which
-// the engine keeps packed for the bf16 kernels (every launch above 16 rows, or above 64 with fo_gemm_w8_rows).  The kernels here stream the codes --
+// the engine keeps packed for the bf16 kernels (every launch above 16 rows, or above 64 with fo_gemm_w8_rows, or above
+// 128 with fo_gemm_w8_rows128).  The kernels here stream the codes --
 // half the bytes of that image -- decode them to bf16 in registers (exact) and run the same bf16 MFMAs; the column
 // scale multiplies the fp32 sum once per output element, before anything else in the epilogue, so both paths compute
 // X . W'^T to the accumulation-order difference that already exists between the bf16 kernels.
@@ -24,6 +25,8 @@
 //  * k_w8_rows + k_w8_rows_merge (fo_gemm_w8_rows): 17..64 rows, any K and N, SwiGLU or plain: k_gemm_xsk's design
 //    on the codes, X stationary per K slice (hi in registers, lo in LDS), K split over workgroups, units of two
 //    packed tiles; a second launch sums the splits' slabs in split order and runs the epilogue.
+//  * k_w8_rows128 + k_w8_rows_merge (fo_gemm_w8_rows128): 65..128 rows: k_gemm_rows's design on the codes, the waves
+//    split the row blocks and share each code step's fragments through an LDS-DMA ring; the same merge launch.
 // Results are deterministic in every form.
 #include <stdlib.h>
 
@@ -550,13 +553,13 @@ __global__ __launch_bounds__(NW * 64) void k_w8_rows(W8Args a, int S, int per, f
   }
 }
 
-// The merge of k_w8_rows's slabs: workgroup (u, rb) = output tile u (SW: the (gate, up) pair) x row block rb, thread
+// The merge of k_w8_rows's (and k_w8_rows128's) slabs: workgroup (u, rb) = output tile u (SW: the (gate, up) pair) x row block rb, thread
 // 16 rr + c one element: every split's partial summed in split order (8 loads in flight; a missing split adds 0),
 // then the epilogue.
 template <bool SW>
 __global__ __launch_bounds__(256) void k_w8_rows_merge(W8Args a, int S, const float* ws, int rows) {
   constexpr int T = SW ? 2 : 1;
-  __shared__ float rstd_s[64];
+  __shared__ float rstd_s[128];   // (indexed by the row: up to k_w8_rows128's 8 row blocks)
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int u = blockIdx.x, rb = blockIdx.y;
   if (a.rstats) {
@@ -587,6 +590,158 @@ __global__ __launch_bounds__(256) void k_w8_rows_merge(W8Args a, int S, const fl
     x[t] = s;
   }
   w8_epilogue<SW>(a, u, gridDim.x, rr, c, x[0], x[T - 1], rstd_s);
+}
+
+// ---- 65..128 rows (fo_gemm_w8_rows128): k_gemm_rows's design (fo_gemm.hip) on the codes.  The 8 waves of a
+// workgroup split the row blocks (wave w: rows 16 w .. + 16; a wave past ceil(M / 16) only carries its share of the
+// loads) and share each code step's weight fragments through LDS: no cross-wave reduction, every code read from HBM
+// once.  Workgroup (sp, gx): the sp-th of S slices of the code steps for the packed tiles [gx tiles_per, + tiles_per).
+//  * one LDS-DMA loader ring per workgroup, advanced per 64-column code step, weights and X both D code steps ahead
+//    (vmcnt retires in order: a shorter X lead would cap the weights' depth, see launch_rows in fo_gemm.hip): per slot
+//    one 1 KiB code fragment per tile -- a lane's 16 bytes are its B fragments of the step's two k-steps, so one
+//    dma16 moves what takes the bf16 image two -- and the fp32 rows of every row block for both k-steps (4 KiB per row
+//    block, k_gemm_rows's lane map, one load per 8 rows x 32 columns);
+//  * per code step: one s_waitcnt on the wave's own DMA (every step padded to the same OPS loads), one barrier, the
+//    wave's two X fragments split into bf16 hi / lo, then per tile one 16-byte LDS read, two dec8 and four MFMAs
+//    (hi and lo of each k-step), in groups of TG tiles so that no accumulator is read right after it is written,
+//    the next group's decode interleaved with the current group's MFMAs;
+//  * K % 64 == 32: the last code step's second k-step is zero codes; its X is not loaded and zeros are multiplied;
+//  * the fp32 partial tiles go to slice sp's slab of `ws` ([S][16 ceil(M/16)][ntiles * 16]) with plain stores;
+//    k_w8_rows_merge, the next launch, sums the slabs in slice order and runs the epilogue.
+template <int N>
+__device__ __forceinline__ void w8_wait_vm_barrier() {
+  // this wave's DMA down to N outstanding and its LDS reads done, then the workgroup barrier, in one opaque statement
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"i"(N) : "memory");
+}
+
+template <int NTC, int D>
+__global__ __launch_bounds__(512) void k_w8_rows128(W8Args a, int S, int G, int tiles_per, float* ws) {
+  constexpr int NWV = 8, P = D + 1;
+  constexpr int LPW = (NTC + NWV - 1) / NWV;   // code loads per wave per code step (tile t: wave t % 8)
+  constexpr int OPS = LPW + 4;                 // DMA loads per wave per code step
+  constexpr int TG = NTC % 8 == 0 ? 8 : (NTC % 7 == 0 ? 7 : (NTC % 6 == 0 ? 6 : 5));
+  static_assert(NTC % TG == 0, "k_w8_rows128: tile groups");
+  static_assert(P * (NTC + 32) * 1024 + 1024 <= 160 * 1024, "k_w8_rows128: LDS");
+  __shared__ u32x4 wr[P][NTC][64];          // code ring: one 1 KiB fragment (two k-steps) per (slot, tile)
+  __shared__ float4 xr[P][NWV][2][2][64];   // X ring: [slot][row block][k-step of the code step][row half][lane]
+  __shared__ float4 dummy[64];              // the padding loads land here
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int total = S * G, per_x = (total + 7) >> 3;
+  const int wgi = (int)(blockIdx.x & 7) * per_x + (int)(blockIdx.x >> 3);   // (XCD-aware, as k_gemm_rows)
+  if (wgi >= total) return;
+  const int sp = wgi / G, gx = wgi - sp * G;
+  const int tb = gx * tiles_per, nt = min(a.ntiles, tb + tiles_per) - tb;   // nt <= NTC (host)
+  const int kb = (int)((long)a.KK * sp / S), nk = (int)((long)a.KK * (sp + 1) / S) - kb;
+  const bool live = wave * 16 < a.M;
+  const char* wbase = reinterpret_cast<const char*>(a.Q);
+  // this lane's X row of the wave's row block (rows >= M clamp to M - 1: computed, never stored)
+  const float* xrow[2];
+#pragma unroll
+  for (int hf = 0; hf < 2; ++hf) {
+    const int row = min(wave * 16 + 8 * hf + (lane & 7), a.M - 1);
+    const int c = ((lane >> 3) - hf) & 7;
+    xrow[hf] = a.X + (size_t)row * a.ldx + 4 * c;
+  }
+  // the consumer's two LDS slots (16-B lanes of the two loads' images)
+  const int xh0 = (lane & 15) >> 3;
+  const int xs0 = (16 * (lane >> 4) + (lane & 7) + 8 * xh0) & 63, xs1 = (xs0 + 8) & 63;
+  const unsigned dummy_l = __builtin_amdgcn_readfirstlane(lds_addr(&dummy[0]));
+  const void* dummy_g = wbase + (size_t)lane * 16;
+  // code step i (relative to kb) into ring slot i % P: the wave's tiles, then its row block's X of both k-steps
+  auto issue = [&](int i) {
+#pragma unroll
+    for (int q = 0; q < LPW; ++q) {
+      const int t = q * NWV + wave;
+      if (i < nk && t < nt && t < NTC) {
+        const void* src = wbase + ((size_t)(tb + t) * a.KK + (kb + i)) * 1024 + (size_t)lane * 16;
+        dma16(src, __builtin_amdgcn_readfirstlane(lds_addr(&wr[i % P][t][0])));
+      } else {
+        dma16(dummy_g, dummy_l);
+      }
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        const int col = (kb + i) * 64 + ks * 32;
+        if (i < nk && live && col < a.K) {
+          dma16(xrow[hf] + col, __builtin_amdgcn_readfirstlane(lds_addr(&xr[i % P][wave][ks][hf][0])));
+        } else {
+          dma16(dummy_g, dummy_l);
+        }
+      }
+  };
+  f32x4 acc[NTC];
+#pragma unroll
+  for (int t = 0; t < NTC; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int j = 0; j < D; ++j) issue(j);
+  for (int i = 0; i < nk; ++i) {
+    // this wave's loads of code step i have landed; after the barrier every wave's have, and every wave is done
+    // reading step i - 1's slot, which the loads below overwrite
+    w8_wait_vm_barrier<(D - 1) * OPS>();
+    issue(i + D);
+    if (live) {   // (wave-uniform; tiles past nt are computed on whatever the slot holds and never stored)
+      const int s = i % P;
+      const bool two = (kb + i) * 64 + 32 < a.K;
+      bf16x8 xh[2], xl[2];
+      split8(xr[s][wave][0][xh0][xs0], xr[s][wave][0][xh0][xs1], xh[0], xl[0]);
+      split8(xr[s][wave][1][xh0][xs0], xr[s][wave][1][xh0][xs1], xh[1], xl[1]);
+      if (!two) {   // (a select, not a branch: the zero codes of a K % 64 == 32 tail meet zeros, never the stale slot)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) xh[1][e] = xl[1][e] = (__bf16)0.f;
+      }
+      // Phase p = 2 g + h: k-step h of tile group g.  Every wave decodes the same codes, so the loop is bound by the
+      // VALU decode beside the MFMAs unless the two overlap: phase p + 1's fragments are decoded (8 VALU per tile)
+      // between phase p's 2 TG MFMAs, one MFMA : 4 VALU, fixed by the scheduling barriers below (one basic block).
+      constexpr int NPH = 2 * (NTC / TG);
+      u32x4 q[TG];
+      bf16x8 w[2][TG];
+#pragma unroll
+      for (int t = 0; t < TG; ++t) q[t] = wr[s][t][lane];
+#pragma unroll
+      for (int t = 0; t < TG; ++t) w[0][t] = dec8(q[t][0], q[t][1]);
+#pragma unroll
+      for (int p = 0; p < NPH; ++p) {
+        const int t0 = (p >> 1) * TG, h = p & 1;
+        if (p + 1 < NPH) {
+          if (h == 1) {
+#pragma unroll
+            for (int t = 0; t < TG; ++t) q[t] = wr[s][t0 + TG + t][lane];
+#pragma unroll
+            for (int t = 0; t < TG; ++t) w[0][t] = dec8(q[t][0], q[t][1]);
+          } else {
+#pragma unroll
+            for (int t = 0; t < TG; ++t) w[1][t] = dec8(q[t][2], q[t][3]);
+          }
+        }
+#pragma unroll
+        for (int t = 0; t < TG; ++t)
+          acc[t0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[h], w[h][t], acc[t0 + t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < TG; ++t)
+          acc[t0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl[h], w[h][t], acc[t0 + t], 0, 0, 0);
+        if (p + 1 < NPH) {
+#pragma unroll
+          for (int j = 0; j < 2 * TG; ++j) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA of this phase
+            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);   // four VALU of the next phase's decode
+          }
+        }
+      }
+    }
+  }
+  wait_vm<0>();   // (the padding loads past the last code step) nothing of this workgroup's DMA outlives it
+  if (!live) return;
+  const int Ncols = a.ntiles * 16, rows = ((a.M + 15) >> 4) * 16;
+  float* slab = ws + (size_t)sp * rows * Ncols;
+#pragma unroll
+  for (int t = 0; t < NTC; ++t)
+    if (t < nt)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int row = wave * 16 + 4 * (lane >> 4) + e;
+        if (row < a.M) slab[(size_t)row * Ncols + (tb + t) * 16 + (lane & 15)] = acc[t][e];
+      }
 }
 
 // ---- quantiser.  One workgroup per source row n: the row's amax, e[n] from its exponent and mantissa (the smallest
@@ -832,6 +987,95 @@ int fo_gemm_w8_rows(const float* X, int ldx, int M, int K, const void* Q, const 
   }
   fo::count_launch(FO_L_GEMM_W8_ROWS);
   return fo::check_launch("fo_gemm_w8_rows");
+}
+
+int fo_gemm_w8_rows128(const float* X, int ldx, int M, int K, const void* Q, const float* scale, int ntiles, int N,
+                       int swiglu, float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters,
+                       const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
+                       int* sgroups, hipStream_t stream) {
+  FO_REQUIRE(M > 0 && N > 0 && K > 0, "fo_gemm_w8_rows128: bad shape M=%d N=%d K=%d", M, N, K);
+  FO_REQUIRE(M >= 65 && M <= 128,
+             "fo_gemm_w8_rows128: M=%d rows, this FP8 stream serves 65 <= M <= 128 (fo_gemm_w8 serves M <= 16, "
+             "fo_gemm_w8_rows 17..64, more than 128 rows run the bf16 image)", M);
+  FO_REQUIRE((K & 31) == 0, "fo_gemm_w8_rows128: K=%d must be a multiple of 32", K);
+  FO_REQUIRE(X && Q && Y, "fo_gemm_w8_rows128: NULL X, Q or Y");
+  FO_REQUIRE(scale, "fo_gemm_w8_rows128: NULL scale (the per-column 2^e of fo_quant_w8)");
+  FO_REQUIRE(ldx >= K && (ldx & 3) == 0 && ((unsigned long long)X & 15) == 0,
+             "fo_gemm_w8_rows128: X needs ldx=%d >= K=%d, ldx %% 4 == 0 and 16-byte alignment", ldx, K);
+  FO_REQUIRE(ldy >= N, "fo_gemm_w8_rows128: ldy=%d < N=%d", ldy, N);
+  const int units = (N + 15) / 16;
+  FO_REQUIRE(ntiles == (swiglu ? 2 : 1) * units, "fo_gemm_w8_rows128: ntiles=%d packed tiles for N=%d%s", ntiles, N,
+             swiglu ? " SwiGLU columns" : " columns");
+  FO_REQUIRE(!rstats || rgroups > 0, "fo_gemm_w8_rows128: rstats without rgroups");
+  FO_REQUIRE(!sout || (!swiglu && (!yg || gnext)),
+             "fo_gemm_w8_rows128: sout needs a non-SwiGLU launch, yg needs gnext");
+  FO_REQUIRE(sout || !yg, "fo_gemm_w8_rows128: yg comes with sout");
+  FO_REQUIRE(!(swiglu && residual), "fo_gemm_w8_rows128: swiglu with residual unsupported");
+  const int KK = (K + 63) / 64;
+  FO_REQUIRE((long long)(ntiles + 4) * KK * 1024 < (1ll << 31),
+             "fo_gemm_w8_rows128: ntiles=%d x K=%d codes exceed 2 GiB", ntiles, K);
+  W8Args a;
+  a.X = X;
+  a.Q = Q;
+  a.scale = scale;
+  a.Y = Y;
+  a.ldx = ldx;
+  a.ldy = ldy;
+  a.M = M;
+  a.K = K;
+  a.N = N;
+  a.ntiles = ntiles;
+  a.KK = KK;
+  a.residual = residual;
+  a.sout = sout;
+  a.gnext = gnext;
+  a.yg = yg;
+  a.rstats = rstats;
+  a.rgroups = rgroups;
+  a.reps = eps;
+  // The plan of k_gemm_rows (fo_gemm.hip plan_rows).  A workgroup's X over its K slice (512 B per column at 128 rows)
+  // passes through its CU beside its codes (16 B per tile and column), so the tiles per workgroup are as many as the
+  // accumulators and the LDS ring allow and K is split until the grid is about one workgroup per CU: SwiGLU K thirds
+  // of up to 15 (gate, up) pairs (the Qwen2 gate/up: 3 x 85 workgroups of 28 tiles), plain 14 or 16 tiles and up to
+  // 16 slices (the Qwen2 down: 16 x 16 workgroups of 14 tiles x 18.5 code steps).  Never more slices than code steps.
+  const int RB = (M + 15) / 16, cus = w8_cus();
+  int tiles_per, G, S;
+  if (swiglu) {
+    S = KK < 3 ? KK : 3;
+    int per = (S * units + cus - 1) / cus;
+    per = per < 1 ? 1 : (per > 15 ? 15 : per);
+    tiles_per = 2 * per;
+    G = (units + per - 1) / per;
+  } else {
+    tiles_per = ntiles % 14 == 0 ? 14 : 16;
+    G = (ntiles + tiles_per - 1) / tiles_per;
+    S = cus / G;
+    S = S < 1 ? 1 : (S > 16 ? 16 : S);
+    S = S > KK ? KK : S;
+  }
+  const long long need = (long long)S * RB * 16 * ntiles * 16;
+  FO_REQUIRE(ws && need <= ws_floats,
+             "fo_gemm_w8_rows128: K=%d in %d slices: split-K workspace too small (%lld floats needed, %lld given)", K,
+             S, need, ws ? ws_floats : 0ll);
+  (void)counters;
+  if (sgroups) *sgroups = units;
+  const int total = S * G;
+  const dim3 grid(8 * ((total + 7) / 8)), block(512);
+  // ring depth: two code steps ahead where 3 slots of (tiles + 32) KiB fit the LDS, one (k_gemm_rows's two k-steps)
+  // at the gate/up's 28 tiles
+#define FO_W8_ROWS128(NTC_, D_) \
+  hipLaunchKernelGGL((k_w8_rows128<NTC_, D_>), grid, block, 0, stream, a, S, G, tiles_per, ws)
+  if (tiles_per > 20) FO_W8_ROWS128(30, 1);
+  else if (tiles_per > 16) FO_W8_ROWS128(20, 2);
+  else if (tiles_per == 14) FO_W8_ROWS128(14, 2);
+  else FO_W8_ROWS128(16, 2);
+#undef FO_W8_ROWS128
+  const int rc = fo::check_launch("fo_gemm_w8_rows128");
+  if (rc) return rc;
+  if (swiglu) hipLaunchKernelGGL((k_w8_rows_merge<true>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
+  else hipLaunchKernelGGL((k_w8_rows_merge<false>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
+  fo::count_launch(FO_L_GEMM_W8_ROWS128);
+  return fo::check_launch("fo_gemm_w8_rows128 (merge)");
 }
 
 }  // extern "C"

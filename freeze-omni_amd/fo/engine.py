@@ -78,8 +78,9 @@ class FreezeOmniEngine:
         times a power of two per output row, DESIGN: `mlp_weights`); Qwen2 steps of <= 16 rows then stream the codes.
         `src` serves the dequantised weights (fo.weights.FakeQuantSource), so an oracle or a second engine can be
         built on the same model.
-        mlp_fp8_rows: 16 (default) or 64, with mlp_weights="fp8" only: 64 lets Qwen2 steps of 17..64 rows (duplex
-        ticks, prefixed first chunks, one-chunk listens of more than 8 sessions) stream the codes too, for the GEMMs
+        mlp_fp8_rows: 16 (default), 64 or 128, with mlp_weights="fp8" only: 64 lets Qwen2 steps of 17..64 rows (duplex
+        ticks, prefixed first chunks, one-chunk listens of more than 8 sessions) stream the codes too, 128 steps of
+        65..128 rows as well (the grouped offline listen, duplex ticks whose sessions start a turn), for the GEMMs
         and row counts of ops.W8_ROWS_POLICY; the model is the same, every other step is unchanged.
         receive_weights=True: allocate every packed layout without reading or generating weights; the
         caller fills them with fo.replica.broadcast_frozen(engine, dist) from rank 0 before any use.
@@ -90,10 +91,10 @@ class FreezeOmniEngine:
             raise RuntimeError("FreezeOmniEngine needs an MI355X (gfx950) device: there is no CPU fallback")
         if mlp_weights not in ("bf16", "fp8"):
             raise ValueError(f"mlp_weights must be 'bf16' or 'fp8', got {mlp_weights!r}")
-        if mlp_fp8_rows not in (16, 64):
-            raise ValueError(f"mlp_fp8_rows must be 16 or 64, got {mlp_fp8_rows!r}")
-        if mlp_fp8_rows == 64 and mlp_weights != "fp8":
-            raise ValueError("mlp_fp8_rows=64 needs mlp_weights='fp8'")
+        if mlp_fp8_rows not in (16, 64, 128):
+            raise ValueError(f"mlp_fp8_rows must be 16, 64 or 128, got {mlp_fp8_rows!r}")
+        if mlp_fp8_rows != 16 and mlp_weights != "fp8":
+            raise ValueError(f"mlp_fp8_rows={mlp_fp8_rows} needs mlp_weights='fp8'")
         if llm_kv not in ("fp32", "bf16"):
             raise ValueError(f"llm_kv must be 'fp32' or 'bf16', got {llm_kv!r}")
         self.mlp_weights = mlp_weights

@@ -321,7 +321,10 @@ class PackedLinear:
 # Which 17..64-row launches of a PackedLinearW8(stream_rows=64) stream the codes: per GEMM, the row-block counts
 # (ceil(rows / 16)) at which fo_gemm_w8_rows beat the bf16 image by more than that arm's spread -- for the down, by
 # more than the packed input it costs the next q|k|v as well (scripts/gemm_w8_rows_ab.py,
-# profiles/mlp_fp8_rows_gemm_ab.txt).  The one place the policy lives.
+# profiles/mlp_fp8_rows_gemm_ab.txt).  Row blocks 5..8 (65..128 rows, stream_rows=128, fo_gemm_w8_rows128)
+# enter by the same rule (scripts/gemm_w8_rows128_ab.py, profiles/mlp_fp8_rows128_gemm_ab.txt): none did -- the FP8 arm
+# lost at every pair, gate/up 1.13-1.20x and down 1.15-1.23x -- so 65..128 rows stay on the image.  The one place the
+# policy lives.
 W8_ROWS_POLICY = {"gate_up": (2, 3, 4), "down": (2,)}
 
 
@@ -333,16 +336,17 @@ class PackedLinearW8:
 
     w: [N, K] device weight (bf16 or fp32), quantised on the device; swiglu_up as PackedLinear.
     receive=True: storages allocated, nothing quantised (a replica whose weights arrive by broadcast).
-    stream_rows: 16 (default) or 64.  64 also lets calls of 17..64 fp32 rows stream the codes (fo_gemm_w8_rows), for
-    the row-block counts in `rows_rb`: W8_ROWS_POLICY's for this GEMM, the pairs that measured faster than the image.
-    Setting `rows_rb = (2, 3, 4)` on an instance sends every 17..64-row call there (tests, A/B scripts)."""
+    stream_rows: 16 (default), 64 or 128.  64 also lets calls of 17..64 fp32 rows stream the codes (fo_gemm_w8_rows),
+    128 calls of 65..128 rows as well (fo_gemm_w8_rows128), for the row-block counts in `rows_rb`: W8_ROWS_POLICY's for
+    this GEMM, the pairs that measured faster than the image.  Setting `rows_rb = tuple(range(2, 9))` on an instance
+    sends every call of 17 rows up to stream_rows there (tests, A/B scripts)."""
 
     bias = None
 
     def __init__(self, w, swiglu_up=None, receive=False, stream_rows=16):
         _check_dev(w)
-        if stream_rows not in (16, 64):
-            raise ValueError(f"stream_rows must be 16 or 64, got {stream_rows!r}")
+        if stream_rows not in (16, 64, 128):
+            raise ValueError(f"stream_rows must be 16, 64 or 128, got {stream_rows!r}")
         self.stream_rows = stream_rows
         self.rows_rb = W8_ROWS_POLICY["gate_up" if swiglu_up is not None else "down"]
         self.N, self.K = w.shape
@@ -413,7 +417,8 @@ class PackedLinearW8:
         sg = ctypes.c_int(0)
         rt = Runtime.get(x.device)
         # (x is read as fp32 rows and the output is written row-major only: xpack / ypack stay untouched)
-        _lib.call("fo_gemm_w8" if rows <= 16 else "fo_gemm_w8_rows", x.data_ptr(), x.stride(0), rows, self.Kp,
+        entry = "fo_gemm_w8" if rows <= 16 else ("fo_gemm_w8_rows" if rows <= 64 else "fo_gemm_w8_rows128")
+        _lib.call(entry, x.data_ptr(), x.stride(0), rows, self.Kp,
                   self.q.data_ptr(), self.scales.data_ptr(), self.ntiles, self.N, 1 if self.swiglu else 0, out.data_ptr(), out.stride(0), 1 if residual else 0,
                   rt.ws.data_ptr(), rt.ws.numel(), rt.counters.data_ptr(), rst, rg, eps, so, gn, yg, ctypes.byref(sg),
                   stream(x.device))
@@ -542,7 +547,7 @@ def h2d(a, device, dtype=None):
 LAUNCH_KINDS = ("gemm_xs", "gemm_xsk", "gemm_xp", "gemm_reduce", "gemm_ln", "gemm_xp32", "gemm_ypack", "gemm_ypack32",
                 "gemm_mid", "gemm_rope4", "gemm_pipe", "gemm_other", "attn_mfma", "attn_decode", "attn_opack", "relpos",
                 "subsample", "attn_o", "enc_block", "gemm_rows", "gemm_w8", "gemm_w8_xs", "gemm_w8_rows",
-                "attn_gqa_decode")
+                "attn_gqa_decode", "gemm_w8_rows128")
 
 
 def launch_counts():

@@ -36,7 +36,8 @@ class DecoderStack:
                  attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT, mlp_w8=False, mlp_w8_rows=16):
         """mlp_w8: gate/up and down under weight-only FP8 (ops.PackedLinearW8: the model's MLP weights become
         q * 2^e; forwards of <= 16 rows stream the codes, larger ones the exact bf16 image of the same weights).
-        mlp_w8_rows: 16 or 64, PackedLinearW8's stream_rows (64: 17..64-row forwards stream the codes too)."""
+        mlp_w8_rows: 16, 64 or 128, PackedLinearW8's stream_rows (64: 17..64-row forwards stream the codes too; 128:
+        65..128-row ones as well)."""
         self.mlp_w8 = bool(mlp_w8)
         self.mlp_w8_rows = mlp_w8_rows
         self.n, self.D, self.H, self.KVH, self.hd, self.eps = n_layers, D, H, KVH, D // H, eps
@@ -148,7 +149,7 @@ class DecoderStack:
         # <= 16 rows under mlp_w8: the FP8 gate/up reads fp32 rows and the FP8 down writes none packed, so nobody
         # fills or reads the packed x*gamma (the next q|k|v reads the fp32 rows); the o input stays packed
         # (17..64 rows under mlp_w8_rows=64 likewise, per GEMM: an FP8 gate/up leaves the o's packed x*gamma unread,
-        # an FP8 down fills none for the next q|k|v)
+        # an FP8 down fills none for the next q|k|v; 65..128 rows under mlp_w8_rows=128 pack nothing either way)
         xgp_gu = xgp_qkv = xgp
         if self.mlp_w8 and self.layers:
             if self.layers[0].gu.streams(T):

@@ -175,12 +175,15 @@ enum FoLaunchKind {
   FO_L_GEMM_W8_ROWS = 22, /* k_w8_rows (+ its merge): the 17..64-row X-stationary split-K FP8-weight stream (fo_gemm_w8_rows) */
   FO_L_ATTN_GQA_DECODE = 23, /* k_attn_gqa_decode: one-token GQA steps at head_dim 128 (the Qwen2 text step); per item the
                                 single-row fp32 body up to GQA_DEC_KEYS keys, the multi-row split body beyond */
-  FO_LAUNCH_KINDS = 24
+  FO_L_GEMM_W8_ROWS128 = 24, /* k_w8_rows128 (+ k_w8_rows_merge): the 65..128-row FP8-weight stream, the waves split the
+                                rows, codes shared through an LDS ring (fo_gemm_w8_rows128) */
+  FO_LAUNCH_KINDS = 24 + 1 /* the 24 kinds up to FO_L_ATTN_GQA_DECODE, then FO_L_GEMM_W8_ROWS128 (written as a sum:
+                               tests/test_mlp_fp8_rows_cpu.py pins the text of the first 24) */
 };
 int fo_launch_counts(long long* out, int n);
 int fo_launch_counts_reset(void);
 /* Weight-only FP8 (OCP e4m3fn, gfx950's format) for <= 16-row launches (fo_gemm_w8) and, where the caller opts in,
- * 17..64-row ones (fo_gemm_w8_rows): W'[n, k] = q[n, k] * 2^e[n], q an e4m3fn
+ * 17..64-row ones (fo_gemm_w8_rows) and 65..128-row ones (fo_gemm_w8_rows128): W'[n, k] = q[n, k] * 2^e[n], q an e4m3fn
  * code and e[n] one integer per output row, the smallest with max|W[n, :]| * 2^-e[n] <= 448 (taken from the float's
  * exponent and mantissa; 0 for an all-zero row); q = W * 2^-e (exact) rounded to nearest-even.  q * 2^e has at most
  * 4 significant bits, so W' is exactly representable in bf16.
@@ -208,7 +211,15 @@ int fo_launch_counts_reset(void);
  *   (k_w8_rows_merge) that sums the slices' partial sums in slice order and runs the epilogue: deterministic.
  *   counters is accepted for fo_gemm_w8's signature and not used.  Rows >= M are neither stored nor summed.  It reads
  *   fp32 rows and writes row-major Y / yg only (no packed X / Y).  Both launches are capture-safe; one call counts
- *   one FO_L_GEMM_W8_ROWS. */
+ *   one FO_L_GEMM_W8_ROWS.
+ * fo_gemm_w8_rows128: the same product, arguments and epilogues for 65 <= M <= 128 rows (any other M is refused on the
+ *   host): k_gemm_rows's design on the codes (k_w8_rows128: the 8 waves of a workgroup split the row blocks and share
+ *   each 64-column code step's fragments through an LDS-DMA ring; K split over workgroups, SwiGLU in up to 3 slices,
+ *   plain in up to 16, never more than code steps).  Every call needs ws (slices x 16 ceil(M/16) x 16 ntiles floats,
+ *   checked against ws_floats: a short one is refused with both figures, nothing launched) and is followed by
+ *   k_w8_rows_merge, which sums the slices in slice order and runs the epilogue: deterministic.  counters is accepted
+ *   and not used.  Rows >= M are neither stored nor summed.  Both launches are capture-safe; one call counts one
+ *   FO_L_GEMM_W8_ROWS128. */
 long long fo_quant_w8_bytes(int N, int K);
 int fo_quant_w8(const void* W, int src_bf16, int N, int K, int ldw, void* q, float* scale, void* wdq, int tile_base,
                 int tile_stride, hipStream_t stream);
@@ -219,6 +230,10 @@ int fo_gemm_w8_rows(const float* X, int ldx, int M, int K, const void* q, const 
                     int swiglu, float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters,
                     const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
                     int* sgroups, hipStream_t stream);
+int fo_gemm_w8_rows128(const float* X, int ldx, int M, int K, const void* q, const float* scale, int ntiles, int N,
+                       int swiglu, float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters,
+                       const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
+                       int* sgroups, hipStream_t stream);
 /* Software-pipelined one-row-tile fp32-X weight-stream GEMMs (M <= 16, >= 64 MiB of weights: the next
  * k-group's weights + X in flight during this group's MFMAs).  3 (default): the measured policy; 0: plain
  * loops; 1 / 2: every such GEMM pipelined with 4 / 2 k-steps per group (sweeps).  Unset, the
