@@ -22,12 +22,13 @@ typedef __attribute__((address_space(1))) float g_f32;
 __device__ __forceinline__ void st_wt(float* p, float v) {
   __hip_atomic_store((g_f32*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void* base) {
+// (a load at or past `bytes` is out of the descriptor's range: dropped without touching memory, it returns zeros)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void* base, int bytes = 0x7fffffff) {
   const unsigned long long b = (unsigned long long)base;
   return __builtin_amdgcn_make_buffer_rsrc(
       reinterpret_cast<void*>(((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(b >> 32)) << 32) |
                               (unsigned)__builtin_amdgcn_readfirstlane((unsigned)b)),
-      (short)0, 0x7fffffff, 0x00020000);
+      (short)0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
 __device__ __forceinline__ float ld_sc1(__amdgpu_buffer_rsrc_t r, size_t off_floats) {
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (unsigned)(off_floats * 4), 0, 16));

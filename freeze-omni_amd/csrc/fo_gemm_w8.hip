@@ -1,33 +1,20 @@
-// Weight-only FP8 (OCP e4m3fn) GEMMs for the Qwen2 MLP at <= 16 activation rows (and, opt-in, 17..64 and 65..128), and
-// their quantiser.
+// Weight-only FP8 (OCP e4m3fn) GEMMs for the Qwen2 MLP, and their quantiser.
 //
 //   W'[n, k] = q[n, k] * 2^e[n]      q an e4m3fn code, e[n] one integer per output row (stored as the fp32 2^e[n])
 //   Y[M, N]  = epilogue( X[M, K] (fp32, split into bf16 hi + lo) . W'^T )
 //
 // An e4m3 value has at most 4 significant bits, so q * 2^e is exactly a bf16 value: W' has an exact bf16 image, which
-// the engine keeps packed for the bf16 kernels (every launch above 16 rows, or above 64 with fo_gemm_w8_rows, or above
-// 128 with fo_gemm_w8_rows128).  The kernels here stream the codes --
-// half the bytes of that image -- decode them to bf16 in registers (exact) and run the same bf16 MFMAs; the column
-// scale multiplies the fp32 sum once per output element, before anything else in the epilogue, so both paths compute
-// X . W'^T to the accumulation-order difference that already exists between the bf16 kernels.
+// the engine keeps packed for the bf16 kernels.  The kernels here stream the codes -- half the bytes of that image --
+// decode them to bf16 in registers (exact) and run the same bf16 MFMAs; the column scale multiplies the fp32 sum once
+// per output element, before anything else in the epilogue, so both paths compute X . W'^T to the accumulation-order
+// difference that already exists between the bf16 kernels.  Results are deterministic in every form.
 //
 // Code layout (include/fo_hip.h): [tile][K64][64 lanes][16 codes], a lane's 16 bytes being its 8-element MFMA
-// B-fragments of two consecutive 32-column k-steps, K padded to a multiple of 64 with zero codes.
-//  * k_w8: the general form, any K % 32 == 0; one workgroup per output tile (per gate/up pair), its waves split K and
-//    reduce through LDS in wave order.
-//  * k_w8_xs: the SwiGLU pair at K = 3584, X-stationary and persistent as k_gemm_xs (fo_gemm.hip): X hi in registers,
-//    lo in LDS, units dealt evenly to at most one workgroup per CU, the next unit's codes issued before the current
-//    one is reduced, a fixed-order cross-wave reduction.
-//  * k_w8_sk: long-K plain projections (the down, K = 18944): 4 tiles per workgroup share each X fragment's load and
-//    hi / lo split, and K is split across workgroups to fill the chip.  The splits merge inside the launch, in this
-//    file: each stores its partial tiles write-through and takes the tile group's ticket; the split that arrives
-//    last sums every partial in split order (so the bits do not depend on which one that is) and runs the epilogue.
-//  * k_w8_rows + k_w8_rows_merge (fo_gemm_w8_rows): 17..64 rows, any K and N, SwiGLU or plain: k_gemm_xsk's design
-//    on the codes, X stationary per K slice (hi in registers, lo in LDS), K split over workgroups, units of two
-//    packed tiles; a second launch sums the splits' slabs in split order and runs the epilogue.
-//  * k_w8_rows128 + k_w8_rows_merge (fo_gemm_w8_rows128): 65..128 rows: k_gemm_rows's design on the codes, the waves
-//    split the row blocks and share each code step's fragments through an LDS-DMA ring; the same merge launch.
-// Results are deterministic in every form.
+// B-fragments of two consecutive 32-column k-steps, K padded to a multiple of 64 with zero codes.  One entry per row
+// band, each kernel's design above the kernel:
+//  * fo_gemm_w8, <= 16 rows: k_w8 (general), k_w8_xs (the SwiGLU pair at K = 3584) or k_w8_sk (long-K plain);
+//  * fo_gemm_w8_rows, 17..64 rows: k_w8_rows, then k_w8_rows_merge where K is split;
+//  * fo_gemm_w8_rows128, 65..128 rows: k_w8_rows128, then k_w8_rows_merge.
 #include <stdlib.h>
 
 #include "fo_common.h"
@@ -79,15 +66,6 @@ __device__ __forceinline__ void split8(const float4 p0, const float4 p1, bf16x8&
   }
 }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t code_rsrc(const W8Args& a) {
-  // the descriptor covers exactly the codes (ntiles * KK KiB): a load of "tile ntiles" is out of range and dropped
-  const unsigned long long b = (unsigned long long)a.Q;
-  return __builtin_amdgcn_make_buffer_rsrc(
-      reinterpret_cast<void*>(((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(b >> 32)) << 32) |
-                              (unsigned)__builtin_amdgcn_readfirstlane((unsigned)b)),
-      (short)0, __builtin_amdgcn_readfirstlane(a.ntiles * a.KK * 1024), 0x00020000);
-}
-
 // Output element (row rr, column c) of unit u, thread e = 16 rr + c of the first 256: x1 / x2 are the fp32 sums of
 // the unit's (gate, up) tiles (SW) or of its one tile.  The column scale first, then the consumer's rstd, SwiGLU,
 // the residual and the store; a producer also writes yg = y * gamma_next and the row's sum of squares over the
@@ -127,10 +105,12 @@ __device__ __forceinline__ void w8_epilogue(const W8Args& a, int u, int groups, 
   }
 }
 
+// The consumer's rstd of rows [r0, r0 + n) into rstd_s[row], a row per wave of NW: the row's statistics summed
+// lane-strided, then across the wave.  Rows >= M take the last row's (computed, never stored).
 template <int NW>
-__device__ __forceinline__ void w8_rstd(const W8Args& a, float* rstd_s, int wave, int lane) {
-  for (int rr = wave; rr < 16; rr += NW) {
-    const int m = min(rr, a.M - 1);
+__device__ __forceinline__ void w8_rstd(const W8Args& a, float* rstd_s, int wave, int lane, int r0 = 0, int n = 16) {
+  for (int r = wave; r < n; r += NW) {
+    const int rr = r0 + r, m = min(rr, a.M - 1);
     float v = 0.f;
     for (int j = lane; j < a.rgroups; j += 64) v += a.rstats[(size_t)m * a.rgroups + j];
     v = wave_sum(v);
@@ -138,106 +118,19 @@ __device__ __forceinline__ void w8_rstd(const W8Args& a, float* rstd_s, int wave
   }
 }
 
-// ---- general form: workgroup u = output tile u (SW: the (gate, up) pair 2u, 2u + 1); wave w takes the code steps
-// [KK w / NW, KK (w + 1) / NW), U of them (per tile) in flight
-template <int NW, bool SW>
-__global__ __launch_bounds__(NW * 64) void k_w8(W8Args a) {
-  constexpr int T = SW ? 2 : 1, U = SW ? 2 : 4;   // (4 pair steps spill at 16 waves' 128 VGPRs)
-  __shared__ float part[NW][T][16][17];
-  __shared__ float rstd_s[16];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int u = blockIdx.x;
-  const __amdgpu_buffer_rsrc_t srd = code_rsrc(a);
-  const int kb = (int)((long)a.KK * wave / NW), ke = (int)((long)a.KK * (wave + 1) / NW);
-  const int row = min(lane & 15, a.M - 1);
-  const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
-  const int voff = lane * 16;
-  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
-  f32x4 acc[T];
+// One wave's accumulator tile (a lane holds rows 4 (lane >> 4) .. + 4 of column lane & 15) into a padded LDS tile
+template <typename Tile>
+__device__ __forceinline__ void w8_store_tile(Tile& tile, const f32x4 acc, int lane, int r0 = 0) {
 #pragma unroll
-  for (int t = 0; t < T; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int k0 = kb; k0 < ke; k0 += U) {
-    u32x4 q[U][T];
-    float4 x[U][4];
-#pragma unroll
-    for (int i = 0; i < U; ++i) {
-      const int kk = k0 + i;
-      if (kk < ke) {
-#pragma unroll
-        for (int t = 0; t < T; ++t)
-          q[i][t] = __builtin_bit_cast(
-              u32x4, __builtin_amdgcn_raw_buffer_load_b128(srd, voff, ((T * u + t) * a.KK + kk) * 1024, 2));
-        const float* p = xp + (size_t)kk * 64;
-        x[i][0] = reinterpret_cast<const float4*>(p)[0];
-        x[i][1] = reinterpret_cast<const float4*>(p)[1];
-        if (kk * 64 + 32 < a.K) {   // (K % 64 == 32: the last step's second half is zero codes and no X)
-          x[i][2] = reinterpret_cast<const float4*>(p + 32)[0];
-          x[i][3] = reinterpret_cast<const float4*>(p + 32)[1];
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < U; ++i) {
-      const int kk = k0 + i;
-      if (kk < ke) {
-        bf16x8 hi, lo;
-        split8(x[i][0], x[i][1], hi, lo);
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-          const bf16x8 w = dec8(q[i][t][0], q[i][t][1]);
-          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hi, w, acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lo, w, acc[t], 0, 0, 0);
-        }
-        if (kk * 64 + 32 < a.K) {
-          split8(x[i][2], x[i][3], hi, lo);
-#pragma unroll
-          for (int t = 0; t < T; ++t) {
-            const bf16x8 w = dec8(q[i][t][2], q[i][t][3]);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hi, w, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lo, w, acc[t], 0, 0, 0);
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < T; ++t)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) part[wave][t][4 * (lane >> 4) + i][lane & 15] = acc[t][i];
-  __syncthreads();
-  const int e = threadIdx.x;
-  if (e < 256) {
-    const int rr = e >> 4, c = e & 15;
-    float x1 = 0.f, x2 = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      x1 += part[w][0][rr][c];
-      if constexpr (SW) x2 += part[w][1][rr][c];
-    }
-    w8_epilogue<SW>(a, u, gridDim.x, rr, c, x1, x2, rstd_s);
-  }
+  for (int i = 0; i < 4; ++i) tile[r0 + 4 * (lane >> 4) + i][lane & 15] = acc[i];
 }
 
-// ---- long-K plain form: workgroup (tg, sp) = tiles NT tg .. + NT over the sp-th of S slices of the code steps, the
-// slice split over the waves as in k_w8.  ws: S slabs of [16][groups * NT * 16] partial sums; counters: one zeroed
-// ticket per tile group, left zeroed.  The hand-off is fo_common.h's (st_wt / ld_sc1): no fences, no waiting.
-template <int NW, int NT>
-__global__ __launch_bounds__(NW * 64) void k_w8_sk(W8Args a, int S, float* ws, int* counters) {
-  constexpr int U = 2;
-  __shared__ float part[NW][NT][16][17];
-  __shared__ float red[NT][16][17];
-  __shared__ float rstd_s[16];
-  __shared__ int last_s;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int tg = blockIdx.x, sp = blockIdx.y;
-  const __amdgpu_buffer_rsrc_t srd = code_rsrc(a);
-  const int k_lo = (int)((long)a.KK * sp / S), k_n = (int)((long)a.KK * (sp + 1) / S) - k_lo;
-  const int kb = k_lo + (int)((long)k_n * wave / NW), ke = k_lo + (int)((long)k_n * (wave + 1) / NW);
-  const int row = min(lane & 15, a.M - 1);
-  const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
-  const int voff = lane * 16;
-  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
-  f32x4 acc[NT];
+// acc[t] = X[rows 0..16, code steps [kb, ke)] . (packed tile tile0 + t)^T for t < NT: U code steps in flight, each X
+// fragment loaded and split once for the NT tiles.  The codes' descriptor covers exactly the codes (ntiles * KK KiB): a
+// tile at or past ntiles is out of its range and loads zero codes.
+template <int NT, int U>
+__device__ __forceinline__ void w8_accumulate(const W8Args& a, __amdgpu_buffer_rsrc_t srd, const float* xp, int voff,
+                                              int tile0, int kb, int ke, f32x4 (&acc)[NT]) {
 #pragma unroll
   for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int k0 = kb; k0 < ke; k0 += U) {
@@ -248,13 +141,13 @@ __global__ __launch_bounds__(NW * 64) void k_w8_sk(W8Args a, int S, float* ws, i
       const int kk = k0 + i;
       if (kk < ke) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t)   // (a tile past ntiles is out of the descriptor's range: zero codes)
+        for (int t = 0; t < NT; ++t)
           q[i][t] = __builtin_bit_cast(
-              u32x4, __builtin_amdgcn_raw_buffer_load_b128(srd, voff, ((NT * tg + t) * a.KK + kk) * 1024, 2));
+              u32x4, __builtin_amdgcn_raw_buffer_load_b128(srd, voff, ((tile0 + t) * a.KK + kk) * 1024, 2));
         const float* p = xp + (size_t)kk * 64;
         x[i][0] = reinterpret_cast<const float4*>(p)[0];
         x[i][1] = reinterpret_cast<const float4*>(p)[1];
-        if (kk * 64 + 32 < a.K) {
+        if (kk * 64 + 32 < a.K) {   // (K % 64 == 32: the last step's second half is zero codes and no X)
           x[i][2] = reinterpret_cast<const float4*>(p + 32)[0];
           x[i][3] = reinterpret_cast<const float4*>(p + 32)[1];
         }
@@ -284,10 +177,64 @@ __global__ __launch_bounds__(NW * 64) void k_w8_sk(W8Args a, int S, float* ws, i
       }
     }
   }
+}
+
+// ---- general form: workgroup u = output tile u (SW: the (gate, up) pair 2u, 2u + 1); wave w takes the code steps
+// [KK w / NW, KK (w + 1) / NW), U of them (per tile) in flight
+template <int NW, bool SW>
+__global__ __launch_bounds__(NW * 64) void k_w8(W8Args a) {
+  constexpr int T = SW ? 2 : 1, U = SW ? 2 : 4;   // (4 pair steps spill at 16 waves' 128 VGPRs)
+  __shared__ float part[NW][T][16][17];
+  __shared__ float rstd_s[16];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int u = blockIdx.x;
+  const __amdgpu_buffer_rsrc_t srd = rsrc_of(a.Q, a.ntiles * a.KK * 1024);
+  const int kb = (int)((long)a.KK * wave / NW), ke = (int)((long)a.KK * (wave + 1) / NW);
+  const int row = min(lane & 15, a.M - 1);
+  const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
+  const int voff = lane * 16;
+  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
+  f32x4 acc[T];
+  w8_accumulate<T, U>(a, srd, xp, voff, T * u, kb, ke, acc);
 #pragma unroll
-  for (int t = 0; t < NT; ++t)
+  for (int t = 0; t < T; ++t) w8_store_tile(part[wave][t], acc[t], lane);
+  __syncthreads();
+  const int e = threadIdx.x;
+  if (e < 256) {
+    const int rr = e >> 4, c = e & 15;
+    float x1 = 0.f, x2 = 0.f;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) part[wave][t][4 * (lane >> 4) + i][lane & 15] = acc[t][i];
+    for (int w = 0; w < NW; ++w) {
+      x1 += part[w][0][rr][c];
+      if constexpr (SW) x2 += part[w][1][rr][c];
+    }
+    w8_epilogue<SW>(a, u, gridDim.x, rr, c, x1, x2, rstd_s);
+  }
+}
+
+// ---- long-K plain form: workgroup (tg, sp) = tiles NT tg .. + NT over the sp-th of S slices of the code steps, the
+// slice split over the waves as in k_w8.  ws: S slabs of [16][groups * NT * 16] partial sums; counters: one zeroed
+// ticket per tile group, left zeroed.  The hand-off is fo_common.h's (st_wt / ld_sc1): no fences, no waiting.
+template <int NW, int NT>
+__global__ __launch_bounds__(NW * 64) void k_w8_sk(W8Args a, int S, float* ws, int* counters) {
+  constexpr int U = 2;
+  __shared__ float part[NW][NT][16][17];
+  __shared__ float red[NT][16][17];
+  __shared__ float rstd_s[16];
+  __shared__ int last_s;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int tg = blockIdx.x, sp = blockIdx.y;
+  const __amdgpu_buffer_rsrc_t srd = rsrc_of(a.Q, a.ntiles * a.KK * 1024);
+  const int k_lo = (int)((long)a.KK * sp / S), k_n = (int)((long)a.KK * (sp + 1) / S) - k_lo;
+  const int kb = k_lo + (int)((long)k_n * wave / NW), ke = k_lo + (int)((long)k_n * (wave + 1) / NW);
+  const int row = min(lane & 15, a.M - 1);
+  const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
+  const int voff = lane * 16;
+  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
+  f32x4 acc[NT];
+  w8_accumulate<NT, U>(a, srd, xp, voff, NT * tg, kb, ke, acc);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) w8_store_tile(part[wave][t], acc[t], lane);
   __syncthreads();
   constexpr int NE = NT * 256, NTH = NW * 64;
   for (int e = threadIdx.x; e < NE; e += NTH) {
@@ -336,7 +283,9 @@ __global__ __launch_bounds__(NW * 64) void k_w8_sk(W8Args a, int S, float* ws, i
   }
 }
 
-// ---- X-stationary persistent form: the SwiGLU pair, K = NW * KPW * 64 (3584 = 56 code steps)
+// ---- X-stationary persistent form, as k_gemm_xs (fo_gemm.hip): the SwiGLU pair, K = NW * KPW * 64 (3584 = 56 code
+// steps).  X hi in registers, lo in LDS, units dealt evenly to at most one workgroup per CU, the next unit's codes
+// issued before the current one is reduced, a fixed-order cross-wave reduction.
 template <int NW, int KPW>
 __global__ __launch_bounds__(NW * 64) void k_w8_xs(W8Args a, int units) {
   __shared__ bf16x8 xlo[NW][2 * KPW][64];
@@ -346,7 +295,7 @@ __global__ __launch_bounds__(NW * 64) void k_w8_xs(W8Args a, int units) {
   constexpr int KK = NW * KPW;
   const int ub = (int)((long)units * blockIdx.x / gridDim.x);
   const int ue = (int)((long)units * (blockIdx.x + 1) / gridDim.x);
-  const __amdgpu_buffer_rsrc_t srd = code_rsrc(a);
+  const __amdgpu_buffer_rsrc_t srd = rsrc_of(a.Q, a.ntiles * a.KK * 1024);   // (exactly the codes)
   const int voff = (wave * KPW * 64 + lane) * 16;
   u32x4 q0[KPW], q1[KPW];
   auto issue = [&](u32x4 (&q)[KPW], int tile) {
@@ -384,18 +333,15 @@ __global__ __launch_bounds__(NW * 64) void k_w8_xs(W8Args a, int units) {
   };
   for (int u = ub; u < ue; ++u) {
     // the next unit's codes are issued unconditionally; past the last unit they address tile `ntiles`, beyond the
-    // descriptor's range (code_rsrc), which the hardware drops without touching memory
+    // descriptor's range, which the hardware drops without touching memory
     const int nxt = u + 1 < ue ? 2 * (u + 1) : a.ntiles;
     const f32x4 c0 = compute(q0);
     issue(q0, nxt);
     const f32x4 c1 = compute(q1);
     issue(q1, nxt + (u + 1 < ue ? 1 : 0));
     __syncthreads();  // the previous unit's epilogue has read part[]
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      part[wave][0][4 * (lane >> 4) + i][lane & 15] = c0[i];
-      part[wave][1][4 * (lane >> 4) + i][lane & 15] = c1[i];
-    }
+    w8_store_tile(part[wave][0], c0, lane);
+    w8_store_tile(part[wave][1], c1, lane);
     __syncthreads();
     const int e = threadIdx.x;
     if (e < 256) {
@@ -432,7 +378,7 @@ __global__ __launch_bounds__(NW * 64) void k_w8_rows(W8Args a, int S, int per, f
   const int G = gridDim.x, g = blockIdx.x, sp = blockIdx.y;
   const int units = (a.ntiles + 1) >> 1, tiles = (a.N + 15) / 16;   // (tiles: output tiles, the statistics' groups)
   const int ub = (int)((long)units * g / G), ue = (int)((long)units * (g + 1) / G);
-  const __amdgpu_buffer_rsrc_t srd = code_rsrc(a);
+  const __amdgpu_buffer_rsrc_t srd = rsrc_of(a.Q, a.ntiles * a.KK * 1024);   // (exactly the codes)
   // this wave's code steps: [k0, k0 + nj) inside the slice [sp * per, (sp + 1) * per) and inside KK (wave-uniform)
   const int k0 = sp * per + wave * KPW;
   const int nj = max(0, min(KPW, min(a.KK, (sp + 1) * per) - k0));
@@ -476,14 +422,7 @@ __global__ __launch_bounds__(NW * 64) void k_w8_rows(W8Args a, int S, int per, f
     }
   }
   if (S == 1) {   // the consumer's rstd of every row (rows >= M from the clamped row)
-    if (a.rstats)
-      for (int rr = wave; rr < ROWS; rr += NW) {
-        const int m = min(rr, a.M - 1);
-        float v = 0.f;
-        for (int j = lane; j < a.rgroups; j += 64) v += a.rstats[(size_t)m * a.rgroups + j];
-        v = wave_sum(v);
-        if (lane == 0) rstd_s[rr] = rsqrtf(v / (float)a.K + a.reps);
-      }
+    if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane, 0, ROWS);
     __syncthreads();
   }
   const int Ncols = a.ntiles * 16;
@@ -514,9 +453,7 @@ __global__ __launch_bounds__(NW * 64) void k_w8_rows(W8Args a, int S, int per, f
 #pragma unroll
       for (int p = 0; p < PT; ++p)
 #pragma unroll
-        for (int r = 0; r < RB; ++r)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) part[wave][p][r * 16 + 4 * (lane >> 4) + i][lane & 15] = acc[p][r][i];
+        for (int r = 0; r < RB; ++r) w8_store_tile(part[wave][p], acc[p][r], lane, r * 16);
       __syncthreads();
 #pragma unroll
       for (int p = 0; p < PT; ++p)
@@ -553,9 +490,9 @@ __global__ __launch_bounds__(NW * 64) void k_w8_rows(W8Args a, int S, int per, f
   }
 }
 
-// The merge of k_w8_rows's (and k_w8_rows128's) slabs: workgroup (u, rb) = output tile u (SW: the (gate, up) pair) x row block rb, thread
-// 16 rr + c one element: every split's partial summed in split order (8 loads in flight; a missing split adds 0),
-// then the epilogue.
+// The merge of k_w8_rows's (and k_w8_rows128's) slabs: workgroup (u, rb) = output tile u (SW: the (gate, up) pair) x
+// row block rb, thread 16 rr + c one element: every split's partial summed in split order (8 loads in flight; a
+// missing split adds 0), then the epilogue.
 template <bool SW>
 __global__ __launch_bounds__(256) void k_w8_rows_merge(W8Args a, int S, const float* ws, int rows) {
   constexpr int T = SW ? 2 : 1;
@@ -563,13 +500,7 @@ __global__ __launch_bounds__(256) void k_w8_rows_merge(W8Args a, int S, const fl
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int u = blockIdx.x, rb = blockIdx.y;
   if (a.rstats) {
-    for (int r = wave; r < 16; r += 4) {
-      const int m = min(rb * 16 + r, a.M - 1);
-      float v = 0.f;
-      for (int j = lane; j < a.rgroups; j += 64) v += a.rstats[(size_t)m * a.rgroups + j];
-      v = wave_sum(v);
-      if (lane == 0) rstd_s[rb * 16 + r] = rsqrtf(v / (float)a.K + a.reps);
-    }
+    w8_rstd<4>(a, rstd_s, wave, lane, rb * 16, 16);
     __syncthreads();
   }
   const int rr = rb * 16 + (threadIdx.x >> 4), c = threadIdx.x & 15;
@@ -809,6 +740,40 @@ int w8_cus() {
   return g_cus;
 }
 
+// What the three GEMM entries share: the checks of everything but the workspace (all before the entry's first HIP
+// call), then W8Args (with KK) and the output tile count.  `fn` is the entry's name, [m_lo, m_hi] its row band and
+// `serves` what its refusal says of the band.
+int w8_args(const char* fn, int m_lo, int m_hi, const char* serves, const float* X, int ldx, int M, int K, const void* Q,
+            const float* scale, int ntiles, int N, int swiglu, float* Y, int ldy, int residual, const float* rstats,
+            int rgroups, float eps, float* sout, const float* gnext, float* yg, W8Args& a, int& units) {
+  FO_REQUIRE(M > 0 && N > 0 && K > 0, "%s: bad shape M=%d N=%d K=%d", fn, M, N, K);
+  FO_REQUIRE(M >= m_lo && M <= m_hi, "%s: M=%d rows, %s", fn, M, serves);
+  FO_REQUIRE((K & 31) == 0, "%s: K=%d must be a multiple of 32", fn, K);
+  FO_REQUIRE(X && Q && Y, "%s: NULL X, Q or Y", fn);
+  FO_REQUIRE(scale, "%s: NULL scale (the per-column 2^e of fo_quant_w8)", fn);
+  FO_REQUIRE(ldx >= K && (ldx & 3) == 0 && ((unsigned long long)X & 15) == 0,
+             "%s: X needs ldx=%d >= K=%d, ldx %% 4 == 0 and 16-byte alignment", fn, ldx, K);
+  FO_REQUIRE(ldy >= N, "%s: ldy=%d < N=%d", fn, ldy, N);
+  units = (N + 15) / 16;
+  // ntiles is the extent of Q and scale (the code descriptor's range): (gate, up) pairs for SwiGLU
+  FO_REQUIRE(ntiles == (swiglu ? 2 : 1) * units, "%s: ntiles=%d packed tiles for N=%d%s", fn, ntiles, N,
+             swiglu ? " SwiGLU columns" : " columns");
+  FO_REQUIRE(!rstats || rgroups > 0, "%s: rstats without rgroups", fn);
+  FO_REQUIRE(!sout || (!swiglu && (!yg || gnext)), "%s: sout needs a non-SwiGLU launch, yg needs gnext", fn);
+  FO_REQUIRE(sout || !yg, "%s: yg comes with sout", fn);
+  FO_REQUIRE(!(swiglu && residual), "%s: swiglu with residual unsupported", fn);
+  const int KK = (K + 63) / 64;
+  FO_REQUIRE((long long)(ntiles + 4) * KK * 1024 < (1ll << 31), "%s: ntiles=%d x K=%d codes exceed 2 GiB", fn, ntiles, K);
+  a = W8Args{X, Q, scale, Y, ldx, ldy, M, K, N, ntiles, KK, residual, sout, gnext, yg, rstats, rgroups, eps};
+  return 0;
+}
+
+// k_w8_rows_merge over the S slabs of RB row blocks in `ws`
+void launch_merge(const W8Args& a, int swiglu, int units, int RB, int S, const float* ws, hipStream_t stream) {
+  if (swiglu) hipLaunchKernelGGL((k_w8_rows_merge<true>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
+  else hipLaunchKernelGGL((k_w8_rows_merge<false>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
+}
+
 }  // namespace
 
 extern "C" {
@@ -830,45 +795,15 @@ int fo_quant_w8(const void* W, int src_bf16, int N, int K, int ldw, void* q, flo
 int fo_gemm_w8(const float* X, int ldx, int M, int K, const void* Q, const float* scale, int ntiles, int N, int swiglu,
                float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters, const float* rstats,
                int rgroups, float eps, float* sout, const float* gnext, float* yg, int* sgroups, hipStream_t stream) {
-  FO_REQUIRE(M > 0 && N > 0 && K > 0, "fo_gemm_w8: bad shape M=%d N=%d K=%d", M, N, K);
-  FO_REQUIRE(M <= 16, "fo_gemm_w8: M=%d rows, the FP8 stream serves M <= 16 (more rows run the bf16 image)", M);
-  FO_REQUIRE((K & 31) == 0, "fo_gemm_w8: K=%d must be a multiple of 32", K);
-  FO_REQUIRE(X && Q && Y, "fo_gemm_w8: NULL X, Q or Y");
-  FO_REQUIRE(scale, "fo_gemm_w8: NULL scale (the per-column 2^e of fo_quant_w8)");
-  FO_REQUIRE(ldx >= K && (ldx & 3) == 0 && ((unsigned long long)X & 15) == 0,
-             "fo_gemm_w8: X needs ldx=%d >= K=%d, ldx %% 4 == 0 and 16-byte alignment", ldx, K);
-  FO_REQUIRE(ldy >= N, "fo_gemm_w8: ldy=%d < N=%d", ldy, N);
-  const int units = (N + 15) / 16;
-  // ntiles is the extent of Q and scale (the code descriptor's range): (gate, up) pairs for SwiGLU
   FO_REQUIRE(!swiglu || (ntiles & 1) == 0, "fo_gemm_w8: swiglu with an odd ntiles=%d (gate/up tiles come in pairs)",
              ntiles);
-  FO_REQUIRE(ntiles == (swiglu ? 2 : 1) * units, "fo_gemm_w8: ntiles=%d packed tiles for N=%d%s", ntiles, N,
-             swiglu ? " SwiGLU columns" : " columns");
-  FO_REQUIRE(!rstats || rgroups > 0, "fo_gemm_w8: rstats without rgroups");
-  FO_REQUIRE(!sout || (!swiglu && (!yg || gnext)), "fo_gemm_w8: sout needs a non-SwiGLU launch, yg needs gnext");
-  FO_REQUIRE(sout || !yg, "fo_gemm_w8: yg comes with sout");
-  FO_REQUIRE(!(swiglu && residual), "fo_gemm_w8: swiglu with residual unsupported");
-  const int KK = (K + 63) / 64;
-  FO_REQUIRE((long long)(ntiles + 4) * KK * 1024 < (1ll << 31), "fo_gemm_w8: ntiles=%d x K=%d codes exceed 2 GiB", ntiles, K);
   W8Args a;
-  a.X = X;
-  a.Q = Q;
-  a.scale = scale;
-  a.Y = Y;
-  a.ldx = ldx;
-  a.ldy = ldy;
-  a.M = M;
-  a.K = K;
-  a.N = N;
-  a.ntiles = ntiles;
-  a.KK = KK;
-  a.residual = residual;
-  a.sout = sout;
-  a.gnext = gnext;
-  a.yg = yg;
-  a.rstats = rstats;
-  a.rgroups = rgroups;
-  a.reps = eps;
+  int units;
+  if (const int rc = w8_args("fo_gemm_w8", 1, 16, "the FP8 stream serves M <= 16 (more rows run the bf16 image)", X, ldx,
+                             M, K, Q, scale, ntiles, N, swiglu, Y, ldy, residual, rstats, rgroups, eps, sout, gnext, yg,
+                             a, units))
+    return rc;
+  const int KK = a.KK;
   if (sgroups) *sgroups = units;
   if (swiglu && K == 3584) {
     const int G = units < w8_cus() ? units : w8_cus();
@@ -910,45 +845,15 @@ int fo_gemm_w8_rows(const float* X, int ldx, int M, int K, const void* Q, const 
                     int swiglu, float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters,
                     const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
                     int* sgroups, hipStream_t stream) {
-  FO_REQUIRE(M > 0 && N > 0 && K > 0, "fo_gemm_w8_rows: bad shape M=%d N=%d K=%d", M, N, K);
-  FO_REQUIRE(M >= 17 && M <= 64,
-             "fo_gemm_w8_rows: M=%d rows, this FP8 stream serves 17 <= M <= 64 (fo_gemm_w8 serves M <= 16, more than "
-             "64 rows run the bf16 image)", M);
-  FO_REQUIRE((K & 31) == 0, "fo_gemm_w8_rows: K=%d must be a multiple of 32", K);
-  FO_REQUIRE(X && Q && Y, "fo_gemm_w8_rows: NULL X, Q or Y");
-  FO_REQUIRE(scale, "fo_gemm_w8_rows: NULL scale (the per-column 2^e of fo_quant_w8)");
-  FO_REQUIRE(ldx >= K && (ldx & 3) == 0 && ((unsigned long long)X & 15) == 0,
-             "fo_gemm_w8_rows: X needs ldx=%d >= K=%d, ldx %% 4 == 0 and 16-byte alignment", ldx, K);
-  FO_REQUIRE(ldy >= N, "fo_gemm_w8_rows: ldy=%d < N=%d", ldy, N);
-  const int units = (N + 15) / 16;
-  FO_REQUIRE(ntiles == (swiglu ? 2 : 1) * units, "fo_gemm_w8_rows: ntiles=%d packed tiles for N=%d%s", ntiles, N,
-             swiglu ? " SwiGLU columns" : " columns");
-  FO_REQUIRE(!rstats || rgroups > 0, "fo_gemm_w8_rows: rstats without rgroups");
-  FO_REQUIRE(!sout || (!swiglu && (!yg || gnext)), "fo_gemm_w8_rows: sout needs a non-SwiGLU launch, yg needs gnext");
-  FO_REQUIRE(sout || !yg, "fo_gemm_w8_rows: yg comes with sout");
-  FO_REQUIRE(!(swiglu && residual), "fo_gemm_w8_rows: swiglu with residual unsupported");
-  const int KK = (K + 63) / 64;
-  FO_REQUIRE((long long)(ntiles + 4) * KK * 1024 < (1ll << 31), "fo_gemm_w8_rows: ntiles=%d x K=%d codes exceed 2 GiB",
-             ntiles, K);
   W8Args a;
-  a.X = X;
-  a.Q = Q;
-  a.scale = scale;
-  a.Y = Y;
-  a.ldx = ldx;
-  a.ldy = ldy;
-  a.M = M;
-  a.K = K;
-  a.N = N;
-  a.ntiles = ntiles;
-  a.KK = KK;
-  a.residual = residual;
-  a.sout = sout;
-  a.gnext = gnext;
-  a.yg = yg;
-  a.rstats = rstats;
-  a.rgroups = rgroups;
-  a.reps = eps;
+  int units;
+  if (const int rc = w8_args("fo_gemm_w8_rows", 17, 64,
+                             "this FP8 stream serves 17 <= M <= 64 (fo_gemm_w8 serves M <= 16, more than 64 rows run the "
+                             "bf16 image)",
+                             X, ldx, M, K, Q, scale, ntiles, N, swiglu, Y, ldy, residual, rstats, rgroups, eps, sout,
+                             gnext, yg, a, units))
+    return rc;
+  const int KK = a.KK;
   // NW waves x KPW code steps of X per K slice (hi in VGPRs, lo in LDS): 7 x 4 at 2 row blocks, 7 x 2 at 3 and 6 x 2
   // at 4, the largest slices whose LDS still holds both tiles of a unit in one reduction round (7 x 3 at 3 row blocks
   // reduced a tile at a time and measured 63.8 against 58.1 us on gate/up at 48 rows, 7 x 2 at 4 row blocks 48.7
@@ -982,8 +887,7 @@ int fo_gemm_w8_rows(const float* X, int ldx, int M, int K, const void* Q, const 
   if (S > 1) {
     const int rc = fo::check_launch("fo_gemm_w8_rows");
     if (rc) return rc;
-    if (swiglu) hipLaunchKernelGGL((k_w8_rows_merge<true>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
-    else hipLaunchKernelGGL((k_w8_rows_merge<false>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
+    launch_merge(a, swiglu, units, RB, S, ws, stream);
   }
   fo::count_launch(FO_L_GEMM_W8_ROWS);
   return fo::check_launch("fo_gemm_w8_rows");
@@ -993,46 +897,15 @@ int fo_gemm_w8_rows128(const float* X, int ldx, int M, int K, const void* Q, con
                        int swiglu, float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters,
                        const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
                        int* sgroups, hipStream_t stream) {
-  FO_REQUIRE(M > 0 && N > 0 && K > 0, "fo_gemm_w8_rows128: bad shape M=%d N=%d K=%d", M, N, K);
-  FO_REQUIRE(M >= 65 && M <= 128,
-             "fo_gemm_w8_rows128: M=%d rows, this FP8 stream serves 65 <= M <= 128 (fo_gemm_w8 serves M <= 16, "
-             "fo_gemm_w8_rows 17..64, more than 128 rows run the bf16 image)", M);
-  FO_REQUIRE((K & 31) == 0, "fo_gemm_w8_rows128: K=%d must be a multiple of 32", K);
-  FO_REQUIRE(X && Q && Y, "fo_gemm_w8_rows128: NULL X, Q or Y");
-  FO_REQUIRE(scale, "fo_gemm_w8_rows128: NULL scale (the per-column 2^e of fo_quant_w8)");
-  FO_REQUIRE(ldx >= K && (ldx & 3) == 0 && ((unsigned long long)X & 15) == 0,
-             "fo_gemm_w8_rows128: X needs ldx=%d >= K=%d, ldx %% 4 == 0 and 16-byte alignment", ldx, K);
-  FO_REQUIRE(ldy >= N, "fo_gemm_w8_rows128: ldy=%d < N=%d", ldy, N);
-  const int units = (N + 15) / 16;
-  FO_REQUIRE(ntiles == (swiglu ? 2 : 1) * units, "fo_gemm_w8_rows128: ntiles=%d packed tiles for N=%d%s", ntiles, N,
-             swiglu ? " SwiGLU columns" : " columns");
-  FO_REQUIRE(!rstats || rgroups > 0, "fo_gemm_w8_rows128: rstats without rgroups");
-  FO_REQUIRE(!sout || (!swiglu && (!yg || gnext)),
-             "fo_gemm_w8_rows128: sout needs a non-SwiGLU launch, yg needs gnext");
-  FO_REQUIRE(sout || !yg, "fo_gemm_w8_rows128: yg comes with sout");
-  FO_REQUIRE(!(swiglu && residual), "fo_gemm_w8_rows128: swiglu with residual unsupported");
-  const int KK = (K + 63) / 64;
-  FO_REQUIRE((long long)(ntiles + 4) * KK * 1024 < (1ll << 31),
-             "fo_gemm_w8_rows128: ntiles=%d x K=%d codes exceed 2 GiB", ntiles, K);
   W8Args a;
-  a.X = X;
-  a.Q = Q;
-  a.scale = scale;
-  a.Y = Y;
-  a.ldx = ldx;
-  a.ldy = ldy;
-  a.M = M;
-  a.K = K;
-  a.N = N;
-  a.ntiles = ntiles;
-  a.KK = KK;
-  a.residual = residual;
-  a.sout = sout;
-  a.gnext = gnext;
-  a.yg = yg;
-  a.rstats = rstats;
-  a.rgroups = rgroups;
-  a.reps = eps;
+  int units;
+  if (const int rc = w8_args("fo_gemm_w8_rows128", 65, 128,
+                             "this FP8 stream serves 65 <= M <= 128 (fo_gemm_w8 serves M <= 16, fo_gemm_w8_rows 17..64, "
+                             "more than 128 rows run the bf16 image)",
+                             X, ldx, M, K, Q, scale, ntiles, N, swiglu, Y, ldy, residual, rstats, rgroups, eps, sout,
+                             gnext, yg, a, units))
+    return rc;
+  const int KK = a.KK;
   // The plan of k_gemm_rows (fo_gemm.hip plan_rows).  A workgroup's X over its K slice (512 B per column at 128 rows)
   // passes through its CU beside its codes (16 B per tile and column), so the tiles per workgroup are as many as the
   // accumulators and the LDS ring allow and K is split until the grid is about one workgroup per CU: SwiGLU K thirds
@@ -1072,8 +945,7 @@ int fo_gemm_w8_rows128(const float* X, int ldx, int M, int K, const void* Q, con
 #undef FO_W8_ROWS128
   const int rc = fo::check_launch("fo_gemm_w8_rows128");
   if (rc) return rc;
-  if (swiglu) hipLaunchKernelGGL((k_w8_rows_merge<true>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
-  else hipLaunchKernelGGL((k_w8_rows_merge<false>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
+  launch_merge(a, swiglu, units, RB, S, ws, stream);
   fo::count_launch(FO_L_GEMM_W8_ROWS128);
   return fo::check_launch("fo_gemm_w8_rows128 (merge)");
 }

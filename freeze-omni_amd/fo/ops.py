@@ -143,6 +143,20 @@ def _check_dev(t):
         raise RuntimeError("Freeze-Omni MI355X kernels take device tensors only (no CPU fallback)")
 
 
+def _norm_args(norm, stats_out=None, out=None):
+    """A GEMM call's norm = (RowStats, eps) and stats_out = RowStats (PackedLinear.__call__) as the C-ABI's
+    (rstats, rgroups, eps, sout, gnext, yg); `out` is the output stats_out's yg goes beside."""
+    rst, rg, eps = (None, 0, 0.0) if norm is None else (norm[0].buf.data_ptr(), norm[0].groups, float(norm[1]))
+    if norm is not None and rg <= 0:
+        raise RuntimeError("RowStats consumed before any GEMM produced them")
+    so = gn = yg = None
+    if stats_out is not None:
+        so, gn, yg = stats_out.buf.data_ptr(), stats_out.gamma.data_ptr(), stats_out.yg.data_ptr()
+        if stats_out.yg.stride(0) != out.stride(0):
+            raise ValueError("yg must share the output's row stride")
+    return rst, rg, eps, so, gn, yg
+
+
 class PackedLinear:
     """A linear layer's weight packed into MFMA fragment order (fo_pack_weight).
 
@@ -274,9 +288,7 @@ class PackedLinear:
         if x.stride(-1) != 1 or x.shape[-1] < self.Kp or x.dtype not in (F32, BF16):
             raise ValueError("qkv_rope input needs unit stride, fp32/bf16 and >= Kp columns")
         rt = Runtime.get(x.device)
-        rst, rg, eps = (None, 0, 0.0) if norm is None else (norm[0].buf.data_ptr(), norm[0].groups, float(norm[1]))
-        if norm is not None and rg <= 0:
-            raise RuntimeError("RowStats consumed before any GEMM produced them")
+        rst, rg, eps = _norm_args(norm)[:3]
         kvb = kv_bytes(kc, vc)
         with _packed(xpack, None):
             _lib.call("fo_gemm_qkv_rope_kv", x.data_ptr(), 1 if x.dtype == F32 else 0, x.stride(0), M, self.Kp,
@@ -295,14 +307,7 @@ class PackedLinear:
         if out is None:
             out = torch.empty(M, self.N, dtype=F32, device=x.device)
         rt = Runtime.get(x.device)
-        rst, rg, eps = (None, 0, 0.0) if norm is None else (norm[0].buf.data_ptr(), norm[0].groups, float(norm[1]))
-        if norm is not None and rg <= 0:
-            raise RuntimeError("RowStats consumed before any GEMM produced them")
-        so = gn = yg = None
-        if stats_out is not None:
-            so, gn, yg = stats_out.buf.data_ptr(), stats_out.gamma.data_ptr(), stats_out.yg.data_ptr()
-            if stats_out.yg.stride(0) != out.stride(0):
-                raise ValueError("yg must share the output's row stride")
+        rst, rg, eps, so, gn, yg = _norm_args(norm, stats_out, out)
         sg = ctypes.c_int(0)
         if ypack is not None and stats_out is None:
             raise ValueError("ypack packs the stats_out yg: pass stats_out")
@@ -322,7 +327,7 @@ class PackedLinear:
 # (ceil(rows / 16)) at which fo_gemm_w8_rows beat the bf16 image by more than that arm's spread -- for the down, by
 # more than the packed input it costs the next q|k|v as well (scripts/gemm_w8_rows_ab.py,
 # profiles/mlp_fp8_rows_gemm_ab.txt).  Row blocks 5..8 (65..128 rows, stream_rows=128, fo_gemm_w8_rows128)
-# enter by the same rule (scripts/gemm_w8_rows128_ab.py, profiles/mlp_fp8_rows128_gemm_ab.txt): none did -- the FP8 arm
+# enter by the same rule (scripts/gemm_w8_rows_ab.py --band 128, profiles/mlp_fp8_rows128_gemm_ab.txt): none did -- the FP8 arm
 # lost at every pair, gate/up 1.13-1.20x and down 1.15-1.23x -- so 65..128 rows stay on the image.  The one place the
 # policy lives.
 W8_ROWS_POLICY = {"gate_up": (2, 3, 4), "down": (2,)}
@@ -365,13 +370,7 @@ class PackedLinearW8:
         self.bf16 = PackedLinear(dq[0], swiglu_up=dq[1] if self.swiglu else None)
 
     def _quant(self, w, base, stride):
-        if w.dtype not in (BF16, F32):
-            w = w.float()
-        w = w.contiguous()
-        dq = torch.empty(self.N, self.K, dtype=BF16, device=w.device)
-        _lib.call("fo_quant_w8", w.data_ptr(), 1 if w.dtype == BF16 else 0, self.N, self.K, self.K, self.q.data_ptr(),
-                  self.scales.data_ptr(), dq.data_ptr(), base, stride, stream(w.device))
-        return dq
+        return _quant_w8(w, self.q, self.scales, base, stride)
 
     @property
     def packed(self):
@@ -403,17 +402,10 @@ class PackedLinearW8:
             raise ValueError(f"PackedLinearW8 input needs unit stride and >= {self.Kp} columns, got {tuple(x.shape)}")
         if out is None:
             out = torch.empty(rows, self.N, dtype=F32, device=x.device)
-        rst, rg, eps = (None, 0, 0.0) if norm is None else (norm[0].buf.data_ptr(), norm[0].groups, float(norm[1]))
-        if norm is not None and rg <= 0:
-            raise RuntimeError("RowStats consumed before any GEMM produced them")
-        so = gn = yg = None
-        if stats_out is not None:
-            so, gn, yg = stats_out.buf.data_ptr(), stats_out.gamma.data_ptr(), stats_out.yg.data_ptr()
-            if stats_out.yg.stride(0) != out.stride(0):
-                raise ValueError("yg must share the output's row stride")
-            if (self.N + 15) // 16 > stats_out.max_groups:
-                raise RuntimeError(f"RowStats holds {stats_out.max_groups} groups per row, fo_gemm_w8 writes "
-                                   f"{(self.N + 15) // 16}")
+        rst, rg, eps, so, gn, yg = _norm_args(norm, stats_out, out)
+        if stats_out is not None and (self.N + 15) // 16 > stats_out.max_groups:
+            raise RuntimeError(f"RowStats holds {stats_out.max_groups} groups per row, fo_gemm_w8 writes "
+                               f"{(self.N + 15) // 16}")
         sg = ctypes.c_int(0)
         rt = Runtime.get(x.device)
         # (x is read as fp32 rows and the output is written row-major only: xpack / ypack stay untouched)
@@ -427,15 +419,27 @@ class PackedLinearW8:
         return out
 
 
+def _quant_w8(w, q, scales, base, stride):
+    """fo_quant_w8 of the [N, K] weight w into packed tiles base, base + stride, ... of q / scales; returns the
+    dequantised weight (bf16 [N, K])."""
+    if w.dtype not in (BF16, F32):
+        w = w.float()
+    w = w.contiguous()
+    N, K = w.shape
+    dq = torch.empty(N, K, dtype=BF16, device=w.device)
+    _lib.call("fo_quant_w8", w.data_ptr(), 1 if w.dtype == BF16 else 0, N, K, K, q.data_ptr(), scales.data_ptr(),
+              dq.data_ptr(), base, stride, stream(w.device))
+    return dq
+
+
 def quant_w8(w):
     """fo_quant_w8 of one [N, K] device weight (bf16 or fp32) -> (packed codes uint8, packed scales fp32 [tiles * 16],
     dequantised weight bf16 [N, K]); the CPU reference is fo.quant.quantize_rows_e4m3."""
-    p = PackedLinearW8.__new__(PackedLinearW8)
-    p.N, p.K = w.shape
-    nt = (p.N + 15) // 16
-    p.q = torch.empty(nt * ((p.K + 63) // 64) * 1024, dtype=torch.uint8, device=w.device)
-    p.scales = torch.empty(nt * 16, dtype=F32, device=w.device)
-    return p.q, p.scales, p._quant(w, 0, 1)
+    N, K = w.shape
+    nt = (N + 15) // 16
+    q = torch.empty(nt * ((K + 63) // 64) * 1024, dtype=torch.uint8, device=w.device)
+    scales = torch.empty(nt * 16, dtype=F32, device=w.device)
+    return q, scales, _quant_w8(w, q, scales, 0, 1)
 
 
 # FO_XPACK=0 turns the packed <= 64-row activations off (A/B only)

@@ -196,30 +196,27 @@ int fo_launch_counts_reset(void);
  *   to packed tile tile_base + t * tile_stride of q and scale (gate at base 0 and up at base 1 with stride 2
  *   interleave the SwiGLU pair, as fo_pack_weight); wdq (optional) receives the dequantised W' as bf16 [N][K]
  *   (contiguous), from which fo_pack_weight builds the bf16 image.
- * fo_gemm_w8: Y = X . W'^T for fp32 X (split into bf16 hi + lo) of M <= 16 rows, K % 32 == 0, fp32 Y; ntiles is the
- *   packed tile count of q / scale (ceil(N/16), twice that with swiglu).  Epilogues, with fo_gemm_rms's semantics:
- *   plain, + Y (residual), swiglu (Y = silu(s_g g) * (s_u u)), the RMSNorm consumer (rstats / rgroups / eps) and
- *   producer (sout, gnext, yg; *sgroups = ceil(N/16) groups per row).  The column scale multiplies the fp32 sum
- *   before anything else.  It has no bias, affine, activation, bf16 output, RoPE, LayerNorm-on-load or packed X / Y;
- *   those and M > 16 run the bf16 image through fo_gemm.  ws / ws_floats / counters (fo_gemm's: scratch floats and
- *   zeroed ints, left zeroed; may be NULL) let long-K plain launches (the Qwen2 down) split K across workgroups and
- *   merge inside the launch, the partials summed in split order: deterministic in every form.
- * fo_gemm_w8_rows: the same product, arguments and epilogues for 17 <= M <= 64 rows (any other M is refused on the
- *   host), any K % 32 == 0 and any N, SwiGLU or plain: X stationary per K slice (k_w8_rows), K split over workgroups
- *   whenever it exceeds one slice (28 / 14 / 12 code steps at 2 / 3 / 4 row blocks of 16).  A split launch needs ws
- *   (slices x 16 ceil(M/16) x 16 ntiles floats, checked against ws_floats) and is followed by a second launch
- *   (k_w8_rows_merge) that sums the slices' partial sums in slice order and runs the epilogue: deterministic.
- *   counters is accepted for fo_gemm_w8's signature and not used.  Rows >= M are neither stored nor summed.  It reads
- *   fp32 rows and writes row-major Y / yg only (no packed X / Y).  Both launches are capture-safe; one call counts
- *   one FO_L_GEMM_W8_ROWS.
- * fo_gemm_w8_rows128: the same product, arguments and epilogues for 65 <= M <= 128 rows (any other M is refused on the
- *   host): k_gemm_rows's design on the codes (k_w8_rows128: the 8 waves of a workgroup split the row blocks and share
- *   each 64-column code step's fragments through an LDS-DMA ring; K split over workgroups, SwiGLU in up to 3 slices,
- *   plain in up to 16, never more than code steps).  Every call needs ws (slices x 16 ceil(M/16) x 16 ntiles floats,
- *   checked against ws_floats: a short one is refused with both figures, nothing launched) and is followed by
- *   k_w8_rows_merge, which sums the slices in slice order and runs the epilogue: deterministic.  counters is accepted
- *   and not used.  Rows >= M are neither stored nor summed.  Both launches are capture-safe; one call counts one
- *   FO_L_GEMM_W8_ROWS128. */
+ * fo_gemm_w8, fo_gemm_w8_rows, fo_gemm_w8_rows128: Y = X . W'^T for fp32 X (split into bf16 hi + lo), K % 32 == 0,
+ *   any N, fp32 Y, one entry per band of M (any other M is refused on the host); ntiles is the packed tile count of
+ *   q / scale (ceil(N/16), twice that with swiglu).  Epilogues, with fo_gemm_rms's semantics: plain, + Y (residual),
+ *   swiglu (Y = silu(s_g g) * (s_u u)), the RMSNorm consumer (rstats / rgroups / eps) and producer (sout, gnext, yg;
+ *   *sgroups = ceil(N/16) groups per row).  The column scale multiplies the fp32 sum before anything else; rows >= M
+ *   are neither stored nor summed.  No bias, affine, activation, bf16 output, RoPE, LayerNorm-on-load or packed X / Y:
+ *   those, and more rows than the caller's band, run the bf16 image through fo_gemm.  ws / ws_floats / counters are
+ *   fo_gemm's (scratch floats, and zeroed ints that are left zeroed).  Where K is split over workgroups the partial
+ *   sums are added in split order: deterministic in every form.  Every launch is capture-safe.
+ *   - fo_gemm_w8, M <= 16: one workgroup per output tile, its waves splitting K (k_w8); the SwiGLU pair at K = 3584
+ *     X-stationary and persistent (k_w8_xs, FO_L_GEMM_W8_XS); long-K plain launches (the Qwen2 down) split K across
+ *     workgroups and merge inside the launch where ws and counters are given (both may be NULL).  FO_L_GEMM_W8.
+ *   - fo_gemm_w8_rows, 17 <= M <= 64: X stationary per K slice (k_w8_rows), K split over workgroups whenever it
+ *     exceeds one slice (28 / 14 / 12 code steps at 2 / 3 / 4 row blocks of 16).  A split launch needs ws (slices x
+ *     16 ceil(M/16) x 16 ntiles floats, checked against ws_floats) and is followed by k_w8_rows_merge, which sums the
+ *     slices and runs the epilogue.  counters is not used.  One call counts one FO_L_GEMM_W8_ROWS.
+ *   - fo_gemm_w8_rows128, 65 <= M <= 128: k_gemm_rows's design on the codes (k_w8_rows128: the 8 waves of a
+ *     workgroup split the row blocks and share each code step's fragments through an LDS-DMA ring; SwiGLU in up to 3
+ *     K slices, plain in up to 16, never more than code steps).  Every call needs ws (as above: a short one is
+ *     refused with both figures, nothing launched) and is followed by k_w8_rows_merge.  counters is not used.  One
+ *     call counts one FO_L_GEMM_W8_ROWS128. */
 long long fo_quant_w8_bytes(int N, int K);
 int fo_quant_w8(const void* W, int src_bf16, int N, int K, int ldw, void* q, float* scale, void* wdq, int tile_base,
                 int tile_stride, hipStream_t stream);

@@ -1,21 +1,12 @@
 """fo_quant_w8 / fo_gemm_w8 (weight-only FP8 for <= 16 rows): the device quantiser against the CPU reference bit for
 bit, and the GEMM's epilogues against float64 on the DEQUANTISED weight -- the FP8 stream computes X . W'^T with the
 bf16 kernels' arithmetic, so the tolerances are those of tests/test_gemm_gpu.py."""
-import functools
-
 import pytest
 import torch
 
+from gemm_w8_ref import _weight
+
 pytestmark = pytest.mark.gpu
-
-
-@functools.lru_cache(maxsize=None)
-def _weight(N, K, seed):
-    """(bf16 weight, its dequantised FP8 image as float64), on the CPU, shared between the tests."""
-    from fo.quant import quantize_rows_e4m3
-    g = torch.Generator().manual_seed(seed)
-    w = (torch.randn(N, K, generator=g) / K ** 0.5).to(torch.bfloat16)
-    return w, quantize_rows_e4m3(w)[2].double()
 
 
 def _counts():
