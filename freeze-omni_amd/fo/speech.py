@@ -153,6 +153,23 @@ class EncoderCache:
 # fo_relpos_attention_fused launch per chunk (A/B)
 CHUNK_ATTN = os.environ.get("FO_ENC_CHUNK_ATTN", "1") != "0"
 
+ENC_MAX_T = 8   # encoder rows per chunk (dims): the kernels' limit
+
+
+def ring_geometry(chunk, left):
+    """(buffersize, full_chunk, max_len, cap) of the left-chunk ring (models/encoder/attention.py:83-88, :423-425):
+    the ring holds the kept frames and a chunk's new rows (<= ENC_MAX_T)."""
+    buffersize, full_chunk = chunk * left, (left + 1) * chunk
+    return buffersize, full_chunk, chunk * (5000 // chunk) - full_chunk, buffersize + ENC_MAX_T
+
+
+def pos_table_rows(max_len, full_chunk, buffersize, max_t=ENC_MAX_T):
+    """Rows of a layer's position table: one past the largest row host_meta can make a kernel read.  A launch reads
+    rows pstart .. pstart + len + T - 1 with pstart = max(0, pe - full_chunk) for any pe < max_len (pe_index is the
+    caller's and may have any residue), len up to a full ring (buffersize) and T up to max_t -- a few rows past
+    max_len once T > chunk + 1, which the reference computes on the fly (models/encoder/attention.py:105-121)."""
+    return max(max_len, max(0, max_len - 1 - full_chunk) + buffersize + max_t)
+
 
 class SpeechEncoderEngine:
     def __init__(self, src, cfg, ident, device, max_sessions=64):
@@ -169,10 +186,7 @@ class SpeechEncoderEngine:
         self.nb = tr["transformer-num-blocks"]
         self.chunk = tr["transformer-chunk_size"]
         self.left = tr["transformer-left_chunks"]
-        self.buffersize = self.chunk * self.left
-        self.full_chunk = (self.left + 1) * self.chunk
-        self.max_len = self.chunk * (5000 // self.chunk) - self.full_chunk
-        self.cap = self.buffersize + 8
+        self.buffersize, self.full_chunk, self.max_len, self.cap = ring_geometry(self.chunk, self.left)
         g = lambda n, dt=F32: src.get(p + n, dt)  # noqa: E731
         self.mean, self.istd = g("global_cmvn.mean"), g("global_cmvn.istd")
         # Conv2dSubsampling4 (fo_subsample): conv1 as a 9-tap fp32 stencil (bf16-valued weights, as the GEMMs see them),
@@ -187,8 +201,9 @@ class SpeechEncoderEngine:
         self.embed = PackedLinear(g("enc.1.embed.0.weight", torch.bfloat16), g("enc.1.embed.0.bias"))
         self.embed_ln = (g("enc.1.embed.1.weight"), g("enc.1.embed.1.bias"))
         self.after = (g("enc.1.after_norm.weight"), g("enc.1.after_norm.bias"))
-        sinus = tables.relpos_sinusoid(self.max_len, self.d).to(self.device)
-        self.ptab = torch.empty(self.nb, self.max_len, self.d, dtype=F32, device=self.device)
+        self.pos_rows = pos_table_rows(self.max_len, self.full_chunk, self.buffersize)
+        sinus = tables.relpos_sinusoid(self.pos_rows, self.d).to(self.device)
+        self.ptab = torch.empty(self.nb, self.pos_rows, self.d, dtype=F32, device=self.device)
         self.layers = []
         for i in range(self.nb):
             q = f"enc.1.encoders.{i}."
@@ -227,7 +242,7 @@ class SpeechEncoderEngine:
     def dims(self, R):
         H1, W1 = (R - 3) // 2 + 1, (80 - 3) // 2 + 1
         H2, W2 = (H1 - 3) // 2 + 1, (W1 - 3) // 2 + 1
-        assert W2 == self.F and H2 <= 8
+        assert W2 == self.F and H2 <= ENC_MAX_T
         return H1, W1, H2, W2
 
     def buffers(self, B, R):
