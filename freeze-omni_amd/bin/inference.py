@@ -48,8 +48,9 @@ def get_args(argv=None):
     p.add_argument("--input_wav", required=True, help="input wav")
     p.add_argument("--output_wav", required=True, help="output wav")
     p.add_argument("--device", default="cuda:0")
-    p.add_argument("--llm_mlp_weights", choices=["bf16", "fp8"], default="bf16",
-                   help="Qwen2 gate/up/down weights: bf16, or weight-only FP8 (e4m3 codes x a power of two per row)")
+    p.add_argument("--llm_mlp_weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
+                   help="Qwen2 gate/up/down weights: bf16, weight-only FP8 (e4m3 codes x a power of two per row) or "
+                        "weight-only MXFP4 (e2m1 codes x a power of two per 32 columns)")
     p.add_argument("--llm_mlp_fp8_rows", type=int, choices=[16, 64, 128], default=16,
                    help="with --llm_mlp_weights fp8: the most rows of a Qwen2 step that stream the FP8 codes")
     p.add_argument("--llm_kv", choices=["fp32", "bf16"], default="fp32",

@@ -374,8 +374,8 @@ def get_parser():
     p.add_argument("--top_p", type=float, default=0.8)
     p.add_argument("--top_k", type=int, default=20)
     p.add_argument("--temperature", type=float, default=0.8)
-    p.add_argument("--llm_mlp_weights", choices=["bf16", "fp8"], default=None,
-                   help="Qwen2 gate/up/down weights: bf16 (default), or weight-only FP8")
+    p.add_argument("--llm_mlp_weights", choices=["bf16", "fp8", "mxfp4"], default=None,
+                   help="Qwen2 gate/up/down weights: bf16 (default), weight-only FP8, or weight-only MXFP4")
     p.add_argument("--llm_mlp_fp8_rows", type=int, choices=[16, 64, 128], default=None,
                    help="with FP8 weights: the most rows of a Qwen2 step that stream the codes (default 16)")
     p.add_argument("--llm_kv", choices=["fp32", "bf16"], default=None,

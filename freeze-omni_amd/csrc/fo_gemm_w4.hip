@@ -1,0 +1,452 @@
+// Weight-only MXFP4 (OCP e2m1 codes, one power-of-two scale per 32 elements) GEMMs for the Qwen2 MLP at <= 16 rows,
+// and their quantiser.
+//
+//   W'[n, k] = q[n, k] * 2^e[n, k / 32]   q an e2m1 code (0, 0.5, 1, 1.5, 2, 3, 4, 6 and a sign bit), e one integer
+//                                         per (output row, block of 32 columns), stored as the E8M0 byte e + 127
+//   Y[M, N]  = epilogue( X[M, K] (fp32, split into bf16 hi + lo) . W'^T )
+//
+// An e2m1 value has 2 significant bits, so q * 2^e is exactly a bf16 value: W' has an exact bf16 image, which the
+// engine keeps packed for the bf16 kernels and runs above 16 rows.  The kernels here stream the codes -- a quarter of
+// the bytes of that image, plus 1/32 of scales -- decode them to bf16 in registers with the block scale applied
+// (v_cvt_scalef32_pk_bf16_fp4: exact) and run the same bf16 MFMAs, so both paths compute X . W'^T to the
+// accumulation-order difference that already exists between the bf16 kernels.  The block scale cannot multiply the
+// sum as the FP8 stream's column scale does; the epilogue (fo_gemm_wq.h) runs without one.  Results are deterministic
+// in every form.
+//
+// Code layout (include/fo_hip.h): [tile][K128][64 lanes][16 bytes], a lane's dword j being its 8-element MFMA
+// B fragment of k-step 4 s + j (two codes per byte, the lower column in the low nibble), K padded to a multiple of
+// 128 with zero codes; scale bytes [tile][K128][16 rows][4].  fo_gemm_w4: k_w4 (general), k_w4_xs (the SwiGLU pair at
+// K = 3584) or k_w4_sk (long-K plain), the forms of fo_gemm_w8.hip.
+#include <stdlib.h>
+
+#include <atomic>
+
+#include "fo_gemm_wq.h"
+
+namespace {
+
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+
+// 8 e2m1 codes (one dword) times 2^(sb - 127) -> 8 bf16: one convert per byte (the low nibble is the lower column)
+__device__ __forceinline__ bf16x8 dec4(unsigned d, unsigned sb) {
+  const float s = __uint_as_float(sb << 23);
+  u32x4 r;
+  r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 0));
+  r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 1));
+  r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 2));
+  r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 3));
+  return __builtin_bit_cast(bf16x8, r);
+}
+
+// The two descriptors cover exactly the codes (ntiles * KK KiB) and the scale bytes (ntiles * KK * 64): a tile at or
+// past ntiles is out of range and loads zero codes under a zero scale byte (2^-127 times 0)
+struct W4Srd {
+  __amdgpu_buffer_rsrc_t q, s;
+};
+__device__ __forceinline__ W4Srd w4_srd(const W8Args& a) {
+  return W4Srd{rsrc_of(a.Q, a.ntiles * a.KK * 1024), rsrc_of(a.scale, a.ntiles * a.KK * 64)};
+}
+__device__ __forceinline__ u32x4 w4_codes(const W4Srd& d, int lane, int step) {   // step = tile * KK + code step
+  return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(d.q, lane * 16, step * 1024, 2));
+}
+__device__ __forceinline__ unsigned w4_scales(const W4Srd& d, int lane, int step) {
+  return __builtin_amdgcn_raw_buffer_load_b32(d.s, (lane & 15) * 4, step * 64, 0);
+}
+
+// acc[t] = X[rows 0..16, code steps [kb, ke)] . (packed tile tile0 + t)^T for t < NT: U code steps in flight, each X
+// fragment loaded and split once for the NT tiles.  A k-step at or past K (K % 128 != 0: zero codes) reads no X and
+// runs no MFMA.
+template <int NT, int U>
+__device__ __forceinline__ void w4_accumulate(const W8Args& a, const W4Srd& d, const float* xp, int lane, int tile0,
+                                              int kb, int ke, f32x4 (&acc)[NT]) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int k0 = kb; k0 < ke; k0 += U) {
+    u32x4 q[U][NT];
+    unsigned sc[U][NT];
+    float4 x[U][8];
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+      const int kk = k0 + i;
+      if (kk < ke) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          q[i][t] = w4_codes(d, lane, (tile0 + t) * a.KK + kk);
+          sc[i][t] = w4_scales(d, lane, (tile0 + t) * a.KK + kk);
+        }
+        const float* p = xp + (size_t)kk * 128;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (kk * 128 + 32 * j < a.K) {
+            x[i][2 * j] = reinterpret_cast<const float4*>(p + 32 * j)[0];
+            x[i][2 * j + 1] = reinterpret_cast<const float4*>(p + 32 * j)[1];
+          }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+      const int kk = k0 + i;
+      if (kk < ke) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (kk * 128 + 32 * j < a.K) {
+            bf16x8 hi, lo;
+            split8(x[i][2 * j], x[i][2 * j + 1], hi, lo);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+              const bf16x8 w = dec4(q[i][t][j], (sc[i][t] >> (8 * j)) & 0xffu);
+              acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hi, w, acc[t], 0, 0, 0);
+              acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lo, w, acc[t], 0, 0, 0);
+            }
+          }
+      }
+    }
+  }
+}
+
+// ---- general form: workgroup u = output tile u (SW: the (gate, up) pair 2u, 2u + 1); wave w takes the code steps
+// [KK w / NW, KK (w + 1) / NW), U of them (per tile) in flight
+template <int NW, bool SW>
+__global__ __launch_bounds__(NW * 64) void k_w4(W8Args a) {
+  constexpr int T = SW ? 2 : 1, U = SW ? 1 : 2;   // (32 X floats per code step: k_w8's register budget)
+  __shared__ float part[NW][T][16][17];
+  __shared__ float rstd_s[16];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int u = blockIdx.x;
+  const W4Srd d = w4_srd(a);
+  const int kb = (int)((long)a.KK * wave / NW), ke = (int)((long)a.KK * (wave + 1) / NW);
+  const int row = min(lane & 15, a.M - 1);
+  const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
+  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
+  f32x4 acc[T];
+  w4_accumulate<T, U>(a, d, xp, lane, T * u, kb, ke, acc);
+#pragma unroll
+  for (int t = 0; t < T; ++t) w8_store_tile(part[wave][t], acc[t], lane);
+  __syncthreads();
+  const int e = threadIdx.x;
+  if (e < 256) {
+    const int rr = e >> 4, c = e & 15;
+    float x1 = 0.f, x2 = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      x1 += part[w][0][rr][c];
+      if constexpr (SW) x2 += part[w][1][rr][c];
+    }
+    w8_epilogue<SW, false>(a, u, gridDim.x, rr, c, x1, x2, rstd_s);
+  }
+}
+
+// ---- long-K plain form, as k_w8_sk: workgroup (tg, sp) = tiles NT tg .. + NT over the sp-th of S slices of the code
+// steps, the slice split over the waves as in k_w4.  ws: S slabs of [16][groups * NT * 16] partial sums; counters: one
+// zeroed ticket per tile group, left zeroed.  The hand-off is fo_common.h's (st_wt / ld_sc1): no fences, no waiting;
+// the last split to arrive sums every split's partial in split order.
+template <int NW, int NT>
+__global__ __launch_bounds__(NW * 64) void k_w4_sk(W8Args a, int S, float* ws, int* counters) {
+  // (two code steps in flight measured 18.6 / 19.5 / 21.8 us at 1 / 8 / 16 rows against 18.0 / 19.5 / 20.9 for one)
+  constexpr int U = 1;
+  __shared__ float part[NW][NT][16][17];
+  __shared__ float red[NT][16][17];
+  __shared__ float rstd_s[16];
+  __shared__ int last_s;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int tg = blockIdx.x, sp = blockIdx.y;
+  const W4Srd d = w4_srd(a);
+  const int k_lo = (int)((long)a.KK * sp / S), k_n = (int)((long)a.KK * (sp + 1) / S) - k_lo;
+  const int kb = k_lo + (int)((long)k_n * wave / NW), ke = k_lo + (int)((long)k_n * (wave + 1) / NW);
+  const int row = min(lane & 15, a.M - 1);
+  const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
+  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
+  f32x4 acc[NT];
+  w4_accumulate<NT, U>(a, d, xp, lane, NT * tg, kb, ke, acc);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) w8_store_tile(part[wave][t], acc[t], lane);
+  __syncthreads();
+  constexpr int NE = NT * 256, NTH = NW * 64;
+  for (int e = threadIdx.x; e < NE; e += NTH) {
+    const int t = e >> 8, rr = (e >> 4) & 15, c = e & 15;
+    float v = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) v += part[w][t][rr][c];
+    red[t][rr][c] = v;
+  }
+  if (S > 1) {
+    const int Ncols = gridDim.x * NT * 16;
+    const size_t sl = (size_t)16 * Ncols;
+    float* slab = ws + (size_t)sp * sl;
+    for (int e = threadIdx.x; e < NE; e += NTH) {   // (each thread stores the elements it just summed)
+      const int t = e >> 8, rr = (e >> 4) & 15, c = e & 15;
+      st_wt(slab + (size_t)rr * Ncols + (tg * NT + t) * 16 + c, red[t][rr][c]);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int* tk = counters + tg;
+      const int old = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      last_s = old == S - 1;
+      if (old == S - 1) __hip_atomic_store(tk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (!last_s) return;
+    const __amdgpu_buffer_rsrc_t rws = rsrc_of(ws);
+    for (int e = threadIdx.x; e < NE; e += NTH) {
+      const int t = e >> 8, rr = (e >> 4) & 15, c = e & 15;
+      const size_t o = (size_t)rr * Ncols + (tg * NT + t) * 16 + c;
+      const float own = red[t][rr][c];
+      float v = 0.f;
+      for (int q0 = 0; q0 < S; ++q0) v += q0 != sp ? ld_sc1(rws, q0 * sl + o) : own;
+      red[t][rr][c] = v;
+    }
+  }
+  __syncthreads();
+  const int units = (a.N + 15) / 16;
+  if (threadIdx.x < 256) {
+    const int rr = threadIdx.x >> 4, c = threadIdx.x & 15;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      if (tg * NT + t < units) w8_epilogue<false, false>(a, tg * NT + t, units, rr, c, red[t][rr][c], 0.f, rstd_s);
+  }
+}
+
+// ---- X-stationary persistent form, as k_w8_xs: the SwiGLU pair, K = NW * KPW * 128 (3584 = 28 code steps).  X hi in
+// registers, lo in LDS, units dealt evenly to at most one workgroup per CU, the next unit's codes and scales issued
+// before the current one is reduced, a fixed-order cross-wave reduction.
+template <int NW, int KPW>
+__global__ __launch_bounds__(NW * 64) void k_w4_xs(W8Args a, int units) {
+  __shared__ bf16x8 xlo[NW][4 * KPW][64];
+  __shared__ float part[NW][2][16][17];
+  __shared__ float rstd_s[16];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  constexpr int KK = NW * KPW;
+  const int ub = (int)((long)units * blockIdx.x / gridDim.x);
+  const int ue = (int)((long)units * (blockIdx.x + 1) / gridDim.x);
+  const W4Srd d = w4_srd(a);
+  u32x4 q0[KPW], q1[KPW];
+  unsigned s0[KPW], s1[KPW];
+  auto issue = [&](u32x4 (&q)[KPW], unsigned (&s)[KPW], int tile) {
+#pragma unroll
+    for (int j = 0; j < KPW; ++j) {
+      q[j] = w4_codes(d, lane, tile * KK + wave * KPW + j);
+      s[j] = w4_scales(d, lane, tile * KK + wave * KPW + j);
+    }
+  };
+  issue(q0, s0, ub < ue ? 2 * ub : a.ntiles);
+  issue(q1, s1, ub < ue ? 2 * ub + 1 : a.ntiles);
+  // X slice (hi in registers, lo in LDS); rows >= M clamp to the last row (computed, never stored)
+  bf16x8 xh[4 * KPW];
+  {
+    const int row = min(lane & 15, a.M - 1);
+    const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4) + (size_t)wave * KPW * 128;
+#pragma unroll
+    for (int j = 0; j < 4 * KPW; ++j) {
+      bf16x8 lo;
+      split8(reinterpret_cast<const float4*>(xp + j * 32)[0], reinterpret_cast<const float4*>(xp + j * 32)[1], xh[j],
+             lo);
+      xlo[wave][j][lane] = lo;
+    }
+  }
+  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
+  auto compute = [&](u32x4 (&q)[KPW], unsigned (&s)[KPW]) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < KPW; ++j)
+#pragma unroll
+      for (int h = 0; h < 4; ++h) {
+        const bf16x8 w = dec4(q[j][h], (s[j] >> (8 * h)) & 0xffu);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[4 * j + h], w, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xlo[wave][4 * j + h][lane], w, acc, 0, 0, 0);
+      }
+    return acc;
+  };
+  for (int u = ub; u < ue; ++u) {
+    // the next unit's codes are issued unconditionally; past the last unit they address tile `ntiles`, beyond the
+    // descriptors' range, which the hardware drops without touching memory
+    const int nxt = u + 1 < ue ? 2 * (u + 1) : a.ntiles;
+    const f32x4 c0 = compute(q0, s0);
+    issue(q0, s0, nxt);
+    const f32x4 c1 = compute(q1, s1);
+    issue(q1, s1, nxt + (u + 1 < ue ? 1 : 0));
+    __syncthreads();  // the previous unit's epilogue has read part[]
+    w8_store_tile(part[wave][0], c0, lane);
+    w8_store_tile(part[wave][1], c1, lane);
+    __syncthreads();
+    const int e = threadIdx.x;
+    if (e < 256) {
+      const int rr = e >> 4, c = e & 15;
+      float x1 = 0.f, x2 = 0.f;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) {
+        x1 += part[w][0][rr][c];
+        x2 += part[w][1][rr][c];
+      }
+      w8_epilogue<true, false>(a, u, 0, rr, c, x1, x2, rstd_s);
+    }
+  }
+}
+
+// ---- quantiser.  One workgroup per source row n, one 32-column block per thread and pass: the block's amax, e from
+// its exponent and mantissa (the smallest integer with amax * 2^-e <= 6 = 1.5 * 2^2, at least -125 so that every
+// non-zero q * 2^e is a normal bf16; 0 for an all-zero block), W * 2^-e (exact, or an underflow that rounds to 0 anyway)
+// rounded to the nearest e2m1 magnitude, ties to the even code, the sign bit copied; then the block's four dwords to
+// their fragment positions (lane group g = columns 8 g .. + 8 of the k-step), its scale byte, and the 32 dequantised
+// bf16 values to wdq.  Columns K .. 128 KK and rows N .. 16 ceil(N / 16) get zero codes and scale byte 127.
+__device__ __forceinline__ unsigned e2m1_code(float v) {
+  const float m = fabsf(v);
+  const unsigned c = (unsigned)(m > 0.25f) + (unsigned)(m >= 0.75f) + (unsigned)(m > 1.25f) + (unsigned)(m >= 1.75f) +
+                     (unsigned)(m > 2.5f) + (unsigned)(m >= 3.5f) + (unsigned)(m > 5.f);
+  return c | ((__float_as_uint(v) >> 28) & 8u);
+}
+
+__global__ __launch_bounds__(256) void k_quant_w4(const void* W, int src_bf16, int N, int K, int ldw, unsigned char* q,
+                                                  unsigned char* scale, bf16_t* wdq, int KK, int tile_base,
+                                                  int tile_stride) {
+  const int n = blockIdx.x;
+  auto at = [&](int k) {
+    return src_bf16 ? bf2f(reinterpret_cast<const bf16_t*>(W)[(size_t)n * ldw + k])
+                    : reinterpret_cast<const float*>(W)[(size_t)n * ldw + k];
+  };
+  const size_t dt = (size_t)tile_base + (size_t)(n >> 4) * tile_stride;
+  for (int b = threadIdx.x; b < KK * 4; b += 256) {   // block b: columns 32 b .. + 32, k-step b & 3 of code step b >> 2
+    const bool live = n < N && 32 * b < K;   // (K % 32 == 0: a block is inside K or past it)
+    float v[32];
+    float amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+      v[j] = live ? at(32 * b + j) : 0.f;
+      amax = fmaxf(amax, fabsf(v[j]));
+    }
+    int e = 0;
+    if (amax > 0.f) {
+      const unsigned bits = __float_as_uint(amax);
+      e = (int)(bits >> 23) - 127 - 2 + ((bits & 0x7fffffu) > 0x400000u ? 1 : 0);
+      e = max(e, -125);
+    }
+    const float s = __uint_as_float((unsigned)(e + 127) << 23), inv = __uint_as_float((unsigned)(127 - e) << 23);
+    const int kk = b >> 2, ks = b & 3;
+    scale[((dt * KK + kk) * 16 + (n & 15)) * 4 + ks] = (unsigned char)(e + 127);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      unsigned dw = 0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const unsigned c = e2m1_code(v[8 * g + j] * inv);
+        dw |= c << (4 * j);
+        if (wdq && live) {
+          const float mag = (c & 7u) < 4u ? 0.5f * (float)(c & 7u) : (float)(((c & 1u) + 2u) << (((c & 7u) >> 1) - 2u));
+          wdq[(size_t)n * K + 32 * b + 8 * g + j] = f2bf(__uint_as_float(__float_as_uint(mag * s) | ((c & 8u) << 28)));
+        }
+      }
+      *reinterpret_cast<unsigned*>(q + ((dt * KK + kk) * 64 + 16 * g + (n & 15)) * 16 + 4 * ks) = dw;
+    }
+  }
+}
+
+int g_cus = 0;
+int w4_cus() {
+  if (!g_cus) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    g_cus = n;
+  }
+  return g_cus;
+}
+
+// the launch counters of the three forms (fo_gemm_w4_counts): general, xs, sk
+std::atomic<long long> g_w4_launches[3];
+
+}  // namespace
+
+extern "C" {
+
+long long fo_quant_w4_bytes(int N, int K) { return (long long)((N + 15) / 16) * ((K + 127) / 128) * 1024; }
+long long fo_quant_w4_scale_bytes(int N, int K) { return (long long)((N + 15) / 16) * ((K + 127) / 128) * 64; }
+
+int fo_quant_w4(const void* W, int src_bf16, int N, int K, int ldw, void* q, void* scale, void* wdq, int tile_base,
+                int tile_stride, hipStream_t stream) {
+  FO_REQUIRE(W && q && scale, "fo_quant_w4: NULL W, q or scale");
+  FO_REQUIRE(N > 0 && K > 0 && ldw >= K, "fo_quant_w4: bad shape N=%d K=%d ldw=%d", N, K, ldw);
+  FO_REQUIRE((K & 31) == 0, "fo_quant_w4: K=%d must be a multiple of 32 (the scale block)", K);
+  FO_REQUIRE(tile_base >= 0 && tile_stride >= 1, "fo_quant_w4: bad tile_base=%d tile_stride=%d", tile_base,
+             tile_stride);
+  const int nt = (N + 15) / 16;
+  hipLaunchKernelGGL(k_quant_w4, dim3(nt * 16), dim3(256), 0, stream, W, src_bf16, N, K, ldw, (unsigned char*)q,
+                     (unsigned char*)scale, (bf16_t*)wdq, (K + 127) / 128, tile_base, tile_stride);
+  return fo::check_launch("fo_quant_w4");
+}
+
+int fo_gemm_w4_counts(long long* out, int n) {
+  for (int i = 0; out && i < n && i < 3; ++i) out[i] = g_w4_launches[i].load(std::memory_order_relaxed);
+  return 3;
+}
+int fo_gemm_w4_counts_reset(void) {
+  for (int i = 0; i < 3; ++i) g_w4_launches[i].store(0, std::memory_order_relaxed);
+  return 0;
+}
+
+int fo_gemm_w4(const float* X, int ldx, int M, int K, const void* Q, const void* scale, int ntiles, int N, int swiglu,
+               float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters, const float* rstats,
+               int rgroups, float eps, float* sout, const float* gnext, float* yg, int* sgroups, hipStream_t stream) {
+  // every check before the first HIP call
+  FO_REQUIRE(M > 0 && N > 0 && K > 0, "fo_gemm_w4: bad shape M=%d N=%d K=%d", M, N, K);
+  FO_REQUIRE(M <= 16, "fo_gemm_w4: M=%d rows, the MXFP4 stream serves M <= 16 (more rows run the bf16 image)", M);
+  FO_REQUIRE((K & 31) == 0, "fo_gemm_w4: K=%d must be a multiple of 32", K);
+  FO_REQUIRE(X && Q && Y, "fo_gemm_w4: NULL X, Q or Y");
+  FO_REQUIRE(scale, "fo_gemm_w4: NULL scale (the E8M0 block bytes of fo_quant_w4)");
+  FO_REQUIRE(ldx >= K && (ldx & 3) == 0 && ((unsigned long long)X & 15) == 0,
+             "fo_gemm_w4: X needs ldx=%d >= K=%d, ldx %% 4 == 0 and 16-byte alignment", ldx, K);
+  FO_REQUIRE(ldy >= N, "fo_gemm_w4: ldy=%d < N=%d", ldy, N);
+  const int units = (N + 15) / 16;
+  FO_REQUIRE(!swiglu || (ntiles & 1) == 0, "fo_gemm_w4: swiglu with an odd ntiles=%d (gate/up tiles come in pairs)",
+             ntiles);
+  // ntiles is the extent of Q and scale (the descriptors' range): (gate, up) pairs for SwiGLU
+  FO_REQUIRE(ntiles == (swiglu ? 2 : 1) * units, "fo_gemm_w4: ntiles=%d packed tiles for N=%d%s", ntiles, N,
+             swiglu ? " SwiGLU columns" : " columns");
+  FO_REQUIRE(!rstats || rgroups > 0, "fo_gemm_w4: rstats without rgroups");
+  FO_REQUIRE(!sout || (!swiglu && (!yg || gnext)), "fo_gemm_w4: sout needs a non-SwiGLU launch, yg needs gnext");
+  FO_REQUIRE(sout || !yg, "fo_gemm_w4: yg comes with sout");
+  FO_REQUIRE(!(swiglu && residual), "fo_gemm_w4: swiglu with residual unsupported");
+  const int KK = (K + 127) / 128;
+  FO_REQUIRE((long long)(ntiles + 4) * KK * 1024 < (1ll << 31), "fo_gemm_w4: ntiles=%d x K=%d codes exceed 2 GiB",
+             ntiles, K);
+  const W8Args a{X,    Q,     reinterpret_cast<const float*>(scale), Y,  ldx,    ldy,     M,
+                 K,    N,     ntiles,                                KK, residual, sout,   gnext,
+                 yg,   rstats, rgroups,                              eps};
+  if (sgroups) *sgroups = units;
+  if (swiglu && K == 3584) {
+    const int G = units < w4_cus() ? units : w4_cus();
+    // 14 waves x 2 code steps (21.0 / 23.5 us at 8 / 16 rows against 21.6 / 24.3 for 7 x 4, which FO_W4_XS=7 runs:
+    // A/B only)
+    static const bool w7 = [] { const char* e = getenv("FO_W4_XS"); return e && atoi(e) == 7; }();
+    if (w7) hipLaunchKernelGGL((k_w4_xs<7, 4>), dim3(G), dim3(448), 0, stream, a, units);
+    else hipLaunchKernelGGL((k_w4_xs<14, 2>), dim3(G), dim3(896), 0, stream, a, units);
+    g_w4_launches[1].fetch_add(1, std::memory_order_relaxed);
+    return fo::check_launch("fo_gemm_w4 (xs)");
+  }
+  // long-K plain projections (the Qwen2 down: 224 tiles x 148 code steps): 4 tiles per workgroup, K split over the
+  // workgroups until the grid is about one workgroup per CU, merged in the launch (needs the caller's workspace and
+  // zeroed tickets; without them the one-tile form below serves)
+  if (!swiglu && KK >= 64 && units >= 16 && ws && counters) {
+    constexpr int NT = 4, NW = 8;
+    const int groups = (units + NT - 1) / NT;
+    int S = w4_cus() / groups;
+    S = S < 1 ? 1 : (S > 8 ? 8 : S);
+    if (S == 1 || ((long long)S * 16 * groups * NT * 16 <= ws_floats && groups <= (1 << 20))) {
+      hipLaunchKernelGGL((k_w4_sk<NW, NT>), dim3(groups, S), dim3(NW * 64), 0, stream, a, S, ws, counters);
+      g_w4_launches[2].fetch_add(1, std::memory_order_relaxed);
+      return fo::check_launch("fo_gemm_w4 (split K)");
+    }
+  }
+  const bool wide = KK >= 16;
+  if (swiglu) {
+    if (wide) hipLaunchKernelGGL((k_w4<16, true>), dim3(units), dim3(1024), 0, stream, a);
+    else hipLaunchKernelGGL((k_w4<4, true>), dim3(units), dim3(256), 0, stream, a);
+  } else {
+    if (wide) hipLaunchKernelGGL((k_w4<16, false>), dim3(units), dim3(1024), 0, stream, a);
+    else hipLaunchKernelGGL((k_w4<4, false>), dim3(units), dim3(256), 0, stream, a);
+  }
+  g_w4_launches[0].fetch_add(1, std::memory_order_relaxed);
+  return fo::check_launch("fo_gemm_w4");
+}
+
+}  // extern "C"

@@ -17,31 +17,9 @@
 //  * fo_gemm_w8_rows128, 65..128 rows: k_w8_rows128, then k_w8_rows_merge.
 #include <stdlib.h>
 
-#include "fo_common.h"
+#include "fo_gemm_wq.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
-struct W8Args {
-  const float* X;
-  const void* Q;       // codes in packed order
-  const float* scale;  // [ntiles][16], packed tile order
-  float* Y;
-  int ldx, ldy;
-  int M, K, N;         // N: logical output columns (after SwiGLU pairing)
-  int ntiles;          // packed 16-column tiles in Q
-  int KK;              // 64-column code steps per tile: ceil(K / 64)
-  int residual;
-  // the RMSNorm split across two GEMMs, as fo_gemm_rms (fo_gemm.hip GemmArgs)
-  float* sout;
-  const float* gnext;
-  float* yg;
-  const float* rstats;
-  int rgroups;
-  float reps;
-};
 
 // 8 e4m3fn codes (two dwords) -> 8 bf16: v_cvt_pk_f32_fp8 per code pair, then the upper halves of the two floats in
 // one v_perm (an e4m3 value has 4 significant bits: the truncation is exact)
@@ -54,75 +32,6 @@ __device__ __forceinline__ bf16x8 dec8(unsigned a, unsigned b) {
   r[2] = __builtin_amdgcn_perm(__float_as_uint(f2[1]), __float_as_uint(f2[0]), 0x07060302u);
   r[3] = __builtin_amdgcn_perm(__float_as_uint(f3[1]), __float_as_uint(f3[0]), 0x07060302u);
   return __builtin_bit_cast(bf16x8, r);
-}
-
-__device__ __forceinline__ void split8(const float4 p0, const float4 p1, bf16x8& hi, bf16x8& lo) {
-  const float f[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const __bf16 h = (__bf16)f[i];
-    hi[i] = h;
-    lo[i] = (__bf16)(f[i] - (float)h);
-  }
-}
-
-// Output element (row rr, column c) of unit u, thread e = 16 rr + c of the first 256: x1 / x2 are the fp32 sums of
-// the unit's (gate, up) tiles (SW) or of its one tile.  The column scale first, then the consumer's rstd, SwiGLU,
-// the residual and the store; a producer also writes yg = y * gamma_next and the row's sum of squares over the
-// unit's 16 columns.  Rows >= M (computed from a clamped row) are neither stored nor summed.
-template <bool SW>
-__device__ __forceinline__ void w8_epilogue(const W8Args& a, int u, int groups, int rr, int c, float x1, float x2,
-                                            const float* rstd_s) {
-  const int n = u * 16 + c;
-  const bool live = rr < a.M && n < a.N;
-  float y = 0.f;
-  if (live) {
-    if constexpr (SW) {
-      x1 *= a.scale[(2 * u) * 16 + c];
-      x2 *= a.scale[(2 * u + 1) * 16 + c];
-    } else {
-      x1 *= a.scale[n];
-    }
-    if (a.rstats) {
-      x1 *= rstd_s[rr];
-      x2 *= rstd_s[rr];
-    }
-    y = SW ? x1 / (1.f + expf(-x1)) * x2 : x1;
-    const size_t o = (size_t)rr * a.ldy + n;
-    if (a.residual) y += a.Y[o];
-    a.Y[o] = y;
-    if (a.yg) a.yg[o] = y * a.gnext[n];
-  }
-  if constexpr (!SW) {
-    if (a.sout) {   // (uniform; the row's 16 columns are one 16-lane row of the wave)
-      float sq = y * y;
-      sq += lane_xor<8>(sq);
-      sq += lane_xor<4>(sq);
-      sq += lane_xor<2>(sq);
-      sq += lane_xor<1>(sq);
-      if (c == 0 && rr < a.M) a.sout[(size_t)rr * groups + u] = sq;
-    }
-  }
-}
-
-// The consumer's rstd of rows [r0, r0 + n) into rstd_s[row], a row per wave of NW: the row's statistics summed
-// lane-strided, then across the wave.  Rows >= M take the last row's (computed, never stored).
-template <int NW>
-__device__ __forceinline__ void w8_rstd(const W8Args& a, float* rstd_s, int wave, int lane, int r0 = 0, int n = 16) {
-  for (int r = wave; r < n; r += NW) {
-    const int rr = r0 + r, m = min(rr, a.M - 1);
-    float v = 0.f;
-    for (int j = lane; j < a.rgroups; j += 64) v += a.rstats[(size_t)m * a.rgroups + j];
-    v = wave_sum(v);
-    if (lane == 0) rstd_s[rr] = rsqrtf(v / (float)a.K + a.reps);
-  }
-}
-
-// One wave's accumulator tile (a lane holds rows 4 (lane >> 4) .. + 4 of column lane & 15) into a padded LDS tile
-template <typename Tile>
-__device__ __forceinline__ void w8_store_tile(Tile& tile, const f32x4 acc, int lane, int r0 = 0) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) tile[r0 + 4 * (lane >> 4) + i][lane & 15] = acc[i];
 }
 
 // acc[t] = X[rows 0..16, code steps [kb, ke)] . (packed tile tile0 + t)^T for t < NT: U code steps in flight, each X

@@ -93,6 +93,13 @@ _SIGS = {
     "fo_gemm_w8_rows128": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int,
                                    c_vp, c_ll, c_vp, c_vp, c_int, c_float, c_vp, c_vp, c_vp, ctypes.POINTER(c_int),
                                    c_vp]),
+    "fo_quant_w4_bytes": (c_ll, [c_int, c_int]),
+    "fo_quant_w4_scale_bytes": (c_ll, [c_int, c_int]),
+    "fo_quant_w4": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
+    "fo_gemm_w4": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_ll,
+                           c_vp, c_vp, c_int, c_float, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), c_vp]),
+    "fo_gemm_w4_counts": (c_int, [ctypes.POINTER(c_ll), c_int]),
+    "fo_gemm_w4_counts_reset": (c_int, []),
     "fo_gemm_pick_split": (c_int, [c_int, c_int, c_int]),
     "fo_gemm": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
                         c_int, c_int, c_vp, c_ll, c_vp, c_int, c_vp]),

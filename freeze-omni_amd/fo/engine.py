@@ -77,7 +77,9 @@ class FreezeOmniEngine:
         mlp_weights: "bf16" (default) or "fp8": the Qwen2 gate/up/down weights under weight-only FP8 (e4m3fn codes
         times a power of two per output row, DESIGN: `mlp_weights`); Qwen2 steps of <= 16 rows then stream the codes.
         `src` serves the dequantised weights (fo.weights.FakeQuantSource), so an oracle or a second engine can be
-        built on the same model.
+        built on the same model.  "mxfp4": the same weights under weight-only MXFP4 instead (e2m1 codes times a power
+        of two per block of 32 columns): Qwen2 steps of <= 16 rows stream the codes for the GEMMs of
+        ops.W4_POLICY, every other launch runs the exact bf16 image; mlp_fp8_rows stays 16.
         mlp_fp8_rows: 16 (default), 64 or 128, with mlp_weights="fp8" only: 64 lets Qwen2 steps of 17..64 rows (duplex
         ticks, prefixed first chunks, one-chunk listens of more than 8 sessions) stream the codes too, 128 steps of
         65..128 rows as well (the grouped offline listen, duplex ticks whose sessions start a turn), for the GEMMs
@@ -89,8 +91,8 @@ class FreezeOmniEngine:
         (models/utils.py:31-38)."""
         if not torch.cuda.is_available():
             raise RuntimeError("FreezeOmniEngine needs an MI355X (gfx950) device: there is no CPU fallback")
-        if mlp_weights not in ("bf16", "fp8"):
-            raise ValueError(f"mlp_weights must be 'bf16' or 'fp8', got {mlp_weights!r}")
+        if mlp_weights not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"mlp_weights must be 'bf16', 'fp8' or 'mxfp4', got {mlp_weights!r}")
         if mlp_fp8_rows not in (16, 64, 128):
             raise ValueError(f"mlp_fp8_rows must be 16, 64 or 128, got {mlp_fp8_rows!r}")
         if mlp_fp8_rows != 16 and mlp_weights != "fp8":
@@ -115,9 +117,9 @@ class FreezeOmniEngine:
             st = {f"encoder_{i}.global_cmvn.{n}": torch.from_numpy(np.asarray(v, np.float32))
                   for i in ("user", "system") for n, v in (("mean", mean), ("istd", istd))}
             src = OverlaySource(CheckpointSource(st, self.device), src)
-        if mlp_weights == "fp8" and not receive_weights:
+        if mlp_weights in ("fp8", "mxfp4") and not receive_weights:
             from .weights import FakeQuantSource
-            self.src = FakeQuantSource(src)   # (the engines below quantise the raw weights themselves)
+            self.src = FakeQuantSource(src, mlp_weights)   # (the engines below quantise the raw weights themselves)
         else:
             self.src = src
         self.max_sessions = max_sessions
@@ -127,7 +129,8 @@ class FreezeOmniEngine:
         V = self.cfg["llm"]["vocab_size"]
         self.llm = LLMEngine(src, self.cfg["llm"], self.device,
                              kv_tokens=llm_kv_tokens or min(max_sessions * 4096, 1 << 17),
-                             mlp_w8=mlp_weights == "fp8", mlp_w8_rows=mlp_fp8_rows, kv_dtype=llm_kv)
+                             mlp_w8=mlp_weights == "fp8", mlp_w8_rows=mlp_fp8_rows, kv_dtype=llm_kv,
+                             mlp_w4=mlp_weights == "mxfp4")
         self.tts = TTSEngine(src, self.cfg["decoder_json"], self.device,
                              kv_tokens=tts_kv_tokens or min(max_sessions * 2048, 1 << 17))
         self.codec = CodecEngine(src, self.cfg["codec_json"], self.device)
@@ -174,10 +177,10 @@ class FreezeOmniEngine:
             torch.cuda.empty_cache()
             self.llm = LLMEngine(src, self.cfg["llm"], self.device, kv_tokens=kv_tokens,
                                  mlp_w8=self.mlp_weights == "fp8", mlp_w8_rows=self.mlp_fp8_rows,
-                                 kv_dtype=self.llm_kv)
+                                 kv_dtype=self.llm_kv, mlp_w4=self.mlp_weights == "mxfp4")
         elif "predictor_head.weight" in src:
             self.llm.head_w, self.llm.head_b = src.get("predictor_head.weight"), src.get("predictor_head.bias")
-        self.src = FakeQuantSource(src) if fq else src
+        self.src = FakeQuantSource(src, self.src.fmt) if fq else src
         return sorted(state)
 
     # ------------------------------------------------------------------ chat template (audioLLM.py:112-126)

@@ -442,6 +442,134 @@ def quant_w8(w):
     return q, scales, _quant_w8(w, q, scales, 0, 1)
 
 
+# Which <= 16-row GEMMs of a PackedLinearW4 stream the MXFP4 codes: a GEMM enters only if, at both 8 and 16 rows, its
+# median beat the bf16 image of the same W' by more than that arm's repeat-to-repeat spread (DESIGN 5.5's rule;
+# scripts/gemm_w4_ab.py, profiles/mlp_mxfp4_gemm_ab.txt).  A GEMM that is not listed runs the image at
+# every row count.  The one place the policy lives.
+W4_POLICY = {"gate_up": True, "down": True}
+
+
+class PackedLinearW4:
+    """A bias-free linear layer under weight-only MXFP4 (fo.quant, include/fo_hip.h fo_quant_w4): the weight is
+    W'[n, k] = q[n, k] * 2^e[n, k // 32] with q an e2m1 code.  Holds the packed codes `q`, the E8M0 block `scales` and
+    `bf16`, a PackedLinear over the dequantised weight (W' is exactly a bf16 matrix).  Calls of <= 16 fp32 rows stream
+    the codes (fo_gemm_w4) where W4_POLICY lists this GEMM; every other call forwards to the bf16 image, so both
+    compute X . W'^T.
+
+    w: [N, K] device weight (bf16 or fp32, K % 32 == 0), quantised on the device; swiglu_up as PackedLinear.
+    receive=True: storages allocated, nothing quantised (a replica whose weights arrive by broadcast).
+    Setting `stream = True` on an instance sends every <= 16-row call to the codes (tests, A/B scripts)."""
+
+    bias = None
+
+    def __init__(self, w, swiglu_up=None, receive=False):
+        _check_dev(w)
+        self.N, self.K = w.shape
+        if self.K % 32:
+            raise ValueError(f"PackedLinearW4 needs K % 32 == 0 (the scale block), got K={self.K}")
+        self.Kp = self.K
+        self.swiglu = swiglu_up is not None
+        self.stream = bool(W4_POLICY["gate_up" if self.swiglu else "down"])
+        self.device = w.device
+        self.ntiles = (self.N + 15) // 16 * (2 if self.swiglu else 1)
+        KK = (self.K + 127) // 128
+        self.q = torch.empty(self.ntiles * KK * 1024, dtype=torch.uint8, device=w.device)
+        self.scales = torch.empty(self.ntiles * KK * 64, dtype=torch.uint8, device=w.device)
+        if receive:
+            self.bf16 = PackedLinear(w, swiglu_up=swiglu_up)
+            return
+        dq = [_quant_w4(w, self.q, self.scales, 0, 2 if self.swiglu else 1)]
+        if self.swiglu:
+            dq.append(_quant_w4(swiglu_up, self.q, self.scales, 1, 2))
+        self.bf16 = PackedLinear(dq[0], swiglu_up=dq[1] if self.swiglu else None)
+
+    @property
+    def packed(self):
+        return self.bf16.packed
+
+    @property
+    def nbytes(self):
+        """The bf16 image (what `weight_bytes` has always counted); the codes and scales are fp4_nbytes."""
+        return self.bf16.nbytes
+
+    @property
+    def fp4_nbytes(self):
+        return self.q.numel() + self.scales.numel()
+
+    def streams(self, rows):
+        """Whether a call of `rows` fp32 rows streams the codes (else it runs the bf16 image)."""
+        return rows <= 16 and self.stream
+
+    def __call__(self, x, out=None, act="none", residual=False, out_dtype=F32, splitk=0, M=None, norm=None,
+                 stats_out=None, xpack=None, ypack=None):
+        rows = x.shape[0] if M is None else M
+        if (not self.streams(rows) or x.dtype != F32 or act != "none" or out_dtype != F32 or
+                (out is not None and out.dtype != F32)):
+            return self.bf16(x, out=out, act=act, residual=residual, out_dtype=out_dtype, splitk=splitk, M=M, norm=norm,
+                             stats_out=stats_out, xpack=xpack, ypack=ypack)
+        import ctypes
+        _check_dev(x)
+        if x.stride(-1) != 1 or x.shape[-1] < self.Kp:
+            raise ValueError(f"PackedLinearW4 input needs unit stride and >= {self.Kp} columns, got {tuple(x.shape)}")
+        if out is None:
+            out = torch.empty(rows, self.N, dtype=F32, device=x.device)
+        rst, rg, eps, so, gn, yg = _norm_args(norm, stats_out, out)
+        if stats_out is not None and (self.N + 15) // 16 > stats_out.max_groups:
+            raise RuntimeError(f"RowStats holds {stats_out.max_groups} groups per row, fo_gemm_w4 writes "
+                               f"{(self.N + 15) // 16}")
+        sg = ctypes.c_int(0)
+        rt = Runtime.get(x.device)
+        # (x is read as fp32 rows and the output is written row-major only: xpack / ypack stay untouched)
+        _lib.call("fo_gemm_w4", x.data_ptr(), x.stride(0), rows, self.Kp, self.q.data_ptr(), self.scales.data_ptr(),
+                  self.ntiles, self.N, 1 if self.swiglu else 0, out.data_ptr(), out.stride(0), 1 if residual else 0,
+                  rt.ws.data_ptr(), rt.ws.numel(), rt.counters.data_ptr(), rst, rg, eps, so, gn, yg, ctypes.byref(sg),
+                  stream(x.device))
+        if stats_out is not None:
+            stats_out.groups = sg.value
+        return out
+
+
+def _quant_w4(w, q, scales, base, stride):
+    """fo_quant_w4 of the [N, K] weight w into packed tiles base, base + stride, ... of q / scales; returns the
+    dequantised weight (bf16 [N, K])."""
+    if w.dtype not in (BF16, F32):
+        w = w.float()
+    w = w.contiguous()
+    N, K = w.shape
+    dq = torch.empty(N, K, dtype=BF16, device=w.device)
+    _lib.call("fo_quant_w4", w.data_ptr(), 1 if w.dtype == BF16 else 0, N, K, K, q.data_ptr(), scales.data_ptr(),
+              dq.data_ptr(), base, stride, stream(w.device))
+    return dq
+
+
+def quant_w4(w, tile_base=0, tile_stride=1):
+    """fo_quant_w4 of one [N, K] device weight (bf16 or fp32) -> (packed codes uint8, packed E8M0 scale bytes uint8,
+    dequantised weight bf16 [N, K]); the CPU reference is fo.quant.quantize_blocks_e2m1.  tile_base / tile_stride place
+    the source tiles in storages sized for them (the other tiles: zero codes, scale byte 127)."""
+    N, K = w.shape
+    nt = tile_base + ((N + 15) // 16 - 1) * tile_stride + 1
+    KK = (K + 127) // 128
+    q = torch.zeros(nt * KK * 1024, dtype=torch.uint8, device=w.device)
+    scales = torch.full((nt * KK * 64,), 127, dtype=torch.uint8, device=w.device)
+    return q, scales, _quant_w4(w, q, scales, tile_base, tile_stride)
+
+
+W4_LAUNCH_KINDS = ("w4", "w4_xs", "w4_sk")
+
+
+def w4_launch_counts():
+    """{form: fo_gemm_w4 launches issued since the last reset} for the general, X-stationary and split-K forms
+    (host-side counters of their own: these kernels have no FoLaunchKind)."""
+    import ctypes
+    buf = (ctypes.c_longlong * 3)()
+    _lib.load().fo_gemm_w4_counts(buf, 3)
+    return {k: int(buf[i]) for i, k in enumerate(W4_LAUNCH_KINDS)}
+
+
+def w4_launch_counts_reset():
+    _lib.call("fo_gemm_w4_counts_reset")
+
+
 # FO_XPACK=0 turns the packed <= 64-row activations off (A/B only)
 XPACK = os.environ.get("FO_XPACK", "1") != "0"
 

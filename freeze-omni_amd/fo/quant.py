@@ -7,6 +7,9 @@ q is an OCP e4m3fn code (gfx950's format), e[n] one integer per output row: the 
 max|W[n, :]| * 2^-e[n] <= 448, taken from the float's exponent and mantissa (448 = 1.75 * 2^8), 0 for an all-zero row.
 W * 2^-e is exact, so the rounding to e4m3fn (nearest-even) never saturates; q * 2^e has at most 4 significant bits and
 is therefore exactly a bf16 value.
+
+Below it, the same for the weight-only MXFP4 quantiser (fo_quant_w4, `mlp_weights="mxfp4"`): e2m1 codes with one
+exponent per block of 32 columns.
 """
 import torch
 
@@ -56,4 +59,73 @@ def pack_scales(e, tile_base=0, tile_stride=1, out=None):
     if out is None:
         out = torch.ones((tile_base + (nt - 1) * tile_stride + 1) * 16, dtype=torch.float32)
     out.view(-1, 16)[tile_base::tile_stride][:nt] = s.view(nt, 16)
+    return out
+
+
+# ---------------------------------------------------------------- MXFP4 (mlp_weights="mxfp4"; fo_quant_w4)
+#     W'[n, k] = q[n, k] * 2^e[n, k // 32]
+# q is an OCP e2m1 code (magnitudes E2M1_GRID as codes 0..7, bit 3 the sign, copied from the weight's sign bit even where
+# the magnitude rounds to 0), e one integer per (output row, block of 32 consecutive k): the smallest with
+# max|W[n, block]| * 2^-e <= 6, taken from the float's exponent and mantissa (6 = 1.5 * 2^2), at least -125 (so that
+# every non-zero q * 2^e is a normal bf16) and 0 for an all-zero block.  W * 2^-e is exact (or an underflow that rounds
+# to 0 anyway) and is rounded to the nearest grid point, ties to the even code; nothing saturates, the scaled block
+# maximum lies in (3, 6].  q * 2^e has 2 significant bits and is therefore exactly a bf16 value.
+E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+MX_BLOCK = 32
+
+
+def block_exponents(w):
+    """e[n, k // 32] (int32) of a [N, K] weight, K % 32 == 0."""
+    N, K = w.shape
+    if K % MX_BLOCK:
+        raise ValueError(f"MXFP4 needs K % 32 == 0, got K={K}")
+    amax = w.detach().float().abs().view(N, K // MX_BLOCK, MX_BLOCK).amax(dim=2)
+    bits = amax.contiguous().view(torch.int32)
+    e = (bits >> 23) - 127 - 2 + ((bits & 0x7FFFFF) > 0x400000).to(torch.int32)
+    e = e.clamp(min=-125)
+    return torch.where(amax > 0, e, torch.zeros_like(e))
+
+
+def quantize_blocks_e2m1(w):
+    """w [N, K] (bf16 or fp32, CPU) -> (q uint8 [N, K] e2m1 codes 0..15, e int32 [N, K // 32], w_dq bf16 [N, K])."""
+    w32 = w.detach().float()
+    e = block_exponents(w32)
+    ek = e.repeat_interleave(MX_BLOCK, dim=1)
+    m = torch.ldexp(w32, -ek).abs()
+    # nearest grid point, a tie to the even code: 0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4
+    code = ((m > 0.25).to(torch.uint8) + (m >= 0.75) + (m > 1.25) + (m >= 1.75) + (m > 2.5) + (m >= 3.5) +
+            (m > 5.0)).to(torch.uint8)
+    neg = torch.signbit(w32)
+    mag = torch.tensor(E2M1_GRID)[code.long()]
+    w_dq = torch.ldexp(torch.where(neg, -mag, mag), ek).to(torch.bfloat16)
+    return code | (neg.to(torch.uint8) << 3), e, w_dq
+
+
+def pack_codes_w4(q, tile_base=0, tile_stride=1, out=None):
+    """q uint8 [N, K] (codes 0..15) -> the packed order fo_quant_w4 writes ([tile][ceil(K/128)][64 lanes][16 bytes],
+    flat uint8, two codes per byte with the lower column in the low nibble); tiles placed as pack_codes does."""
+    N, K = q.shape
+    nt, KK = (N + 15) // 16, (K + 127) // 128
+    p = torch.zeros(nt * 16, KK * 128, dtype=torch.uint8)
+    p[:N, :K] = q
+    p = p[:, 0::2] | (p[:, 1::2] << 4)          # [row][KK * 64 bytes]: byte c holds columns 2 c, 2 c + 1
+    # [tile][row r][step s][k-step j][lane group g][byte b] -> [tile][s][lane 16 g + r][4 j + b]
+    p = p.view(nt, 16, KK, 4, 4, 4).permute(0, 2, 4, 1, 3, 5).reshape(nt, KK * 1024)
+    if out is None:
+        out = torch.zeros((tile_base + (nt - 1) * tile_stride + 1) * KK * 1024, dtype=torch.uint8)
+    out.view(-1, KK * 1024)[tile_base::tile_stride][:nt] = p
+    return out
+
+
+def pack_scales_w4(e, tile_base=0, tile_stride=1, out=None):
+    """e int32 [N, K // 32] -> E8M0 bytes e + 127 at [tile][ceil(K/128)][16 rows][4] in the same tile order (127 for
+    the rows beyond N and the blocks beyond K)."""
+    N, KB = e.shape
+    nt, KK = (N + 15) // 16, (KB + 3) // 4
+    s = torch.full((nt * 16, KK * 4), 127, dtype=torch.uint8)
+    s[:N, :KB] = (e + 127).to(torch.uint8)
+    s = s.view(nt, 16, KK, 4).permute(0, 2, 1, 3).reshape(nt, KK * 64)
+    if out is None:
+        out = torch.full(((tile_base + (nt - 1) * tile_stride + 1) * KK * 64,), 127, dtype=torch.uint8)
+    out.view(-1, KK * 64)[tile_base::tile_stride][:nt] = s
     return out

@@ -14,7 +14,7 @@ import torch
 
 from . import ops
 from .kv import BatchMeta
-from .ops import F32, PackedLinear, PackedLinearW8
+from .ops import F32, PackedLinear, PackedLinearW4, PackedLinearW8
 from .weights import ReceiveSource
 
 # FO_ATTN_DENSE=0 passes the item table even for one-token-per-sequence batches (A/B against a
@@ -33,11 +33,17 @@ class Layer:
 
 class DecoderStack:
     def __init__(self, src, prefix, n_layers, D, H, KVH, eps, bias, rope, pool, kv_layer0=0, first_fp16=False,
-                 attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT, mlp_w8=False, mlp_w8_rows=16):
+                 attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT, mlp_w8=False, mlp_w8_rows=16, mlp_w4=False):
         """mlp_w8: gate/up and down under weight-only FP8 (ops.PackedLinearW8: the model's MLP weights become
         q * 2^e; forwards of <= 16 rows stream the codes, larger ones the exact bf16 image of the same weights).
         mlp_w8_rows: 16, 64 or 128, PackedLinearW8's stream_rows (64: 17..64-row forwards stream the codes too; 128:
-        65..128-row ones as well)."""
+        65..128-row ones as well).
+        mlp_w4: gate/up and down under weight-only MXFP4 instead (ops.PackedLinearW4: q * 2^e with e2m1 codes and one
+        e per 32-column block; forwards of <= 16 rows stream the codes for the GEMMs of ops.W4_POLICY, everything else
+        runs the exact bf16 image)."""
+        if mlp_w8 and mlp_w4:
+            raise ValueError("mlp_w8 and mlp_w4 are two models of the same weights: pick one")
+        self.mlp_w4 = bool(mlp_w4)
         self.mlp_w8 = bool(mlp_w8)
         self.mlp_w8_rows = mlp_w8_rows
         self.n, self.D, self.H, self.KVH, self.hd, self.eps = n_layers, D, H, KVH, D // H, eps
@@ -67,6 +73,11 @@ class DecoderStack:
                                       stream_rows=mlp_w8_rows)
                 L.down = PackedLinearW8(src.get(q + "mlp.down_proj.weight", torch.bfloat16), receive=recv,
                                         stream_rows=mlp_w8_rows)
+            elif self.mlp_w4:
+                recv = isinstance(src, ReceiveSource)
+                L.gu = PackedLinearW4(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
+                                      swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16), receive=recv)
+                L.down = PackedLinearW4(src.get(q + "mlp.down_proj.weight", torch.bfloat16), receive=recv)
             else:
                 L.gu = PackedLinear(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
                                     swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16))
@@ -90,6 +101,11 @@ class DecoderStack:
     def mlp_fp8_bytes(self):
         """The FP8 codes and scales held beside the bf16 image (0 without mlp_w8)."""
         return sum(getattr(L.gu, "fp8_nbytes", 0) + getattr(L.down, "fp8_nbytes", 0) for L in self.layers)
+
+    @property
+    def mlp_fp4_bytes(self):
+        """The MXFP4 codes and scale bytes held beside the bf16 image (0 without mlp_w4)."""
+        return sum(getattr(L.gu, "fp4_nbytes", 0) + getattr(L.down, "fp4_nbytes", 0) for L in self.layers)
 
     def workspace(self, T, nsplit, device):
         """Preallocated per-forward buffers for T tokens (graph capture must not allocate)."""
@@ -150,8 +166,9 @@ class DecoderStack:
         # fills or reads the packed x*gamma (the next q|k|v reads the fp32 rows); the o input stays packed
         # (17..64 rows under mlp_w8_rows=64 likewise, per GEMM: an FP8 gate/up leaves the o's packed x*gamma unread,
         # an FP8 down fills none for the next q|k|v; 65..128 rows under mlp_w8_rows=128 pack nothing either way)
+        # (mlp_w4 likewise at <= 16 rows, per GEMM that streams the MXFP4 codes)
         xgp_gu = xgp_qkv = xgp
-        if self.mlp_w8 and self.layers:
+        if (self.mlp_w8 or self.mlp_w4) and self.layers:
             if self.layers[0].gu.streams(T):
                 xgp_gu = None
             if self.layers[0].down.streams(T):

@@ -125,12 +125,16 @@ class FakeQuantSource:
     """`inner` with the Qwen2 MLP weights (gate_proj, up_proj, down_proj of every model.layers.N) replaced by their
     weight-only FP8 image W' = q * 2^e (fo.quant; quantised on the device from the bf16 weight, returned
     dequantised -- exactly bf16 values).  An engine with mlp_weights="fp8" serves its weights through this, so the
-    oracle, or a second engine of either mode, can be built on the same model."""
+    oracle, or a second engine of either mode, can be built on the same model.
+    fmt: "fp8" (default) or "mxfp4", the image of mlp_weights="mxfp4": W' = q * 2^e with e2m1 codes and one e per
+    32-column block (fo.quant.quantize_blocks_e2m1)."""
 
     MLP = ("mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
 
-    def __init__(self, inner):
-        self.inner = inner
+    def __init__(self, inner, fmt="fp8"):
+        if fmt not in ("fp8", "mxfp4"):
+            raise ValueError(f"FakeQuantSource format must be 'fp8' or 'mxfp4', got {fmt!r}")
+        self.inner, self.fmt = inner, fmt
 
     def __contains__(self, name):
         return name in self.inner
@@ -138,4 +142,5 @@ class FakeQuantSource:
     def get(self, name, dtype=torch.float32):
         if not (name.startswith("model.layers.") and name.endswith(self.MLP)):
             return self.inner.get(name, dtype)
-        return ops.quant_w8(self.inner.get(name, torch.bfloat16))[2].to(dtype)
+        quant = ops.quant_w4 if self.fmt == "mxfp4" else ops.quant_w8
+        return quant(self.inner.get(name, torch.bfloat16))[2].to(dtype)

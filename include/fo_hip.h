@@ -231,6 +231,39 @@ int fo_gemm_w8_rows128(const float* X, int ldx, int M, int K, const void* q, con
                        int swiglu, float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters,
                        const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
                        int* sgroups, hipStream_t stream);
+/* Weight-only MXFP4 (OCP e2m1 codes, one power-of-two scale per 32 elements) for <= 16-row launches:
+ * W'[n, k] = q[n, k] * 2^e[n, k / 32].  q is an e2m1 code: magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 as codes 0..7, bit 3
+ * the sign, copied from the weight's sign bit even where the magnitude rounds to 0.  e is one integer per (output row,
+ * block of 32 consecutive k): the smallest with max|W[n, block]| * 2^-e <= 6, taken from the float's exponent E and
+ * mantissa (e = E - 2 + (mantissa > 1.5)), at least -125 (so that every non-zero q * 2^e is a normal bf16) and 0 for an
+ * all-zero block.  W * 2^-e (exact, or an underflow that rounds to 0 anyway) is rounded to the nearest magnitude, ties
+ * to the even code (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4); nothing saturates.  q * 2^e
+ * has 2 significant bits, so W' is exactly representable in bf16.  The CPU definition is fo/quant.py.
+ * Packed layout: codes [tile][ceil(K/128)][64 lanes][16 bytes] (fo_quant_w4_bytes(N, K) bytes per 16 ceil(N/16) rows),
+ * tile t = rows 16 t .. + 16.  Lane l of code step s holds row 16 t + (l & 15); its bytes 4 j .. 4 j + 3 are its MFMA B
+ * fragment of k-step 4 s + j, columns 128 s + 32 j + 8 (l >> 4) .. + 8, two codes per byte with the lower column in the
+ * low nibble.  Scales: E8M0 bytes e + 127 at [tile][ceil(K/128)][16 rows][4] (fo_quant_w4_scale_bytes(N, K)), byte j
+ * for k-step 4 s + j.  Columns K .. 128 ceil(K/128) and rows beyond N are zero codes with scale byte 127.  K % 32 == 0.
+ * fo_quant_w4: as fo_quant_w8 (tile_base / tile_stride interleave the SwiGLU pair; wdq, optional, receives W' as bf16
+ *   [N][K] contiguous, from which fo_pack_weight builds the bf16 image).
+ * fo_gemm_w4: fo_gemm_w8's arguments and epilogue semantics (plain, + Y, swiglu, the RMSNorm consumer and producer)
+ *   with `scale` the E8M0 bytes, applied as the codes are decoded to bf16 (v_cvt_scalef32_pk_bf16_fp4), so the fp32
+ *   sums need no column scale.  M <= 16 only: any other M, K % 32 != 0, an ntiles that is not the weight's, a NULL
+ *   scale and a producer on a SwiGLU launch are refused on the host before any HIP call; more rows run the bf16 image
+ *   through fo_gemm.  One workgroup per output tile, its waves splitting K (k_w4); the SwiGLU pair at K = 3584
+ *   X-stationary and persistent (k_w4_xs); long-K plain launches (the Qwen2 down) split K across workgroups and
+ *   merge inside the launch in split order where ws and counters are given (k_w4_sk).  Deterministic, capture-safe.
+ * fo_gemm_w4_counts: the launches issued per form since the last reset (general, xs, sk) into out[0 .. min(n, 3));
+ *   returns 3.  These kernels have no FoLaunchKind. */
+long long fo_quant_w4_bytes(int N, int K);
+long long fo_quant_w4_scale_bytes(int N, int K);
+int fo_quant_w4(const void* W, int src_bf16, int N, int K, int ldw, void* q, void* scale, void* wdq, int tile_base,
+                int tile_stride, hipStream_t stream);
+int fo_gemm_w4(const float* X, int ldx, int M, int K, const void* q, const void* scale, int ntiles, int N, int swiglu,
+               float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters, const float* rstats,
+               int rgroups, float eps, float* sout, const float* gnext, float* yg, int* sgroups, hipStream_t stream);
+int fo_gemm_w4_counts(long long* out, int n);
+int fo_gemm_w4_counts_reset(void);
 /* Software-pipelined one-row-tile fp32-X weight-stream GEMMs (M <= 16, >= 64 MiB of weights: the next
  * k-group's weights + X in flight during this group's MFMAs).  3 (default): the measured policy; 0: plain
  * loops; 1 / 2: every such GEMM pipelined with 4 / 2 k-steps per group (sweeps).  Unset, the

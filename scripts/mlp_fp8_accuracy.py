@@ -1,10 +1,10 @@
-"""What mlp_weights="fp8" costs against the unquantised model on the full-depth flow of tests/test_full_depth_gpu.py
-(real geometry, 28 Qwen2 layers, the engine's counter-hash weights): the system prompt, question.wav's 13 chunks (the
+"""What mlp_weights="fp8" (or, with the second argument, "mxfp4") costs against the unquantised model on the
+full-depth flow of tests/test_full_depth_gpu.py (real geometry, 28 Qwen2 layers, the engine's counter-hash weights): the system prompt, question.wav's 13 chunks (the
 reference's fbank features, tests/golden/fbank.npz) with the user chat prefix, the assistant prefix and greedy text
 steps.  Prints the state-probability differences per chunk, the decision-row logit differences under teacher forcing
 with the bf16 engine's ids (and how often the arg-max agrees, against the bf16 top-2 margin), and where the two
 engines' own greedy texts part.  A measurement, not a test.
-python scripts/mlp_fp8_accuracy.py [steps] (GPU only)"""
+python scripts/mlp_fp8_accuracy.py [steps] [fp8|mxfp4] (GPU only)"""
 import os
 import sys
 
@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "freeze-omni_amd"))
 from fo.engine import FreezeOmniEngine  # noqa: E402
 
 STEPS = int(sys.argv[1]) if len(sys.argv) > 1 else 32
+FMT = sys.argv[2] if len(sys.argv) > 2 else "fp8"
 SYS_IDS = list(range(1, 16))
 USER_PREFIX = [151645, 198, 151644, 872, 198]
 ASSIST_PREFIX = [151645, 198, 151644, 77091, 198]
@@ -60,7 +61,8 @@ eng = engine("bf16")
 p0, l0, t0 = flow(eng)
 del eng
 torch.cuda.empty_cache()
-eng = engine("fp8")
+eng = engine(FMT)
+print(f"mlp_weights={FMT} against bf16:")
 p1, l1, t1f = flow(eng, forced=t0)
 _, _, t1 = flow(eng)
 dp = np.abs(p1 - p0)

@@ -1,7 +1,9 @@
 """Wall and device time of one text-decode step (TextGraph: 28 Qwen2 layers + lm_head + sampler) for B
 sessions at real geometry after a ~150-token context, as the bench's speak stage runs it.
-python scripts/text_step_time.py [B] [steps] [fp8] (GPU only; run under rocprofv3 --kernel-trace --stats for
-the per-kernel split).  The third argument `fp8` turns mlp_weights="fp8" on (the MLP streams FP8 codes)."""
+python scripts/text_step_time.py [B] [steps] [fp8|mxfp4] (GPU only; run under rocprofv3 --kernel-trace --stats for
+the per-kernel split).  The third argument `fp8` turns mlp_weights="fp8" on (the MLP streams FP8 codes); `mxfp4` times
+the bf16, fp8 and mxfp4 engines one after the other in the same call, so the three lines share a process and a clock."""
+import gc
 import os
 import sys
 import time
@@ -16,23 +18,34 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 MODE = sys.argv[3] if len(sys.argv) > 3 else "bf16"
 dev = torch.device("cuda:0")
-eng = FreezeOmniEngine(os.path.join(ROOT, "configs", "real"), device=dev, max_sessions=max(8, B), mlp_weights=MODE)
-base = eng.system_role("<|im_start|>system\nYou are a helpful assistant.")
-kvs = [base.fork() for _ in range(B)]
-ctx = list(range(100, 230))
-eng.text_step([(kv, ctx) for kv in kvs])          # ~150-token context per session
-ids, _ = eng.text_step([(kv, [1]) for kv in kvs])
-for _ in range(5):
-    ids, _ = eng.text_step([(kv, [i]) for kv, i in zip(kvs, ids)])
-torch.cuda.synchronize()
-t = time.perf_counter()
-for _ in range(N):
-    ids, _ = eng.text_step([(kv, [i]) for kv, i in zip(kvs, ids)])
-torch.cuda.synchronize()
-dt = (time.perf_counter() - t) / N
-gb = (eng.llm.stack.weight_bytes + eng.llm.lm_head.nbytes) / 1e9
-if MODE == "fp8":   # the MLP streams its codes instead of its bf16 image
+
+
+def run(mode):
+    eng = FreezeOmniEngine(os.path.join(ROOT, "configs", "real"), device=dev, max_sessions=max(8, B), mlp_weights=mode)
+    base = eng.system_role("<|im_start|>system\nYou are a helpful assistant.")
+    kvs = [base.fork() for _ in range(B)]
+    ctx = list(range(100, 230))
+    eng.text_step([(kv, ctx) for kv in kvs])          # ~150-token context per session
+    ids, _ = eng.text_step([(kv, [1]) for kv in kvs])
+    for _ in range(5):
+        ids, _ = eng.text_step([(kv, [i]) for kv, i in zip(kvs, ids)])
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    for _ in range(N):
+        ids, _ = eng.text_step([(kv, [i]) for kv, i in zip(kvs, ids)])
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t) / N
+    gb = (eng.llm.stack.weight_bytes + eng.llm.lm_head.nbytes) / 1e9
     L = eng.llm.stack.layers
-    gb += (eng.llm.mlp_fp8_bytes - sum(l.gu.nbytes + l.down.nbytes for l in L)) / 1e9
-print(f"text step B={B} mlp_weights={MODE}: {dt * 1e3:.3f} ms wall/step, {gb:.2f} GB weights -> {gb / dt / 1e3:.2f} TB/s "
-      f"(roofline {gb / 8.0:.3f} ms at 8 TB/s)", flush=True)
+    if mode == "fp8":   # the MLP streams its codes instead of its bf16 image
+        gb += (eng.llm.mlp_fp8_bytes - sum(l.gu.nbytes + l.down.nbytes for l in L)) / 1e9
+    if mode == "mxfp4":   # ... the GEMMs of ops.W4_POLICY do
+        gb += sum(lin.fp4_nbytes - lin.nbytes for l in L for lin in (l.gu, l.down) if lin.streams(B)) / 1e9
+    print(f"text step B={B} mlp_weights={mode}: {dt * 1e3:.3f} ms wall/step, {gb:.2f} GB weights -> {gb / dt / 1e3:.2f} TB/s "
+          f"(roofline {gb / 8.0:.3f} ms at 8 TB/s)", flush=True)
+
+
+for mode in (("bf16", "fp8", "mxfp4") if MODE == "mxfp4" else (MODE,)):
+    run(mode)
+    gc.collect()
+    torch.cuda.empty_cache()
