@@ -53,6 +53,8 @@ def get_args(argv=None):
                         "weight-only MXFP4 (e2m1 codes x a power of two per 32 columns)")
     p.add_argument("--llm_mlp_fp8_rows", type=int, choices=[16, 64, 128], default=16,
                    help="with --llm_mlp_weights fp8: the most rows of a Qwen2 step that stream the FP8 codes")
+    p.add_argument("--llm_mlp_mxfp4_rows", type=int, choices=[16, 64], default=16,
+                   help="with --llm_mlp_weights mxfp4: the most rows of a Qwen2 step that stream the MXFP4 codes")
     p.add_argument("--llm_kv", choices=["fp32", "bf16"], default="fp32",
                    help="Qwen2 paged KV cache element: fp32, or bf16 (half the memory and attention bytes)")
     p.add_argument("--role", default="You are a helpful assistant.")

@@ -1,12 +1,12 @@
-// Weight-only MXFP4 (OCP e2m1 codes, one power-of-two scale per 32 elements) GEMMs for the Qwen2 MLP at <= 16 rows,
-// and their quantiser.
+// Weight-only MXFP4 (OCP e2m1 codes, one power-of-two scale per 32 elements) GEMMs for the Qwen2 MLP at <= 16 rows
+// (fo_gemm_w4) and at 17..64 rows (fo_gemm_w4_rows), and their quantiser.
 //
 //   W'[n, k] = q[n, k] * 2^e[n, k / 32]   q an e2m1 code (0, 0.5, 1, 1.5, 2, 3, 4, 6 and a sign bit), e one integer
 //                                         per (output row, block of 32 columns), stored as the E8M0 byte e + 127
 //   Y[M, N]  = epilogue( X[M, K] (fp32, split into bf16 hi + lo) . W'^T )
 //
 // An e2m1 value has 2 significant bits, so q * 2^e is exactly a bf16 value: W' has an exact bf16 image, which the
-// engine keeps packed for the bf16 kernels and runs above 16 rows.  The kernels here stream the codes -- a quarter of
+// engine keeps packed for the bf16 kernels and runs wherever the codes are not streamed.  The kernels here stream the codes -- a quarter of
 // the bytes of that image, plus 1/32 of scales -- decode them to bf16 in registers with the block scale applied
 // (v_cvt_scalef32_pk_bf16_fp4: exact) and run the same bf16 MFMAs, so both paths compute X . W'^T to the
 // accumulation-order difference that already exists between the bf16 kernels.  The block scale cannot multiply the
@@ -16,7 +16,8 @@
 // Code layout (include/fo_hip.h): [tile][K128][64 lanes][16 bytes], a lane's dword j being its 8-element MFMA
 // B fragment of k-step 4 s + j (two codes per byte, the lower column in the low nibble), K padded to a multiple of
 // 128 with zero codes; scale bytes [tile][K128][16 rows][4].  fo_gemm_w4: k_w4 (general), k_w4_xs (the SwiGLU pair at
-// K = 3584) or k_w4_sk (long-K plain), the forms of fo_gemm_w8.hip.
+// K = 3584) or k_w4_sk (long-K plain), the forms of fo_gemm_w8.hip; fo_gemm_w4_rows: k_w4_rows, then k_w8_rows_merge
+// (fo_gemm_wq.h) where K is split.
 #include <stdlib.h>
 
 #include <atomic>
@@ -283,6 +284,144 @@ __global__ __launch_bounds__(NW * 64) void k_w4_xs(W8Args a, int units) {
   }
 }
 
+// ---- 17..64 rows (RB = 2..4 row blocks of 16; fo_gemm_w4_rows): k_w8_rows's design (fo_gemm_w8.hip) on 128-column
+// code steps.  Workgroup (g, sp): the sp-th of S slices of the code steps for units [ub, ue) of column group g; a unit
+// is a packed tile pair (the (gate, up) pair, or two adjacent plain tiles: the second of an odd count's last pair lies
+// past both descriptors and loads zero codes under a zero scale byte).  Wave w owns KPW code steps = 4 KPW k-steps of
+// the slice: their X fragments of all RB row blocks are split once (hi in VGPRs, lo in its LDS region; k-steps at or
+// past K -- K % 128 may be 32, 64 or 96 -- hold zeros and read no X), each 16-byte code load comes with its 4-byte
+// scale load and is decoded once per unit (dec4, with the block's 2^e) to feed RB x (hi, lo) MFMAs per k-step, the
+// next unit's codes and scales in flight meanwhile.  Per unit the NW partial tiles are summed through LDS in wave
+// order (both tiles in one round where the LDS allows).  S == 1: the epilogue follows.  S > 1: the sums are stored as
+// split sp's slab of `ws` ([S][RB * 16][ntiles * 16] floats) and k_w8_rows_merge (fo_gemm_wq.h, unscaled), the next
+// launch, sums the slabs in split order and runs the epilogue.
+template <int NW, int KPW, int RB, bool SW>
+__global__ __launch_bounds__(NW * 64) void k_w4_rows(W8Args a, int S, int per, float* ws) {
+  constexpr int ROWS = RB * 16, NTH = NW * 64, NE = ROWS * 16, EPT = (NE + NTH - 1) / NTH;
+  constexpr int PT = (NW * RB * 4 * KPW * 1024 + NW * 2 * ROWS * 17 * 4 + 512 <= 160 * 1024) ? 2 : 1;
+  __shared__ bf16x8 xlo[NW][RB][4 * KPW][64];
+  __shared__ float part[NW][PT][ROWS][17];
+  __shared__ float rstd_s[ROWS];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int G = gridDim.x, g = blockIdx.x, sp = blockIdx.y;
+  const int units = (a.ntiles + 1) >> 1, tiles = (a.N + 15) / 16;   // (tiles: output tiles, the statistics' groups)
+  const int ub = (int)((long)units * g / G), ue = (int)((long)units * (g + 1) / G);
+  const W4Srd d = w4_srd(a);   // (exactly the codes and the scale bytes)
+  // this wave's code steps: [k0, k0 + nj) inside the slice [sp * per, (sp + 1) * per) and inside KK (wave-uniform)
+  const int k0 = sp * per + wave * KPW;
+  const int nj = max(0, min(KPW, min(a.KK, (sp + 1) * per) - k0));
+  u32x4 q[2][2][KPW];
+  unsigned sc[2][2][KPW];
+  auto issue = [&](u32x4 (&qq)[2][KPW], unsigned (&ss)[2][KPW], int u) {   // u >= ue: no load issued
+    if (u < ue) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int j = 0; j < KPW; ++j)
+          if (j < nj) {
+            qq[t][j] = w4_codes(d, lane, (2 * u + t) * a.KK + k0 + j);
+            ss[t][j] = w4_scales(d, lane, (2 * u + t) * a.KK + k0 + j);
+          }
+    }
+  };
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int j = 0; j < KPW; ++j) {   // code steps past the slice: zero codes under a zero scale byte
+        q[b][t][j] = u32x4{0u, 0u, 0u, 0u};
+        sc[b][t][j] = 0u;
+      }
+  issue(q[0], sc[0], ub);
+  issue(q[1], sc[1], ub + 1);
+  bf16x8 zero;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) zero[i] = (__bf16)0.f;
+  bf16x8 xh[RB][4 * KPW];
+#pragma unroll
+  for (int r = 0; r < RB; ++r) {
+    const int row = min(r * 16 + (lane & 15), a.M - 1);   // rows >= M: computed, never stored or summed
+    const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
+#pragma unroll
+    for (int j = 0; j < 4 * KPW; ++j) {
+      bf16x8 hi = zero, lo = zero;
+      const int col = (4 * k0 + j) * 32;   // (K % 128 != 0: the last code step's k-steps at or past K)
+      if ((j >> 2) < nj && col < a.K)
+        split8(reinterpret_cast<const float4*>(xp + col)[0], reinterpret_cast<const float4*>(xp + col)[1], hi, lo);
+      xh[r][j] = hi;
+      xlo[wave][r][j][lane] = lo;
+    }
+  }
+  if (S == 1) {   // the consumer's rstd of every row (rows >= M from the clamped row)
+    if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane, 0, ROWS);
+    __syncthreads();
+  }
+  const int Ncols = a.ntiles * 16;
+  float* slab = ws + (size_t)sp * ROWS * Ncols;
+  auto unit = [&](u32x4 (&qq)[2][KPW], unsigned (&ss)[2][KPW], int u) {
+    float v[2][EPT];
+#pragma unroll
+    for (int t0 = 0; t0 < 2; t0 += PT) {
+      f32x4 acc[PT][RB];
+#pragma unroll
+      for (int p = 0; p < PT; ++p) {
+#pragma unroll
+        for (int r = 0; r < RB; ++r) acc[p][r] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < KPW; ++j)
+#pragma unroll
+          for (int h = 0; h < 4; ++h) {
+            const bf16x8 w = dec4(qq[t0 + p][j][h], (ss[t0 + p][j] >> (8 * h)) & 0xffu);
+#pragma unroll
+            for (int r = 0; r < RB; ++r) {
+              acc[p][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[r][4 * j + h], w, acc[p][r], 0, 0, 0);
+              acc[p][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xlo[wave][r][4 * j + h][lane], w, acc[p][r], 0, 0, 0);
+            }
+          }
+      }
+      if (t0 + PT == 2) issue(qq, ss, u + 2);   // (the unit's codes are decoded: its buffer takes the unit after next)
+      __syncthreads();  // the previous reduction has read part[]
+#pragma unroll
+      for (int p = 0; p < PT; ++p)
+#pragma unroll
+        for (int r = 0; r < RB; ++r) w8_store_tile(part[wave][p], acc[p][r], lane, r * 16);
+      __syncthreads();
+#pragma unroll
+      for (int p = 0; p < PT; ++p)
+#pragma unroll
+        for (int i = 0; i < EPT; ++i) {
+          const int e = threadIdx.x + i * NTH;
+          float s = 0.f;
+          if (e < NE) {
+#pragma unroll
+            for (int w = 0; w < NW; ++w) s += part[w][p][e >> 4][e & 15];
+            if (S > 1 && 2 * u + t0 + p < a.ntiles)
+              slab[(size_t)(e >> 4) * Ncols + (2 * u + t0 + p) * 16 + (e & 15)] = s;
+          }
+          v[t0 + p][i] = s;
+        }
+    }
+    if (S == 1) {
+#pragma unroll
+      for (int i = 0; i < EPT; ++i) {
+        const int e = threadIdx.x + i * NTH;   // (NTH % 16 == 0: a row's 16 columns are one 16-lane row of a wave)
+        const int rr = e < NE ? e >> 4 : ROWS, c = e & 15;
+        if constexpr (SW) {
+          w8_epilogue<true, false>(a, u, tiles, rr, c, v[0][i], v[1][i], rstd_s);
+        } else {
+          w8_epilogue<false, false>(a, 2 * u, tiles, rr, c, v[0][i], 0.f, rstd_s);
+          if (2 * u + 1 < a.ntiles) w8_epilogue<false, false>(a, 2 * u + 1, tiles, rr, c, v[1][i], 0.f, rstd_s);
+        }
+      }
+    }
+  };
+  for (int u = ub; u < ue; u += 2) {   // (workgroup-uniform: every wave reaches unit's barriers)
+    unit(q[0], sc[0], u);
+    if (u + 1 < ue) unit(q[1], sc[1], u + 1);
+  }
+}
+
 // ---- quantiser.  One workgroup per source row n, one 32-column block per thread and pass: the block's amax, e from
 // its exponent and mantissa (the smallest integer with amax * 2^-e <= 6 = 1.5 * 2^2, at least -125 so that every
 // non-zero q * 2^e is a normal bf16; 0 for an all-zero block), W * 2^-e (exact, or an underflow that rounds to 0 anyway)
@@ -352,8 +491,40 @@ int w4_cus() {
   return g_cus;
 }
 
-// the launch counters of the three forms (fo_gemm_w4_counts): general, xs, sk
+// the launch counters of the three <= 16-row forms (fo_gemm_w4_counts): general, xs, sk; and the calls of
+// fo_gemm_w4_rows (fo_gemm_w4_rows_count)
 std::atomic<long long> g_w4_launches[3];
+std::atomic<long long> g_w4_rows_calls;
+
+// What the two GEMM entries share: the checks of everything but the workspace (all before the entry's first HIP call),
+// then W8Args (with KK) and the output tile count.  `fn` is the entry's name, [m_lo, m_hi] its row band and `serves`
+// what its refusal says of the band.
+int w4_args(const char* fn, int m_lo, int m_hi, const char* serves, const float* X, int ldx, int M, int K, const void* Q,
+            const void* scale, int ntiles, int N, int swiglu, float* Y, int ldy, int residual, const float* rstats,
+            int rgroups, float eps, float* sout, const float* gnext, float* yg, W8Args& a, int& units) {
+  FO_REQUIRE(M > 0 && N > 0 && K > 0, "%s: bad shape M=%d N=%d K=%d", fn, M, N, K);
+  FO_REQUIRE(M >= m_lo && M <= m_hi, "%s: M=%d rows, %s", fn, M, serves);
+  FO_REQUIRE((K & 31) == 0, "%s: K=%d must be a multiple of 32", fn, K);
+  FO_REQUIRE(X && Q && Y, "%s: NULL X, Q or Y", fn);
+  FO_REQUIRE(scale, "%s: NULL scale (the E8M0 block bytes of fo_quant_w4)", fn);
+  FO_REQUIRE(ldx >= K && (ldx & 3) == 0 && ((unsigned long long)X & 15) == 0,
+             "%s: X needs ldx=%d >= K=%d, ldx %% 4 == 0 and 16-byte alignment", fn, ldx, K);
+  FO_REQUIRE(ldy >= N, "%s: ldy=%d < N=%d", fn, ldy, N);
+  units = (N + 15) / 16;
+  FO_REQUIRE(!swiglu || (ntiles & 1) == 0, "%s: swiglu with an odd ntiles=%d (gate/up tiles come in pairs)", fn, ntiles);
+  // ntiles is the extent of Q and scale (the descriptors' range): (gate, up) pairs for SwiGLU
+  FO_REQUIRE(ntiles == (swiglu ? 2 : 1) * units, "%s: ntiles=%d packed tiles for N=%d%s", fn, ntiles, N,
+             swiglu ? " SwiGLU columns" : " columns");
+  FO_REQUIRE(!rstats || rgroups > 0, "%s: rstats without rgroups", fn);
+  FO_REQUIRE(!sout || (!swiglu && (!yg || gnext)), "%s: sout needs a non-SwiGLU launch, yg needs gnext", fn);
+  FO_REQUIRE(sout || !yg, "%s: yg comes with sout", fn);
+  FO_REQUIRE(!(swiglu && residual), "%s: swiglu with residual unsupported", fn);
+  const int KK = (K + 127) / 128;
+  FO_REQUIRE((long long)(ntiles + 4) * KK * 1024 < (1ll << 31), "%s: ntiles=%d x K=%d codes exceed 2 GiB", fn, ntiles, K);
+  a = W8Args{X,        Q,    reinterpret_cast<const float*>(scale), Y,  ldx,    ldy,     M, K, N, ntiles, KK,
+             residual, sout, gnext,                                 yg, rstats, rgroups, eps};
+  return 0;
+}
 
 }  // namespace
 
@@ -381,37 +552,22 @@ int fo_gemm_w4_counts(long long* out, int n) {
 }
 int fo_gemm_w4_counts_reset(void) {
   for (int i = 0; i < 3; ++i) g_w4_launches[i].store(0, std::memory_order_relaxed);
+  g_w4_rows_calls.store(0, std::memory_order_relaxed);
   return 0;
 }
+long long fo_gemm_w4_rows_count(void) { return g_w4_rows_calls.load(std::memory_order_relaxed); }
 
 int fo_gemm_w4(const float* X, int ldx, int M, int K, const void* Q, const void* scale, int ntiles, int N, int swiglu,
                float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters, const float* rstats,
                int rgroups, float eps, float* sout, const float* gnext, float* yg, int* sgroups, hipStream_t stream) {
   // every check before the first HIP call
-  FO_REQUIRE(M > 0 && N > 0 && K > 0, "fo_gemm_w4: bad shape M=%d N=%d K=%d", M, N, K);
-  FO_REQUIRE(M <= 16, "fo_gemm_w4: M=%d rows, the MXFP4 stream serves M <= 16 (more rows run the bf16 image)", M);
-  FO_REQUIRE((K & 31) == 0, "fo_gemm_w4: K=%d must be a multiple of 32", K);
-  FO_REQUIRE(X && Q && Y, "fo_gemm_w4: NULL X, Q or Y");
-  FO_REQUIRE(scale, "fo_gemm_w4: NULL scale (the E8M0 block bytes of fo_quant_w4)");
-  FO_REQUIRE(ldx >= K && (ldx & 3) == 0 && ((unsigned long long)X & 15) == 0,
-             "fo_gemm_w4: X needs ldx=%d >= K=%d, ldx %% 4 == 0 and 16-byte alignment", ldx, K);
-  FO_REQUIRE(ldy >= N, "fo_gemm_w4: ldy=%d < N=%d", ldy, N);
-  const int units = (N + 15) / 16;
-  FO_REQUIRE(!swiglu || (ntiles & 1) == 0, "fo_gemm_w4: swiglu with an odd ntiles=%d (gate/up tiles come in pairs)",
-             ntiles);
-  // ntiles is the extent of Q and scale (the descriptors' range): (gate, up) pairs for SwiGLU
-  FO_REQUIRE(ntiles == (swiglu ? 2 : 1) * units, "fo_gemm_w4: ntiles=%d packed tiles for N=%d%s", ntiles, N,
-             swiglu ? " SwiGLU columns" : " columns");
-  FO_REQUIRE(!rstats || rgroups > 0, "fo_gemm_w4: rstats without rgroups");
-  FO_REQUIRE(!sout || (!swiglu && (!yg || gnext)), "fo_gemm_w4: sout needs a non-SwiGLU launch, yg needs gnext");
-  FO_REQUIRE(sout || !yg, "fo_gemm_w4: yg comes with sout");
-  FO_REQUIRE(!(swiglu && residual), "fo_gemm_w4: swiglu with residual unsupported");
-  const int KK = (K + 127) / 128;
-  FO_REQUIRE((long long)(ntiles + 4) * KK * 1024 < (1ll << 31), "fo_gemm_w4: ntiles=%d x K=%d codes exceed 2 GiB",
-             ntiles, K);
-  const W8Args a{X,    Q,     reinterpret_cast<const float*>(scale), Y,  ldx,    ldy,     M,
-                 K,    N,     ntiles,                                KK, residual, sout,   gnext,
-                 yg,   rstats, rgroups,                              eps};
+  W8Args a;
+  int units;
+  if (const int rc = w4_args("fo_gemm_w4", 1, 16, "the MXFP4 stream serves M <= 16 (more rows run the bf16 image)", X, ldx,
+                             M, K, Q, scale, ntiles, N, swiglu, Y, ldy, residual, rstats, rgroups, eps, sout, gnext, yg,
+                             a, units))
+    return rc;
+  const int KK = a.KK;
   if (sgroups) *sgroups = units;
   if (swiglu && K == 3584) {
     const int G = units < w4_cus() ? units : w4_cus();
@@ -447,6 +603,65 @@ int fo_gemm_w4(const float* X, int ldx, int M, int K, const void* Q, const void*
   }
   g_w4_launches[0].fetch_add(1, std::memory_order_relaxed);
   return fo::check_launch("fo_gemm_w4");
+}
+
+int fo_gemm_w4_rows(const float* X, int ldx, int M, int K, const void* Q, const void* scale, int ntiles, int N,
+                    int swiglu, float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters,
+                    const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
+                    int* sgroups, hipStream_t stream) {
+  // every check before the first HIP call
+  W8Args a;
+  int units;
+  if (const int rc = w4_args("fo_gemm_w4_rows", 17, 64,
+                             "this MXFP4 stream serves 17 <= M <= 64 (fo_gemm_w4 serves M <= 16, more than 64 rows run "
+                             "the bf16 image)",
+                             X, ldx, M, K, Q, scale, ntiles, N, swiglu, Y, ldy, residual, rstats, rgroups, eps, sout,
+                             gnext, yg, a, units))
+    return rc;
+  const int KK = a.KK;
+  // NW waves x KPW code steps of X per K slice (hi in VGPRs, lo in LDS), starting from fo_gemm_w8_rows's columns per
+  // wave (7 x 2 at 2 row blocks, 7 x 1 at 3, 6 x 1 at 4) and keeping what measured best per GEMM against one
+  // alternative each (builder-run, profiles/mlp_mxfp4_rows_gemm_ab.txt; gate/up / down in us): 2 row blocks 7 x 2
+  // (41.6 / 26.4 against 42.2 / 27.8 for 7 x 1); 3 row blocks 7 x 1 for SwiGLU (54.2 against 55.1 for 8 x 1) and 8 x 1
+  // for plain (32.5 against 35.6 for 7 x 1); 4 row blocks 7 x 1 for SwiGLU, which reduces a tile at a time (70.9
+  // against 73.3 for 6 x 1), and 6 x 1 for plain (45.1 against 46.3).  S slices of `per` code steps, units of two
+  // packed tiles, about one workgroup per CU.  S > 1: the slabs are merged by a second launch (k_w8_rows_merge), one
+  // small workgroup per (tile, row block)
+  const int RB = (M + 15) / 16;
+  const int NW = RB == 2 ? 7 : (RB == 3 ? (swiglu ? 7 : 8) : (swiglu ? 7 : 6)), KPW = RB == 2 ? 2 : 1;
+  const int S = (KK + NW * KPW - 1) / (NW * KPW), per = (KK + S - 1) / S;
+  const int pairs = (ntiles + 1) / 2;
+  const int per_split = w4_cus() / S < 1 ? 1 : w4_cus() / S;
+  const int G = pairs < per_split ? pairs : per_split;
+  if (S > 1) {
+    const long long need = (long long)S * RB * 16 * ntiles * 16;
+    FO_REQUIRE(ws && need <= ws_floats,
+               "fo_gemm_w4_rows: K=%d splits over %d workgroups: split-K workspace too small (%lld floats needed, "
+               "%lld given)", K, S, need, ws ? ws_floats : 0ll);
+  }
+  (void)counters;
+  if (sgroups) *sgroups = units;
+  const dim3 grid(G, S), block(NW * 64);
+#define FO_W4_ROWS(NW_, KPW_, RB_, SW_) \
+  hipLaunchKernelGGL((k_w4_rows<NW_, KPW_, RB_, SW_>), grid, block, 0, stream, a, S, per, ws)
+  if (RB == 2) {
+    if (swiglu) FO_W4_ROWS(7, 2, 2, true);
+    else FO_W4_ROWS(7, 2, 2, false);
+  } else if (RB == 3) {
+    if (swiglu) FO_W4_ROWS(7, 1, 3, true);
+    else FO_W4_ROWS(8, 1, 3, false);
+  } else {
+    if (swiglu) FO_W4_ROWS(7, 1, 4, true);
+    else FO_W4_ROWS(6, 1, 4, false);
+  }
+#undef FO_W4_ROWS
+  if (S > 1) {
+    const int rc = fo::check_launch("fo_gemm_w4_rows");
+    if (rc) return rc;
+    launch_merge<false>(a, swiglu, units, RB, S, ws, stream);
+  }
+  g_w4_rows_calls.fetch_add(1, std::memory_order_relaxed);
+  return fo::check_launch("fo_gemm_w4_rows");
 }
 
 }  // extern "C"

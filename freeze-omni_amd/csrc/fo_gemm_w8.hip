@@ -399,38 +399,7 @@ __global__ __launch_bounds__(NW * 64) void k_w8_rows(W8Args a, int S, int per, f
   }
 }
 
-// The merge of k_w8_rows's (and k_w8_rows128's) slabs: workgroup (u, rb) = output tile u (SW: the (gate, up) pair) x
-// row block rb, thread 16 rr + c one element: every split's partial summed in split order (8 loads in flight; a
-// missing split adds 0), then the epilogue.
-template <bool SW>
-__global__ __launch_bounds__(256) void k_w8_rows_merge(W8Args a, int S, const float* ws, int rows) {
-  constexpr int T = SW ? 2 : 1;
-  __shared__ float rstd_s[128];   // (indexed by the row: up to k_w8_rows128's 8 row blocks)
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int u = blockIdx.x, rb = blockIdx.y;
-  if (a.rstats) {
-    w8_rstd<4>(a, rstd_s, wave, lane, rb * 16, 16);
-    __syncthreads();
-  }
-  const int rr = rb * 16 + (threadIdx.x >> 4), c = threadIdx.x & 15;
-  const int Ncols = a.ntiles * 16;
-  const size_t sl = (size_t)rows * Ncols;
-  float x[T];
-#pragma unroll
-  for (int t = 0; t < T; ++t) {
-    const float* p0 = ws + (size_t)rr * Ncols + (T * u + t) * 16 + c;
-    float s = 0.f;
-    for (int s0 = 0; s0 < S; s0 += 8) {
-      float p[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) p[k] = s0 + k < S ? p0[(s0 + k) * sl] : 0.f;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) s += p[k];
-    }
-    x[t] = s;
-  }
-  w8_epilogue<SW>(a, u, gridDim.x, rr, c, x[0], x[T - 1], rstd_s);
-}
+// (k_w8_rows_merge, the merge of k_w8_rows's and k_w8_rows128's slabs, is fo_gemm_wq.h's with the column scale.)
 
 // ---- 65..128 rows (fo_gemm_w8_rows128): k_gemm_rows's design (fo_gemm.hip) on the codes.  The 8 waves of a
 // workgroup split the row blocks (wave w: rows 16 w .. + 16; a wave past ceil(M / 16) only carries its share of the
@@ -677,12 +646,6 @@ int w8_args(const char* fn, int m_lo, int m_hi, const char* serves, const float*
   return 0;
 }
 
-// k_w8_rows_merge over the S slabs of RB row blocks in `ws`
-void launch_merge(const W8Args& a, int swiglu, int units, int RB, int S, const float* ws, hipStream_t stream) {
-  if (swiglu) hipLaunchKernelGGL((k_w8_rows_merge<true>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
-  else hipLaunchKernelGGL((k_w8_rows_merge<false>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
-}
-
 }  // namespace
 
 extern "C" {
@@ -796,7 +759,7 @@ int fo_gemm_w8_rows(const float* X, int ldx, int M, int K, const void* Q, const 
   if (S > 1) {
     const int rc = fo::check_launch("fo_gemm_w8_rows");
     if (rc) return rc;
-    launch_merge(a, swiglu, units, RB, S, ws, stream);
+    launch_merge<true>(a, swiglu, units, RB, S, ws, stream);
   }
   fo::count_launch(FO_L_GEMM_W8_ROWS);
   return fo::check_launch("fo_gemm_w8_rows");
@@ -854,7 +817,7 @@ int fo_gemm_w8_rows128(const float* X, int ldx, int M, int K, const void* Q, con
 #undef FO_W8_ROWS128
   const int rc = fo::check_launch("fo_gemm_w8_rows128");
   if (rc) return rc;
-  launch_merge(a, swiglu, units, RB, S, ws, stream);
+  launch_merge<true>(a, swiglu, units, RB, S, ws, stream);
   fo::count_launch(FO_L_GEMM_W8_ROWS128);
   return fo::check_launch("fo_gemm_w8_rows128 (merge)");
 }

@@ -1,6 +1,6 @@
 // What the weight-stream GEMMs over quantised codes share (fo_gemm_w8.hip: e4m3 codes with a scale per output column;
 // fo_gemm_w4.hip: MXFP4 codes whose block scale is applied in the decode): the argument block, the X split, the
-// epilogue, the consumer's rstd and the accumulator hand-off through LDS.
+// epilogue, the consumer's rstd, the accumulator hand-off through LDS and the merge of the row streams' split-K slabs.
 #pragma once
 #include "fo_common.h"
 
@@ -98,6 +98,48 @@ template <typename Tile>
 __device__ __forceinline__ void w8_store_tile(Tile& tile, const f32x4 acc, int lane, int r0 = 0) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) tile[r0 + 4 * (lane >> 4) + i][lane & 15] = acc[i];
+}
+
+// The merge of the row-stream kernels' slabs (k_w8_rows, k_w8_rows128, k_w4_rows): workgroup (u, rb) = output tile u
+// (SW: the (gate, up) pair) x row block rb, thread 16 rr + c one element: every split's partial summed in split order
+// (8 loads in flight; a missing split adds 0), then the epilogue (SCALED: with the FP8 column scale).
+template <bool SW, bool SCALED>
+__global__ __launch_bounds__(256) void k_w8_rows_merge(W8Args a, int S, const float* ws, int rows) {
+  constexpr int T = SW ? 2 : 1;
+  __shared__ float rstd_s[128];   // (indexed by the row: up to k_w8_rows128's 8 row blocks)
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int u = blockIdx.x, rb = blockIdx.y;
+  if (a.rstats) {
+    w8_rstd<4>(a, rstd_s, wave, lane, rb * 16, 16);
+    __syncthreads();
+  }
+  const int rr = rb * 16 + (threadIdx.x >> 4), c = threadIdx.x & 15;
+  const int Ncols = a.ntiles * 16;
+  const size_t sl = (size_t)rows * Ncols;
+  float x[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    const float* p0 = ws + (size_t)rr * Ncols + (T * u + t) * 16 + c;
+    float s = 0.f;
+    for (int s0 = 0; s0 < S; s0 += 8) {
+      float p[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) p[k] = s0 + k < S ? p0[(s0 + k) * sl] : 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) s += p[k];
+    }
+    x[t] = s;
+  }
+  w8_epilogue<SW, SCALED>(a, u, gridDim.x, rr, c, x[0], x[T - 1], rstd_s);
+}
+
+// k_w8_rows_merge over the S slabs of RB row blocks in `ws`
+template <bool SCALED>
+void launch_merge(const W8Args& a, int swiglu, int units, int RB, int S, const float* ws, hipStream_t stream) {
+  if (swiglu)
+    hipLaunchKernelGGL((k_w8_rows_merge<true, SCALED>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
+  else
+    hipLaunchKernelGGL((k_w8_rows_merge<false, SCALED>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
 }
 
 }  // namespace

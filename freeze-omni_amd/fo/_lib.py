@@ -98,7 +98,10 @@ _SIGS = {
     "fo_quant_w4": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
     "fo_gemm_w4": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_ll,
                            c_vp, c_vp, c_int, c_float, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), c_vp]),
+    "fo_gemm_w4_rows": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp,
+                                c_ll, c_vp, c_vp, c_int, c_float, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), c_vp]),
     "fo_gemm_w4_counts": (c_int, [ctypes.POINTER(c_ll), c_int]),
+    "fo_gemm_w4_rows_count": (c_ll, []),
     "fo_gemm_w4_counts_reset": (c_int, []),
     "fo_gemm_pick_split": (c_int, [c_int, c_int, c_int]),
     "fo_gemm": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int,

@@ -69,7 +69,7 @@ def make_source(cfg, synth, device, model_path=None, llm_path=None, receive=Fals
 class FreezeOmniEngine:
     def __init__(self, model_path, llm_path=None, device="cuda:0", max_sessions=64, llm_kv_tokens=None,
                  tts_kv_tokens=None, source=None, receive_weights=False, train_yaml=None, mlp_weights="bf16",
-                 mlp_fp8_rows=16, llm_kv="fp32"):
+                 mlp_fp8_rows=16, llm_kv="fp32", mlp_mxfp4_rows=16):
         """llm_kv: "fp32" (default) or "bf16": the element of the Qwen2 stack's paged KV.  "bf16" is the
         cache the reference keeps: K after bias and RoPE and V after bias are rounded once to bf16 as they are
         appended, stored as 2-byte elements and read as such by the attention; llm_kv_tokens keeps meaning tokens,
@@ -84,6 +84,9 @@ class FreezeOmniEngine:
         ticks, prefixed first chunks, one-chunk listens of more than 8 sessions) stream the codes too, 128 steps of
         65..128 rows as well (the grouped offline listen, duplex ticks whose sessions start a turn), for the GEMMs
         and row counts of ops.W8_ROWS_POLICY; the model is the same, every other step is unchanged.
+        mlp_mxfp4_rows: 16 (default) or 64, with mlp_weights="mxfp4" only: 64 lets Qwen2 steps of 17..64 rows stream the
+        MXFP4 codes too (fo_gemm_w4_rows), for the GEMMs and row counts of ops.W4_ROWS_POLICY; the model
+        is the same, every other step is unchanged.
         receive_weights=True: allocate every packed layout without reading or generating weights; the
         caller fills them with fo.replica.broadcast_frozen(engine, dist) from rank 0 before any use.
         train_yaml: the parsed audiollm/train.yaml as a dict (models/utils.py:init_encoder_llm's configs) in
@@ -97,10 +100,15 @@ class FreezeOmniEngine:
             raise ValueError(f"mlp_fp8_rows must be 16, 64 or 128, got {mlp_fp8_rows!r}")
         if mlp_fp8_rows != 16 and mlp_weights != "fp8":
             raise ValueError(f"mlp_fp8_rows={mlp_fp8_rows} needs mlp_weights='fp8'")
+        if mlp_mxfp4_rows not in (16, 64):
+            raise ValueError(f"mlp_mxfp4_rows must be 16 or 64, got {mlp_mxfp4_rows!r}")
+        if mlp_mxfp4_rows != 16 and mlp_weights != "mxfp4":
+            raise ValueError(f"mlp_mxfp4_rows={mlp_mxfp4_rows} needs mlp_weights='mxfp4'")
         if llm_kv not in ("fp32", "bf16"):
             raise ValueError(f"llm_kv must be 'fp32' or 'bf16', got {llm_kv!r}")
         self.mlp_weights = mlp_weights
         self.mlp_fp8_rows = mlp_fp8_rows
+        self.mlp_mxfp4_rows = mlp_mxfp4_rows
         self.llm_kv = llm_kv
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
@@ -130,7 +138,7 @@ class FreezeOmniEngine:
         self.llm = LLMEngine(src, self.cfg["llm"], self.device,
                              kv_tokens=llm_kv_tokens or min(max_sessions * 4096, 1 << 17),
                              mlp_w8=mlp_weights == "fp8", mlp_w8_rows=mlp_fp8_rows, kv_dtype=llm_kv,
-                             mlp_w4=mlp_weights == "mxfp4")
+                             mlp_w4=mlp_weights == "mxfp4", mlp_w4_rows=mlp_mxfp4_rows)
         self.tts = TTSEngine(src, self.cfg["decoder_json"], self.device,
                              kv_tokens=tts_kv_tokens or min(max_sessions * 2048, 1 << 17))
         self.codec = CodecEngine(src, self.cfg["codec_json"], self.device)
@@ -177,7 +185,8 @@ class FreezeOmniEngine:
             torch.cuda.empty_cache()
             self.llm = LLMEngine(src, self.cfg["llm"], self.device, kv_tokens=kv_tokens,
                                  mlp_w8=self.mlp_weights == "fp8", mlp_w8_rows=self.mlp_fp8_rows,
-                                 kv_dtype=self.llm_kv, mlp_w4=self.mlp_weights == "mxfp4")
+                                 kv_dtype=self.llm_kv, mlp_w4=self.mlp_weights == "mxfp4",
+                                 mlp_w4_rows=self.mlp_mxfp4_rows)
         elif "predictor_head.weight" in src:
             self.llm.head_w, self.llm.head_b = src.get("predictor_head.weight"), src.get("predictor_head.bias")
         self.src = FakeQuantSource(src, self.src.fmt) if fq else src

@@ -14,7 +14,7 @@ from .stack import DecoderStack
 
 class LLMEngine:
     def __init__(self, src, llm_cfg, device, head_src=None, kv_tokens=65536, page_size=16, max_pos=None,
-                 mlp_w8=False, mlp_w8_rows=16, kv_dtype="fp32", mlp_w4=False):
+                 mlp_w8=False, mlp_w8_rows=16, kv_dtype="fp32", mlp_w4=False, mlp_w4_rows=16):
         """kv_dtype: "fp32" (default) or "bf16" -- the paged KV's element: K / V rounded once to bf16
         as they are appended and read as bf16 by the attention; kv_tokens keeps meaning tokens (half the bytes)."""
         if kv_dtype not in ("fp32", "bf16"):
@@ -34,7 +34,7 @@ class LLMEngine:
                            dtype=torch.bfloat16 if kv_dtype == "bf16" else torch.float32)
         self.stack = DecoderStack(src, "model.layers.", c["num_hidden_layers"], self.D, self.H, self.KVH, self.eps,
                                   True, self.rope, self.pool, first_fp16=True, mlp_w8=mlp_w8,
-                                  mlp_w8_rows=mlp_w8_rows, mlp_w4=mlp_w4)
+                                  mlp_w8_rows=mlp_w8_rows, mlp_w4=mlp_w4, mlp_w4_rows=mlp_w4_rows)
         self.embed_tokens = src.get("model.embed_tokens.weight", torch.bfloat16)
         self.norm = src.get("model.norm.weight")
         self.lm_head = PackedLinear(src.get("lm_head.weight", torch.bfloat16))

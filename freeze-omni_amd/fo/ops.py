@@ -448,6 +448,14 @@ def quant_w8(w):
 # every row count.  The one place the policy lives.
 W4_POLICY = {"gate_up": True, "down": True}
 
+# Which 17..64-row launches of a PackedLinearW4(stream_rows=64) stream the codes (fo_gemm_w4_rows): per GEMM, the
+# row-block counts (ceil(rows / 16)) out of 2, 3, 4 at which the MXFP4 row stream beat the bf16 image of the same W' by
+# more than that arm's repeat-to-repeat spread -- for the down, by more than that spread plus the packed input it costs
+# the next q|k|v (DESIGN 5.5's rule; scripts/gemm_w4_rows_ab.py, profiles/mlp_mxfp4_rows_gemm_ab.txt).
+# Builder-run: every pair entered but the down at 4 row blocks, whose 1.8 us gain does not pay for the 2.9 us the next
+# q|k|v loses on fp32 rows.  The one place the policy lives.
+W4_ROWS_POLICY = {"gate_up": (2, 3, 4), "down": (2, 3)}
+
 
 class PackedLinearW4:
     """A bias-free linear layer under weight-only MXFP4 (fo.quant, include/fo_hip.h fo_quant_w4): the weight is
@@ -458,12 +466,19 @@ class PackedLinearW4:
 
     w: [N, K] device weight (bf16 or fp32, K % 32 == 0), quantised on the device; swiglu_up as PackedLinear.
     receive=True: storages allocated, nothing quantised (a replica whose weights arrive by broadcast).
-    Setting `stream = True` on an instance sends every <= 16-row call to the codes (tests, A/B scripts)."""
+    stream_rows: 16 (default) or 64.  64 also lets calls of 17..64 fp32 rows stream the codes (fo_gemm_w4_rows), for
+    the row-block counts in `rows_rb`: W4_ROWS_POLICY's for this GEMM, the pairs that measured faster than the image.
+    Setting `stream = True` on an instance sends every <= 16-row call to the codes, `rows_rb = (2, 3, 4)` every call of
+    17 rows up to stream_rows (tests, A/B scripts)."""
 
     bias = None
 
-    def __init__(self, w, swiglu_up=None, receive=False):
+    def __init__(self, w, swiglu_up=None, receive=False, stream_rows=16):
         _check_dev(w)
+        if stream_rows not in (16, 64):
+            raise ValueError(f"stream_rows must be 16 or 64, got {stream_rows!r}")
+        self.stream_rows = stream_rows
+        self.rows_rb = W4_ROWS_POLICY["gate_up" if swiglu_up is not None else "down"]
         self.N, self.K = w.shape
         if self.K % 32:
             raise ValueError(f"PackedLinearW4 needs K % 32 == 0 (the scale block), got K={self.K}")
@@ -498,7 +513,9 @@ class PackedLinearW4:
 
     def streams(self, rows):
         """Whether a call of `rows` fp32 rows streams the codes (else it runs the bf16 image)."""
-        return rows <= 16 and self.stream
+        if rows <= 16:
+            return self.stream
+        return rows <= self.stream_rows and (rows + 15) // 16 in self.rows_rb
 
     def __call__(self, x, out=None, act="none", residual=False, out_dtype=F32, splitk=0, M=None, norm=None,
                  stats_out=None, xpack=None, ypack=None):
@@ -520,10 +537,10 @@ class PackedLinearW4:
         sg = ctypes.c_int(0)
         rt = Runtime.get(x.device)
         # (x is read as fp32 rows and the output is written row-major only: xpack / ypack stay untouched)
-        _lib.call("fo_gemm_w4", x.data_ptr(), x.stride(0), rows, self.Kp, self.q.data_ptr(), self.scales.data_ptr(),
-                  self.ntiles, self.N, 1 if self.swiglu else 0, out.data_ptr(), out.stride(0), 1 if residual else 0,
-                  rt.ws.data_ptr(), rt.ws.numel(), rt.counters.data_ptr(), rst, rg, eps, so, gn, yg, ctypes.byref(sg),
-                  stream(x.device))
+        _lib.call("fo_gemm_w4" if rows <= 16 else "fo_gemm_w4_rows", x.data_ptr(), x.stride(0), rows, self.Kp,
+                  self.q.data_ptr(), self.scales.data_ptr(), self.ntiles, self.N, 1 if self.swiglu else 0,
+                  out.data_ptr(), out.stride(0), 1 if residual else 0, rt.ws.data_ptr(), rt.ws.numel(),
+                  rt.counters.data_ptr(), rst, rg, eps, so, gn, yg, ctypes.byref(sg), stream(x.device))
         if stats_out is not None:
             stats_out.groups = sg.value
         return out
@@ -568,6 +585,11 @@ def w4_launch_counts():
 
 def w4_launch_counts_reset():
     _lib.call("fo_gemm_w4_counts_reset")
+
+
+def w4_rows_launch_count():
+    """fo_gemm_w4_rows calls since the last w4_launch_counts_reset (one per call, its merge included)."""
+    return int(_lib.load().fo_gemm_w4_rows_count())
 
 
 # FO_XPACK=0 turns the packed <= 64-row activations off (A/B only)

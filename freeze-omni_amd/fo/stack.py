@@ -33,19 +33,22 @@ class Layer:
 
 class DecoderStack:
     def __init__(self, src, prefix, n_layers, D, H, KVH, eps, bias, rope, pool, kv_layer0=0, first_fp16=False,
-                 attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT, mlp_w8=False, mlp_w8_rows=16, mlp_w4=False):
+                 attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT, mlp_w8=False, mlp_w8_rows=16, mlp_w4=False, mlp_w4_rows=16):
         """mlp_w8: gate/up and down under weight-only FP8 (ops.PackedLinearW8: the model's MLP weights become
         q * 2^e; forwards of <= 16 rows stream the codes, larger ones the exact bf16 image of the same weights).
         mlp_w8_rows: 16, 64 or 128, PackedLinearW8's stream_rows (64: 17..64-row forwards stream the codes too; 128:
         65..128-row ones as well).
         mlp_w4: gate/up and down under weight-only MXFP4 instead (ops.PackedLinearW4: q * 2^e with e2m1 codes and one
         e per 32-column block; forwards of <= 16 rows stream the codes for the GEMMs of ops.W4_POLICY, everything else
-        runs the exact bf16 image)."""
+        runs the exact bf16 image).
+        mlp_w4_rows: 16 or 64, PackedLinearW4's stream_rows (64: 17..64-row forwards stream the codes too, for the
+        pairs of ops.W4_ROWS_POLICY)."""
         if mlp_w8 and mlp_w4:
             raise ValueError("mlp_w8 and mlp_w4 are two models of the same weights: pick one")
         self.mlp_w4 = bool(mlp_w4)
         self.mlp_w8 = bool(mlp_w8)
         self.mlp_w8_rows = mlp_w8_rows
+        self.mlp_w4_rows = mlp_w4_rows
         self.n, self.D, self.H, self.KVH, self.hd, self.eps = n_layers, D, H, KVH, D // H, eps
         self.attn_kps = attn_keys_per_split
         self.cos, self.sin = rope
@@ -76,8 +79,10 @@ class DecoderStack:
             elif self.mlp_w4:
                 recv = isinstance(src, ReceiveSource)
                 L.gu = PackedLinearW4(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
-                                      swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16), receive=recv)
-                L.down = PackedLinearW4(src.get(q + "mlp.down_proj.weight", torch.bfloat16), receive=recv)
+                                      swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16), receive=recv,
+                                      stream_rows=mlp_w4_rows)
+                L.down = PackedLinearW4(src.get(q + "mlp.down_proj.weight", torch.bfloat16), receive=recv,
+                                        stream_rows=mlp_w4_rows)
             else:
                 L.gu = PackedLinear(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
                                     swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16))
@@ -166,7 +171,7 @@ class DecoderStack:
         # fills or reads the packed x*gamma (the next q|k|v reads the fp32 rows); the o input stays packed
         # (17..64 rows under mlp_w8_rows=64 likewise, per GEMM: an FP8 gate/up leaves the o's packed x*gamma unread,
         # an FP8 down fills none for the next q|k|v; 65..128 rows under mlp_w8_rows=128 pack nothing either way)
-        # (mlp_w4 likewise at <= 16 rows, per GEMM that streams the MXFP4 codes)
+        # (mlp_w4 likewise at <= 16 rows and, under mlp_w4_rows=64, at 17..64 rows, per GEMM that streams the MXFP4 codes)
         xgp_gu = xgp_qkv = xgp
         if (self.mlp_w8 or self.mlp_w4) and self.layers:
             if self.layers[0].gu.streams(T):

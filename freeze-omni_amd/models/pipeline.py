@@ -30,6 +30,7 @@ class inferencePipeline:
         start-up broadcast, bin/pool.py's `devices` replicas).
         args["llm_mlp_weights"]: "bf16" (default), "fp8" or "mxfp4", the engine's mlp_weights (every replica of a pool takes
         the same value, so the copied layouts match); args["llm_mlp_fp8_rows"]: 16 (default), 64 or 128, its mlp_fp8_rows;
+        args["llm_mlp_mxfp4_rows"]: 16 (default) or 64, its mlp_mxfp4_rows;
         args["llm_kv"]: "fp32" (default) or "bf16", its llm_kv (the Qwen2 paged KV's element)."""
         if isinstance(args, argparse.Namespace):
             args = vars(args)
@@ -45,6 +46,7 @@ class inferencePipeline:
                                              receive_weights=weights_from is not None,
                                              mlp_weights=args.get("llm_mlp_weights") or "bf16",
                                              mlp_fp8_rows=args.get("llm_mlp_fp8_rows") or 16,
+                                             mlp_mxfp4_rows=args.get("llm_mlp_mxfp4_rows") or 16,
                                              llm_kv=args.get("llm_kv") or "fp32")
         if weights_from is not None:
             from fo.replica import copy_frozen

@@ -231,7 +231,8 @@ int fo_gemm_w8_rows128(const float* X, int ldx, int M, int K, const void* q, con
                        int swiglu, float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters,
                        const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
                        int* sgroups, hipStream_t stream);
-/* Weight-only MXFP4 (OCP e2m1 codes, one power-of-two scale per 32 elements) for <= 16-row launches:
+/* Weight-only MXFP4 (OCP e2m1 codes, one power-of-two scale per 32 elements) for <= 16-row launches (fo_gemm_w4) and
+ * 17..64-row ones (fo_gemm_w4_rows):
  * W'[n, k] = q[n, k] * 2^e[n, k / 32].  q is an e2m1 code: magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 as codes 0..7, bit 3
  * the sign, copied from the weight's sign bit even where the magnitude rounds to 0.  e is one integer per (output row,
  * block of 32 consecutive k): the smallest with max|W[n, block]| * 2^-e <= 6, taken from the float's exponent E and
@@ -253,8 +254,19 @@ int fo_gemm_w8_rows128(const float* X, int ldx, int M, int K, const void* q, con
  *   through fo_gemm.  One workgroup per output tile, its waves splitting K (k_w4); the SwiGLU pair at K = 3584
  *   X-stationary and persistent (k_w4_xs); long-K plain launches (the Qwen2 down) split K across workgroups and
  *   merge inside the launch in split order where ws and counters are given (k_w4_sk).  Deterministic, capture-safe.
- * fo_gemm_w4_counts: the launches issued per form since the last reset (general, xs, sk) into out[0 .. min(n, 3));
- *   returns 3.  These kernels have no FoLaunchKind. */
+ * fo_gemm_w4_rows: fo_gemm_w4's arguments and epilogue semantics for 17 <= M <= 64 (fo_gemm_w8_rows's design on the
+ *   128-column code steps, k_w4_rows): X stationary per K slice, the codes decoded once per unit for every row block,
+ *   K split over workgroups whenever it exceeds one workgroup's slice (S = ceil(ceil(K/128) / c) slices, c = 14 at 2
+ *   row blocks, 7 (swiglu) or 8 at 3, 7 (swiglu) or 6 at 4) and merged by a second launch in slice order, which needs
+ *   `ws` of at least S * 16 ceil(M/16) * ntiles * 16 floats; `counters` is not used.  The refusals are fo_gemm_w4's,
+ *   with the band 17 <= M <= 64 and the workspace ("floats needed"), all on the host before any HIP call.
+ *   Deterministic, capture-safe.  Builder-run on an MI355X at the Qwen2 MLP shapes it beat the bf16 image at every
+ *   (GEMM, row blocks) pair but the down at 4 row blocks once the next q|k|v's packed input is counted
+ *   (profiles/mlp_mxfp4_rows_gemm_ab.txt); which launches take it is the caller's policy (fo/ops.py W4_ROWS_POLICY,
+ *   DESIGN 5.7).
+ * fo_gemm_w4_counts: the launches issued per <= 16-row form since the last reset (general, xs, sk) into
+ *   out[0 .. min(n, 3)); returns 3.  fo_gemm_w4_rows_count: the calls of fo_gemm_w4_rows since the last reset
+ *   (fo_gemm_w4_counts_reset zeroes it too).  These kernels have no FoLaunchKind. */
 long long fo_quant_w4_bytes(int N, int K);
 long long fo_quant_w4_scale_bytes(int N, int K);
 int fo_quant_w4(const void* W, int src_bf16, int N, int K, int ldw, void* q, void* scale, void* wdq, int tile_base,
@@ -262,7 +274,12 @@ int fo_quant_w4(const void* W, int src_bf16, int N, int K, int ldw, void* q, voi
 int fo_gemm_w4(const float* X, int ldx, int M, int K, const void* q, const void* scale, int ntiles, int N, int swiglu,
                float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters, const float* rstats,
                int rgroups, float eps, float* sout, const float* gnext, float* yg, int* sgroups, hipStream_t stream);
+int fo_gemm_w4_rows(const float* X, int ldx, int M, int K, const void* q, const void* scale, int ntiles, int N,
+                    int swiglu, float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters,
+                    const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
+                    int* sgroups, hipStream_t stream);
 int fo_gemm_w4_counts(long long* out, int n);
+long long fo_gemm_w4_rows_count(void);
 int fo_gemm_w4_counts_reset(void);
 /* Software-pipelined one-row-tile fp32-X weight-stream GEMMs (M <= 16, >= 64 MiB of weights: the next
  * k-group's weights + X in flight during this group's MFMAs).  3 (default): the measured policy; 0: plain
