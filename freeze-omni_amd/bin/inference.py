@@ -57,6 +57,9 @@ def get_args(argv=None):
                    help="with --llm_mlp_weights mxfp4: the most rows of a Qwen2 step that stream the MXFP4 codes")
     p.add_argument("--llm_kv", choices=["fp32", "bf16"], default="fp32",
                    help="Qwen2 paged KV cache element: fp32, or bf16 (half the memory and attention bytes)")
+    p.add_argument("--llm_lm_head_weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
+                   help="Qwen2 output head (lm_head) weights: bf16, weight-only FP8 (e4m3 codes x a power of two per "
+                        "vocabulary row) or weight-only MXFP4 (e2m1 codes x a power of two per 32 columns)")
     p.add_argument("--role", default="You are a helpful assistant.")
     p.add_argument("--max_text_tokens", type=int, default=MAX_TEXT_TOKENS)
     args = p.parse_args(argv)

@@ -1,5 +1,6 @@
 // Weight-only MXFP4 (OCP e2m1 codes, one power-of-two scale per 32 elements) GEMMs for the Qwen2 MLP at <= 16 rows
-// (fo_gemm_w4) and at 17..64 rows (fo_gemm_w4_rows), and their quantiser.
+// (fo_gemm_w4; fo_gemm_w4_head for the lm_head: k_w4_xs's plain form) and at 17..64 rows (fo_gemm_w4_rows), and their
+// quantiser.
 //
 //   W'[n, k] = q[n, k] * 2^e[n, k / 32]   q an e2m1 code (0, 0.5, 1, 1.5, 2, 3, 4, 6 and a sign bit), e one integer
 //                                         per (output row, block of 32 columns), stored as the E8M0 byte e + 127
@@ -211,8 +212,12 @@ __global__ __launch_bounds__(NW * 64) void k_w4_sk(W8Args a, int S, float* ws, i
 // ---- X-stationary persistent form, as k_w8_xs: the SwiGLU pair, K = NW * KPW * 128 (3584 = 28 code steps).  X hi in
 // registers, lo in LDS, units dealt evenly to at most one workgroup per CU, the next unit's codes and scales issued
 // before the current one is reduced, a fixed-order cross-wave reduction.
-template <int NW, int KPW>
+// SW = false (fo_gemm_w4_head): the plain form, as k_w8_xs's.  A unit is two adjacent plain tiles 2u, 2u + 1 (the
+// second of an odd count's last unit lies past both descriptors: zero codes under a zero scale byte, never stored),
+// each with the plain epilogue: the store, no residual, no statistics (NW * 64 >= 512: a tile per 256 threads).
+template <int NW, int KPW, bool SW = true>
 __global__ __launch_bounds__(NW * 64) void k_w4_xs(W8Args a, int units) {
+  static_assert(SW || NW >= 8, "k_w4_xs: the plain epilogue takes 512 threads");
   __shared__ bf16x8 xlo[NW][4 * KPW][64];
   __shared__ float part[NW][2][16][17];
   __shared__ float rstd_s[16];
@@ -245,7 +250,9 @@ __global__ __launch_bounds__(NW * 64) void k_w4_xs(W8Args a, int units) {
       xlo[wave][j][lane] = lo;
     }
   }
-  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
+  if constexpr (SW) {
+    if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
+  }
   auto compute = [&](u32x4 (&q)[KPW], unsigned (&s)[KPW]) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -271,15 +278,23 @@ __global__ __launch_bounds__(NW * 64) void k_w4_xs(W8Args a, int units) {
     w8_store_tile(part[wave][1], c1, lane);
     __syncthreads();
     const int e = threadIdx.x;
-    if (e < 256) {
-      const int rr = e >> 4, c = e & 15;
-      float x1 = 0.f, x2 = 0.f;
+    if constexpr (SW) {
+      if (e < 256) {
+        const int rr = e >> 4, c = e & 15;
+        float x1 = 0.f, x2 = 0.f;
 #pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        x1 += part[w][0][rr][c];
-        x2 += part[w][1][rr][c];
+        for (int w = 0; w < NW; ++w) {
+          x1 += part[w][0][rr][c];
+          x2 += part[w][1][rr][c];
+        }
+        w8_epilogue<true, false>(a, u, 0, rr, c, x1, x2, rstd_s);
       }
-      w8_epilogue<true, false>(a, u, 0, rr, c, x1, x2, rstd_s);
+    } else if (e < 512) {
+      const int t = e >> 8, rr = (e >> 4) & 15, c = e & 15;
+      float x1 = 0.f;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) x1 += part[w][t][rr][c];
+      if (2 * u + t < a.ntiles) w8_epilogue<false, false>(a, 2 * u + t, 0, rr, c, x1, 0.f, rstd_s);
     }
   }
 }
@@ -495,6 +510,8 @@ int w4_cus() {
 // fo_gemm_w4_rows (fo_gemm_w4_rows_count)
 std::atomic<long long> g_w4_launches[3];
 std::atomic<long long> g_w4_rows_calls;
+// the launches of the two lm_head streams (fo_gemm_head_counts): fo_gemm_w8_head, fo_gemm_w4_head
+std::atomic<long long> g_head_launches[2];
 
 // What the two GEMM entries share: the checks of everything but the workspace (all before the entry's first HIP call),
 // then W8Args (with KK) and the output tile count.  `fn` is the entry's name, [m_lo, m_hi] its row band and `serves`
@@ -527,6 +544,8 @@ int w4_args(const char* fn, int m_lo, int m_hi, const char* serves, const float*
 }
 
 }  // namespace
+
+void fo::count_head(int slot) { g_head_launches[slot].fetch_add(1, std::memory_order_relaxed); }
 
 extern "C" {
 
@@ -603,6 +622,35 @@ int fo_gemm_w4(const float* X, int ldx, int M, int K, const void* Q, const void*
   }
   g_w4_launches[0].fetch_add(1, std::memory_order_relaxed);
   return fo::check_launch("fo_gemm_w4");
+}
+
+int fo_gemm_head_counts(long long* out, int n) {
+  for (int i = 0; out && i < n && i < 2; ++i) out[i] = g_head_launches[i].load(std::memory_order_relaxed);
+  return 2;
+}
+int fo_gemm_head_counts_reset(void) {
+  for (int i = 0; i < 2; ++i) g_head_launches[i].store(0, std::memory_order_relaxed);
+  return 0;
+}
+
+int fo_gemm_w4_head(const float* X, int ldx, int M, int K, const void* Q, const void* scale, int ntiles, int N,
+                    float* Y, int ldy, hipStream_t stream) {
+  // every check before the first HIP call
+  W8Args a;
+  int tiles;
+  if (const int rc = w4_args("fo_gemm_w4_head", 1, 16,
+                             "the MXFP4 head stream serves M <= 16 (more rows run the bf16 image)", X, ldx, M, K, Q,
+                             scale, ntiles, N, 0, Y, ldy, 0, nullptr, 0, 0.f, nullptr, nullptr, nullptr, a, tiles))
+    return rc;
+  FO_REQUIRE(K == 3584, "fo_gemm_w4_head: K=%d, the X-stationary plain form is compiled for K = 3584 (fo_gemm_w4 serves "
+             "any other K)", K);
+  // units of two adjacent plain tiles dealt evenly to at most one workgroup per CU; the SwiGLU form's wave shape
+  // (14 waves x 2 code steps)
+  const int units = (ntiles + 1) / 2;
+  const int G = units < w4_cus() ? units : w4_cus();
+  hipLaunchKernelGGL((k_w4_xs<14, 2, false>), dim3(G), dim3(896), 0, stream, a, units);
+  fo::count_head(1);
+  return fo::check_launch("fo_gemm_w4_head");
 }
 
 int fo_gemm_w4_rows(const float* X, int ldx, int M, int K, const void* Q, const void* scale, int ntiles, int N,

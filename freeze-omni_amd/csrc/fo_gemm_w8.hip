@@ -13,6 +13,7 @@
 // B-fragments of two consecutive 32-column k-steps, K padded to a multiple of 64 with zero codes.  One entry per row
 // band, each kernel's design above the kernel:
 //  * fo_gemm_w8, <= 16 rows: k_w8 (general), k_w8_xs (the SwiGLU pair at K = 3584) or k_w8_sk (long-K plain);
+//  * fo_gemm_w8_head, <= 16 rows: k_w8_xs's plain form at K = 3584 (the Qwen2 lm_head);
 //  * fo_gemm_w8_rows, 17..64 rows: k_w8_rows, then k_w8_rows_merge where K is split;
 //  * fo_gemm_w8_rows128, 65..128 rows: k_w8_rows128, then k_w8_rows_merge.
 #include <stdlib.h>
@@ -195,8 +196,12 @@ __global__ __launch_bounds__(NW * 64) void k_w8_sk(W8Args a, int S, float* ws, i
 // ---- X-stationary persistent form, as k_gemm_xs (fo_gemm.hip): the SwiGLU pair, K = NW * KPW * 64 (3584 = 56 code
 // steps).  X hi in registers, lo in LDS, units dealt evenly to at most one workgroup per CU, the next unit's codes
 // issued before the current one is reduced, a fixed-order cross-wave reduction.
-template <int NW, int KPW>
+// SW = false (fo_gemm_w8_head): the plain form.  A unit is two adjacent plain tiles 2u, 2u + 1 (the second of an odd
+// count's last unit lies past the code descriptor and loads zero codes; it is never stored), each with the plain
+// epilogue: the column scale and the store, no residual, no statistics (NW * 64 >= 512: a tile per 256 threads).
+template <int NW, int KPW, bool SW = true>
 __global__ __launch_bounds__(NW * 64) void k_w8_xs(W8Args a, int units) {
+  static_assert(SW || NW >= 8, "k_w8_xs: the plain epilogue takes 512 threads");
   __shared__ bf16x8 xlo[NW][2 * KPW][64];
   __shared__ float part[NW][2][16][17];
   __shared__ float rstd_s[16];
@@ -227,7 +232,9 @@ __global__ __launch_bounds__(NW * 64) void k_w8_xs(W8Args a, int units) {
       xlo[wave][j][lane] = lo;
     }
   }
-  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
+  if constexpr (SW) {
+    if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
+  }
   auto compute = [&](u32x4 (&q)[KPW]) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -253,15 +260,23 @@ __global__ __launch_bounds__(NW * 64) void k_w8_xs(W8Args a, int units) {
     w8_store_tile(part[wave][1], c1, lane);
     __syncthreads();
     const int e = threadIdx.x;
-    if (e < 256) {
-      const int rr = e >> 4, c = e & 15;
-      float x1 = 0.f, x2 = 0.f;
+    if constexpr (SW) {
+      if (e < 256) {
+        const int rr = e >> 4, c = e & 15;
+        float x1 = 0.f, x2 = 0.f;
 #pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        x1 += part[w][0][rr][c];
-        x2 += part[w][1][rr][c];
+        for (int w = 0; w < NW; ++w) {
+          x1 += part[w][0][rr][c];
+          x2 += part[w][1][rr][c];
+        }
+        w8_epilogue<true>(a, u, 0, rr, c, x1, x2, rstd_s);
       }
-      w8_epilogue<true>(a, u, 0, rr, c, x1, x2, rstd_s);
+    } else if (e < 512) {
+      const int t = e >> 8, rr = (e >> 4) & 15, c = e & 15;
+      float x1 = 0.f;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) x1 += part[w][t][rr][c];
+      if (2 * u + t < a.ntiles) w8_epilogue<false>(a, 2 * u + t, 0, rr, c, x1, 0.f, rstd_s);
     }
   }
 }
@@ -711,6 +726,26 @@ int fo_gemm_w8(const float* X, int ldx, int M, int K, const void* Q, const float
   }
   fo::count_launch(FO_L_GEMM_W8);
   return fo::check_launch("fo_gemm_w8");
+}
+
+int fo_gemm_w8_head(const float* X, int ldx, int M, int K, const void* Q, const float* scale, int ntiles, int N,
+                    float* Y, int ldy, hipStream_t stream) {
+  // every check before the first HIP call
+  W8Args a;
+  int tiles;
+  if (const int rc = w8_args("fo_gemm_w8_head", 1, 16, "the FP8 head stream serves M <= 16 (more rows run the bf16 image)",
+                             X, ldx, M, K, Q, scale, ntiles, N, 0, Y, ldy, 0, nullptr, 0, 0.f, nullptr, nullptr, nullptr,
+                             a, tiles))
+    return rc;
+  FO_REQUIRE(K == 3584, "fo_gemm_w8_head: K=%d, the X-stationary plain form is compiled for K = 3584 (fo_gemm_w8 serves "
+             "any other K)", K);
+  // units of two adjacent plain tiles dealt evenly to at most one workgroup per CU; the SwiGLU form's wave shape
+  // (14 waves x 4 code steps)
+  const int units = (ntiles + 1) / 2;
+  const int G = units < w8_cus() ? units : w8_cus();
+  hipLaunchKernelGGL((k_w8_xs<14, 4, false>), dim3(G), dim3(896), 0, stream, a, units);
+  fo::count_head(0);
+  return fo::check_launch("fo_gemm_w8_head");
 }
 
 int fo_gemm_w8_rows(const float* X, int ldx, int M, int K, const void* Q, const float* scale, int ntiles, int N,

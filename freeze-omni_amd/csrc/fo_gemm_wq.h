@@ -4,6 +4,12 @@
 #pragma once
 #include "fo_common.h"
 
+namespace fo {
+// the launch counters of the lm_head streams (fo_gemm_head_counts, fo_gemm_w4.hip): slot 0 fo_gemm_w8_head, slot 1
+// fo_gemm_w4_head.  Counters of their own: these kernels have no FoLaunchKind.
+void count_head(int slot);
+}  // namespace fo
+
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;

@@ -69,8 +69,13 @@ def make_source(cfg, synth, device, model_path=None, llm_path=None, receive=Fals
 class FreezeOmniEngine:
     def __init__(self, model_path, llm_path=None, device="cuda:0", max_sessions=64, llm_kv_tokens=None,
                  tts_kv_tokens=None, source=None, receive_weights=False, train_yaml=None, mlp_weights="bf16",
-                 mlp_fp8_rows=16, llm_kv="fp32", mlp_mxfp4_rows=16):
-        """llm_kv: "fp32" (default) or "bf16": the element of the Qwen2 stack's paged KV.  "bf16" is the
+                 mlp_fp8_rows=16, llm_kv="fp32", mlp_mxfp4_rows=16, lm_head_weights="bf16"):
+        """lm_head_weights: "bf16" (default), "fp8" or "mxfp4": the Qwen2 output head (lm_head.weight only, never the
+        embedding) under weight-only FP8 per vocabulary row or MXFP4, independent of mlp_weights,
+        mlp_*_rows and llm_kv.  Calls of <= 16 rows (the captured TextGraph, the eager text_step, LLMEngine.logits)
+        stream the codes where ops.HEAD_POLICY says so; more rows run the exact bf16 image.  `src` serves the
+        dequantised head (FakeQuantSource(..., lm_head=...)).
+        llm_kv: "fp32" (default) or "bf16": the element of the Qwen2 stack's paged KV.  "bf16" is the
         cache the reference keeps: K after bias and RoPE and V after bias are rounded once to bf16 as they are
         appended, stored as 2-byte elements and read as such by the attention; llm_kv_tokens keeps meaning tokens,
         so the pool is half the bytes.  The speech decoder's pool, the encoder rings and the adapter caches stay fp32.
@@ -106,6 +111,9 @@ class FreezeOmniEngine:
             raise ValueError(f"mlp_mxfp4_rows={mlp_mxfp4_rows} needs mlp_weights='mxfp4'")
         if llm_kv not in ("fp32", "bf16"):
             raise ValueError(f"llm_kv must be 'fp32' or 'bf16', got {llm_kv!r}")
+        if lm_head_weights not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"lm_head_weights must be 'bf16', 'fp8' or 'mxfp4', got {lm_head_weights!r}")
+        self.lm_head_weights = lm_head_weights
         self.mlp_weights = mlp_weights
         self.mlp_fp8_rows = mlp_fp8_rows
         self.mlp_mxfp4_rows = mlp_mxfp4_rows
@@ -125,11 +133,7 @@ class FreezeOmniEngine:
             st = {f"encoder_{i}.global_cmvn.{n}": torch.from_numpy(np.asarray(v, np.float32))
                   for i in ("user", "system") for n, v in (("mean", mean), ("istd", istd))}
             src = OverlaySource(CheckpointSource(st, self.device), src)
-        if mlp_weights in ("fp8", "mxfp4") and not receive_weights:
-            from .weights import FakeQuantSource
-            self.src = FakeQuantSource(src, mlp_weights)   # (the engines below quantise the raw weights themselves)
-        else:
-            self.src = src
+        self.src = src if receive_weights else self._model_source(src)
         self.max_sessions = max_sessions
         ty = self.cfg["train_yaml"]
         self.enc = {i: SpeechEncoderEngine(src, self.cfg, i, self.device, max_sessions) for i in ("user", "system")}
@@ -138,7 +142,8 @@ class FreezeOmniEngine:
         self.llm = LLMEngine(src, self.cfg["llm"], self.device,
                              kv_tokens=llm_kv_tokens or min(max_sessions * 4096, 1 << 17),
                              mlp_w8=mlp_weights == "fp8", mlp_w8_rows=mlp_fp8_rows, kv_dtype=llm_kv,
-                             mlp_w4=mlp_weights == "mxfp4", mlp_w4_rows=mlp_mxfp4_rows)
+                             mlp_w4=mlp_weights == "mxfp4", mlp_w4_rows=mlp_mxfp4_rows,
+                             lm_head_weights=lm_head_weights)
         self.tts = TTSEngine(src, self.cfg["decoder_json"], self.device,
                              kv_tokens=tts_kv_tokens or min(max_sessions * 2048, 1 << 17))
         self.codec = CodecEngine(src, self.cfg["codec_json"], self.device)
@@ -153,6 +158,16 @@ class FreezeOmniEngine:
         self.use_graphs = True
         self.predict_usr_state = ty["model_conf"].get("predict_usr_state", 0)
         self._chat_template(ty["model_conf"].get("chat_template"))
+
+    def _model_source(self, raw):
+        """`raw` as the model this engine computes: the MLP and / or the head replaced by their quantised images
+        (fo.weights.FakeQuantSource; the engines themselves quantise the raw weights)."""
+        mlp = self.mlp_weights if self.mlp_weights != "bf16" else None
+        head = self.lm_head_weights if self.lm_head_weights != "bf16" else None
+        if mlp is None and head is None:
+            return raw
+        from .weights import FakeQuantSource
+        return FakeQuantSource(raw, mlp, lm_head=head)
 
     # ------------------------------------------------------------------ models/utils.py:11-28
     def rebind_audiollm(self, state):
@@ -186,10 +201,10 @@ class FreezeOmniEngine:
             self.llm = LLMEngine(src, self.cfg["llm"], self.device, kv_tokens=kv_tokens,
                                  mlp_w8=self.mlp_weights == "fp8", mlp_w8_rows=self.mlp_fp8_rows,
                                  kv_dtype=self.llm_kv, mlp_w4=self.mlp_weights == "mxfp4",
-                                 mlp_w4_rows=self.mlp_mxfp4_rows)
+                                 mlp_w4_rows=self.mlp_mxfp4_rows, lm_head_weights=self.lm_head_weights)
         elif "predictor_head.weight" in src:
             self.llm.head_w, self.llm.head_b = src.get("predictor_head.weight"), src.get("predictor_head.bias")
-        self.src = FakeQuantSource(src, self.src.fmt) if fq else src
+        self.src = self._model_source(src) if fq else src
         return sorted(state)
 
     # ------------------------------------------------------------------ chat template (audioLLM.py:112-126)

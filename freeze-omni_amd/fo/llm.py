@@ -8,17 +8,25 @@ import torch
 
 from . import ops, tables
 from .kv import BatchMeta, KVPool, KVSeq
-from .ops import F32, I32, PackedLinear
+from .ops import F32, I32, PackedLinear, PackedLinearW4, PackedLinearW8
 from .stack import DecoderStack
+from .weights import ReceiveSource
 
 
 class LLMEngine:
     def __init__(self, src, llm_cfg, device, head_src=None, kv_tokens=65536, page_size=16, max_pos=None,
-                 mlp_w8=False, mlp_w8_rows=16, kv_dtype="fp32", mlp_w4=False, mlp_w4_rows=16):
-        """kv_dtype: "fp32" (default) or "bf16" -- the paged KV's element: K / V rounded once to bf16
+                 mlp_w8=False, mlp_w8_rows=16, kv_dtype="fp32", mlp_w4=False, mlp_w4_rows=16, lm_head_weights="bf16"):
+        """lm_head_weights: "bf16" (default), "fp8" or "mxfp4" -- lm_head.weight under weight-only FP8 / MXFP4 (DESIGN
+        §5.8): calls of <= 16 rows stream the codes where ops.HEAD_POLICY says so, every other call runs the exact
+        bf16 image.  embed_tokens is never quantised.  Over a ReceiveSource the head's storages are allocated and nothing
+        is quantised (a replica whose weights arrive by broadcast fills codes, scales and image).
+        kv_dtype: "fp32" (default) or "bf16" -- the paged KV's element: K / V rounded once to bf16
         as they are appended and read as bf16 by the attention; kv_tokens keeps meaning tokens (half the bytes)."""
         if kv_dtype not in ("fp32", "bf16"):
             raise ValueError(f'kv_dtype must be "fp32" or "bf16", got {kv_dtype!r}')
+        if lm_head_weights not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"lm_head_weights must be 'bf16', 'fp8' or 'mxfp4', got {lm_head_weights!r}")
+        self.lm_head_weights = lm_head_weights
         self.kv_dtype = kv_dtype
         c = llm_cfg
         self.device = torch.device(device)
@@ -37,7 +45,12 @@ class LLMEngine:
                                   mlp_w8_rows=mlp_w8_rows, mlp_w4=mlp_w4, mlp_w4_rows=mlp_w4_rows)
         self.embed_tokens = src.get("model.embed_tokens.weight", torch.bfloat16)
         self.norm = src.get("model.norm.weight")
-        self.lm_head = PackedLinear(src.get("lm_head.weight", torch.bfloat16))
+        if lm_head_weights == "bf16":
+            self.lm_head = PackedLinear(src.get("lm_head.weight", torch.bfloat16))
+        else:
+            quantised = PackedLinearW8 if lm_head_weights == "fp8" else PackedLinearW4
+            self.lm_head = quantised(src.get("lm_head.weight", torch.bfloat16),
+                                     receive=isinstance(src, ReceiveSource), kind="head")
         hs = head_src or src
         self.head_w = hs.get("predictor_head.weight") if "predictor_head.weight" in hs else None
         self.head_b = hs.get("predictor_head.bias") if self.head_w is not None else None
@@ -53,6 +66,16 @@ class LLMEngine:
     @property
     def mlp_fp4_bytes(self):
         return self.stack.mlp_fp4_bytes
+
+    @property
+    def lm_head_fp8_bytes(self):
+        """The FP8 head's codes and scales, held beside its bf16 image (0 without lm_head_weights="fp8")."""
+        return self.lm_head.fp8_nbytes if self.lm_head_weights == "fp8" else 0
+
+    @property
+    def lm_head_fp4_bytes(self):
+        """The MXFP4 head's codes and scales, held beside its bf16 image (0 without lm_head_weights="mxfp4")."""
+        return self.lm_head.fp4_nbytes if self.lm_head_weights == "mxfp4" else 0
 
     def new_seq(self):
         return KVSeq(self.pool)

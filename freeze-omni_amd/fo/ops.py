@@ -323,6 +323,26 @@ class PackedLinear:
         return out
 
 
+# Whether the <= 16-row calls of a quantised Qwen2 output head (PackedLinearW8 / PackedLinearW4 with kind="head", K =
+# HEAD_K) stream the codes through fo_gemm_w8_head / fo_gemm_w4_head: a format enters only if, at both 8 and 16 rows,
+# its median beat the bf16 image on the head's existing kernel by more than that arm's repeat-to-repeat spread (DESIGN
+# 5.5's rule; scripts/gemm_head_ab.py, profiles/lm_head_quant_gemm_ab.txt).  A format that is false keeps
+# the model and runs the image at every row count.  Builder-run at N = 152,064 (medians, us, bf16 image / fp8 / mxfp4):
+# 172.2 / 88.8 / 55.4 at 8 rows (bf16 spread 2.3) and 188.1 / 95.2 / 59.0 at 16 (spread 1.1): both formats entered.
+# A head of any other K (the tiny config's 128) streams through the general plain form of fo_gemm_w8 / fo_gemm_w4.
+# The one place the policy lives.
+HEAD_POLICY = {"fp8": True, "mxfp4": True}
+HEAD_K = 3584   # the K the X-stationary plain forms are compiled for
+
+
+def _head_kind(kind, swiglu_up, stream_rows):
+    if kind not in (None, "head"):
+        raise ValueError(f"kind must be None or 'head', got {kind!r}")
+    if kind == "head" and (swiglu_up is not None or stream_rows != 16):
+        raise ValueError("a head is a plain projection with stream_rows=16")
+    return kind
+
+
 # Which 17..64-row launches of a PackedLinearW8(stream_rows=64) stream the codes: per GEMM, the row-block counts
 # (ceil(rows / 16)) at which fo_gemm_w8_rows beat the bf16 image by more than that arm's spread -- for the down, by
 # more than the packed input it costs the next q|k|v as well (scripts/gemm_w8_rows_ab.py,
@@ -344,17 +364,20 @@ class PackedLinearW8:
     stream_rows: 16 (default), 64 or 128.  64 also lets calls of 17..64 fp32 rows stream the codes (fo_gemm_w8_rows),
     128 calls of 65..128 rows as well (fo_gemm_w8_rows128), for the row-block counts in `rows_rb`: W8_ROWS_POLICY's for
     this GEMM, the pairs that measured faster than the image.  Setting `rows_rb = tuple(range(2, 9))` on an instance
-    sends every call of 17 rows up to stream_rows there (tests, A/B scripts)."""
+    sends every call of 17 rows up to stream_rows there (tests, A/B scripts).
+    kind="head": the Qwen2 output head (see _head_kind): plain, stream_rows 16, no row-stream policy of its own."""
 
     bias = None
 
-    def __init__(self, w, swiglu_up=None, receive=False, stream_rows=16):
+    def __init__(self, w, swiglu_up=None, receive=False, stream_rows=16, kind=None):
         _check_dev(w)
         if stream_rows not in (16, 64, 128):
             raise ValueError(f"stream_rows must be 16, 64 or 128, got {stream_rows!r}")
         self.stream_rows = stream_rows
-        self.rows_rb = W8_ROWS_POLICY["gate_up" if swiglu_up is not None else "down"]
         self.N, self.K = w.shape
+        self.kind = _head_kind(kind, swiglu_up, stream_rows)
+        self.rows_rb = () if self.kind else W8_ROWS_POLICY["gate_up" if swiglu_up is not None else "down"]
+        self.stream = bool(HEAD_POLICY["fp8"]) if self.kind and self.K == HEAD_K else True
         self.Kp = (self.K + 31) // 32 * 32
         self.swiglu = swiglu_up is not None
         self.device = w.device
@@ -387,13 +410,17 @@ class PackedLinearW8:
 
     def streams(self, rows):
         """Whether a call of `rows` fp32 rows streams the codes (else it runs the bf16 image)."""
-        return rows <= 16 or (rows <= self.stream_rows and (rows + 15) // 16 in self.rows_rb)
+        if rows <= 16:
+            return self.stream
+        return rows <= self.stream_rows and (rows + 15) // 16 in self.rows_rb
 
     def __call__(self, x, out=None, act="none", residual=False, out_dtype=F32, splitk=0, M=None, norm=None,
                  stats_out=None, xpack=None, ypack=None):
         rows = x.shape[0] if M is None else M
+        head = self.kind == "head" and self.K == HEAD_K   # (the head entry is plain: anything else runs the image)
         if (not self.streams(rows) or x.dtype != F32 or act != "none" or out_dtype != F32 or
-                (out is not None and out.dtype != F32)):
+                (out is not None and out.dtype != F32) or
+                (head and (residual or norm is not None or stats_out is not None))):
             return self.bf16(x, out=out, act=act, residual=residual, out_dtype=out_dtype, splitk=splitk, M=M, norm=norm,
                              stats_out=stats_out, xpack=xpack, ypack=ypack)
         import ctypes
@@ -402,6 +429,10 @@ class PackedLinearW8:
             raise ValueError(f"PackedLinearW8 input needs unit stride and >= {self.Kp} columns, got {tuple(x.shape)}")
         if out is None:
             out = torch.empty(rows, self.N, dtype=F32, device=x.device)
+        if head:
+            _lib.call("fo_gemm_w8_head", x.data_ptr(), x.stride(0), rows, self.Kp, self.q.data_ptr(),
+                      self.scales.data_ptr(), self.ntiles, self.N, out.data_ptr(), out.stride(0), stream(x.device))
+            return out
         rst, rg, eps, so, gn, yg = _norm_args(norm, stats_out, out)
         if stats_out is not None and (self.N + 15) // 16 > stats_out.max_groups:
             raise RuntimeError(f"RowStats holds {stats_out.max_groups} groups per row, fo_gemm_w8 writes "
@@ -469,22 +500,27 @@ class PackedLinearW4:
     stream_rows: 16 (default) or 64.  64 also lets calls of 17..64 fp32 rows stream the codes (fo_gemm_w4_rows), for
     the row-block counts in `rows_rb`: W4_ROWS_POLICY's for this GEMM, the pairs that measured faster than the image.
     Setting `stream = True` on an instance sends every <= 16-row call to the codes, `rows_rb = (2, 3, 4)` every call of
-    17 rows up to stream_rows (tests, A/B scripts)."""
+    17 rows up to stream_rows (tests, A/B scripts).
+    kind="head": the Qwen2 output head (see _head_kind): plain, stream_rows 16, no entry in either policy above."""
 
     bias = None
 
-    def __init__(self, w, swiglu_up=None, receive=False, stream_rows=16):
+    def __init__(self, w, swiglu_up=None, receive=False, stream_rows=16, kind=None):
         _check_dev(w)
         if stream_rows not in (16, 64):
             raise ValueError(f"stream_rows must be 16 or 64, got {stream_rows!r}")
         self.stream_rows = stream_rows
-        self.rows_rb = W4_ROWS_POLICY["gate_up" if swiglu_up is not None else "down"]
+        self.kind = _head_kind(kind, swiglu_up, stream_rows)
+        self.rows_rb = () if self.kind else W4_ROWS_POLICY["gate_up" if swiglu_up is not None else "down"]
         self.N, self.K = w.shape
         if self.K % 32:
             raise ValueError(f"PackedLinearW4 needs K % 32 == 0 (the scale block), got K={self.K}")
         self.Kp = self.K
         self.swiglu = swiglu_up is not None
-        self.stream = bool(W4_POLICY["gate_up" if self.swiglu else "down"])
+        if self.kind:
+            self.stream = bool(HEAD_POLICY["mxfp4"]) if self.K == HEAD_K else True
+        else:
+            self.stream = bool(W4_POLICY["gate_up" if self.swiglu else "down"])
         self.device = w.device
         self.ntiles = (self.N + 15) // 16 * (2 if self.swiglu else 1)
         KK = (self.K + 127) // 128
@@ -520,8 +556,10 @@ class PackedLinearW4:
     def __call__(self, x, out=None, act="none", residual=False, out_dtype=F32, splitk=0, M=None, norm=None,
                  stats_out=None, xpack=None, ypack=None):
         rows = x.shape[0] if M is None else M
+        head = self.kind == "head" and self.K == HEAD_K   # (the head entry is plain: anything else runs the image)
         if (not self.streams(rows) or x.dtype != F32 or act != "none" or out_dtype != F32 or
-                (out is not None and out.dtype != F32)):
+                (out is not None and out.dtype != F32) or
+                (head and (residual or norm is not None or stats_out is not None))):
             return self.bf16(x, out=out, act=act, residual=residual, out_dtype=out_dtype, splitk=splitk, M=M, norm=norm,
                              stats_out=stats_out, xpack=xpack, ypack=ypack)
         import ctypes
@@ -530,6 +568,10 @@ class PackedLinearW4:
             raise ValueError(f"PackedLinearW4 input needs unit stride and >= {self.Kp} columns, got {tuple(x.shape)}")
         if out is None:
             out = torch.empty(rows, self.N, dtype=F32, device=x.device)
+        if head:
+            _lib.call("fo_gemm_w4_head", x.data_ptr(), x.stride(0), rows, self.Kp, self.q.data_ptr(),
+                      self.scales.data_ptr(), self.ntiles, self.N, out.data_ptr(), out.stride(0), stream(x.device))
+            return out
         rst, rg, eps, so, gn, yg = _norm_args(norm, stats_out, out)
         if stats_out is not None and (self.N + 15) // 16 > stats_out.max_groups:
             raise RuntimeError(f"RowStats holds {stats_out.max_groups} groups per row, fo_gemm_w4 writes "
@@ -585,6 +627,22 @@ def w4_launch_counts():
 
 def w4_launch_counts_reset():
     _lib.call("fo_gemm_w4_counts_reset")
+
+
+HEAD_LAUNCH_KINDS = ("w8_head", "w4_head")
+
+
+def head_launch_counts():
+    """{entry: fo_gemm_w8_head / fo_gemm_w4_head launches issued since the last reset} (host-side counters of their
+    own: these kernels have no FoLaunchKind; a captured graph counts at capture, a refused call not at all)."""
+    import ctypes
+    buf = (ctypes.c_longlong * 2)()
+    _lib.load().fo_gemm_head_counts(buf, 2)
+    return {k: int(buf[i]) for i, k in enumerate(HEAD_LAUNCH_KINDS)}
+
+
+def head_launch_counts_reset():
+    _lib.call("fo_gemm_head_counts_reset")
 
 
 def w4_rows_launch_count():

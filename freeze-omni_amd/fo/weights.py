@@ -127,20 +127,31 @@ class FakeQuantSource:
     dequantised -- exactly bf16 values).  An engine with mlp_weights="fp8" serves its weights through this, so the
     oracle, or a second engine of either mode, can be built on the same model.
     fmt: "fp8" (default) or "mxfp4", the image of mlp_weights="mxfp4": W' = q * 2^e with e2m1 codes and one e per
-    32-column block (fo.quant.quantize_blocks_e2m1)."""
+    32-column block (fo.quant.quantize_blocks_e2m1).
+    lm_head: None (default), "fp8" or "mxfp4": `lm_head.weight` is replaced by its image in that format too, the
+    model of an engine with lm_head_weights (model.embed_tokens.weight is never touched).
+    fmt=None (with lm_head): the MLP weights pass through unchanged -- a quantised head over a bf16 MLP."""
 
     MLP = ("mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
 
-    def __init__(self, inner, fmt="fp8"):
-        if fmt not in ("fp8", "mxfp4"):
+    def __init__(self, inner, fmt="fp8", lm_head=None):
+        if fmt not in ("fp8", "mxfp4") and not (fmt is None and lm_head is not None):
             raise ValueError(f"FakeQuantSource format must be 'fp8' or 'mxfp4', got {fmt!r}")
-        self.inner, self.fmt = inner, fmt
+        if lm_head not in (None, "fp8", "mxfp4"):
+            raise ValueError(f"FakeQuantSource lm_head must be None, 'fp8' or 'mxfp4', got {lm_head!r}")
+        self.inner, self.fmt, self.lm_head = inner, fmt, lm_head
 
     def __contains__(self, name):
         return name in self.inner
 
     def get(self, name, dtype=torch.float32):
-        if not (name.startswith("model.layers.") and name.endswith(self.MLP)):
+        if name == "lm_head.weight":
+            fmt = self.lm_head
+        elif name.startswith("model.layers.") and name.endswith(self.MLP):
+            fmt = self.fmt
+        else:
+            fmt = None
+        if fmt is None:
             return self.inner.get(name, dtype)
-        quant = ops.quant_w4 if self.fmt == "mxfp4" else ops.quant_w8
+        quant = ops.quant_w4 if fmt == "mxfp4" else ops.quant_w8
         return quant(self.inner.get(name, torch.bfloat16))[2].to(dtype)

@@ -281,6 +281,30 @@ int fo_gemm_w4_rows(const float* X, int ldx, int M, int K, const void* q, const 
 int fo_gemm_w4_counts(long long* out, int n);
 long long fo_gemm_w4_rows_count(void);
 int fo_gemm_w4_counts_reset(void);
+/* The Qwen2 output head (lm_head, 152,064 x 3584) under the same two formats, for calls of <= 16 rows:
+ * Y[M][N] = X . W'^T, plain -- the FP8 column scale (fo_gemm_w8_head) or nothing (fo_gemm_w4_head) and the store: no
+ * residual, no RMSNorm consumer or producer, no SwiGLU, no workspace and no tickets.
+ * Layout: q and scale are exactly fo_quant_w8's / fo_quant_w4's packed codes and scales of the [N][K] weight with
+ * tile_base 0 and tile_stride 1 (FP8: codes [tile][56][64 lanes][16 bytes] and fp32 2^e at [tile][16]; MXFP4: codes
+ * [tile][28][64 lanes][16 bytes] and E8M0 bytes at [tile][28][16 rows][4]); ntiles = ceil(N/16) is their extent.  X is
+ * fp32 [M][ldx] (split into bf16 hi + lo), Y fp32 [M][ldy].
+ * Kernel: the plain form of the X-stationary persistent kernels (k_w8_xs / k_w4_xs), compiled for K = 3584: X hi in
+ * registers and lo in LDS, split once per workgroup; min(units, CUs) workgroups with the units dealt evenly, a unit
+ * being the adjacent tiles 2u, 2u + 1 (the second tile of an odd count's last unit lies past the code descriptor --
+ * and, for MXFP4, the scale descriptor -- loads zeros and is never stored); the next unit's codes are issued before
+ * the current one is reduced; the cross-wave sum runs in wave order.  Rows >= M are computed from a clamped row and
+ * never stored, columns >= N of a ragged last tile are never stored.  Deterministic, capture-safe.
+ * Refused on the host before any HIP call, with the entry's name: M outside 1..16, K != 3584, K % 32 != 0, a NULL X,
+ * q, scale or Y, ldx < K or ldx % 4 != 0 or X not 16-byte aligned, ldy < N, ntiles != ceil(N/16), codes of 2 GiB or
+ * more.  Any other K runs fo_gemm_w8 / fo_gemm_w4's plain form; more rows run the bf16 image through fo_gemm.
+ * fo_gemm_head_counts: the launches issued by (fo_gemm_w8_head, fo_gemm_w4_head) since the last reset into
+ *   out[0 .. min(n, 2)); returns 2.  A refused call is not counted.  These kernels have no FoLaunchKind. */
+int fo_gemm_w8_head(const float* X, int ldx, int M, int K, const void* q, const float* scale, int ntiles, int N,
+                    float* Y, int ldy, hipStream_t stream);
+int fo_gemm_w4_head(const float* X, int ldx, int M, int K, const void* q, const void* scale, int ntiles, int N,
+                    float* Y, int ldy, hipStream_t stream);
+int fo_gemm_head_counts(long long* out, int n);
+int fo_gemm_head_counts_reset(void);
 /* Software-pipelined one-row-tile fp32-X weight-stream GEMMs (M <= 16, >= 64 MiB of weights: the next
  * k-group's weights + X in flight during this group's MFMAs).  3 (default): the measured policy; 0: plain
  * loops; 1 / 2: every such GEMM pipelined with 4 / 2 k-steps per group (sweeps).  Unset, the

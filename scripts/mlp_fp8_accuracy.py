@@ -4,7 +4,9 @@ reference's fbank features, tests/golden/fbank.npz) with the user chat prefix, t
 steps.  Prints the state-probability differences per chunk, the decision-row logit differences under teacher forcing
 with the bf16 engine's ids (and how often the arg-max agrees, against the bf16 top-2 margin), and where the two
 engines' own greedy texts part.  A measurement, not a test.
-python scripts/mlp_fp8_accuracy.py [steps] [fp8|mxfp4] (GPU only)"""
+python scripts/mlp_fp8_accuracy.py [steps] [fp8|mxfp4|bf16] [heads] (GPU only).  The optional third argument is a
+comma-separated list of lm_head_weights formats (`fp8,mxfp4`): each is measured against the bf16 engine in the same
+process, over the MLP mode of the second argument (`bf16`: the head alone is quantised)."""
 import os
 import sys
 
@@ -17,6 +19,7 @@ from fo.engine import FreezeOmniEngine  # noqa: E402
 
 STEPS = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 FMT = sys.argv[2] if len(sys.argv) > 2 else "fp8"
+HEADS = sys.argv[3].split(",") if len(sys.argv) > 3 else ["bf16"]
 SYS_IDS = list(range(1, 16))
 USER_PREFIX = [151645, 198, 151644, 872, 198]
 ASSIST_PREFIX = [151645, 198, 151644, 77091, 198]
@@ -53,27 +56,31 @@ def flow(eng, forced=None):
     return np.stack(probs), np.stack(logits), toks
 
 
-def engine(mode):
-    return FreezeOmniEngine(os.path.join(ROOT, "configs", "real"), device=dev, max_sessions=2, mlp_weights=mode)
+def engine(mode, head="bf16"):
+    return FreezeOmniEngine(os.path.join(ROOT, "configs", "real"), device=dev, max_sessions=2, mlp_weights=mode,
+                            lm_head_weights=head)
 
 
 eng = engine("bf16")
 p0, l0, t0 = flow(eng)
 del eng
 torch.cuda.empty_cache()
-eng = engine(FMT)
-print(f"mlp_weights={FMT} against bf16:")
-p1, l1, t1f = flow(eng, forced=t0)
-_, _, t1 = flow(eng)
-dp = np.abs(p1 - p0)
-print(f"state probs over {len(p0)} chunks: max |diff| {dp.max():.2e}, mean {dp.mean():.2e} "
-      f"(bf16 state_1 range {p0[:, 1].min():.3f}..{p0[:, 1].max():.3f})")
-dl = np.abs(l1 - l0)
-s = np.sort(l0, axis=1)
-margin = s[:, -1] - s[:, -2]
-agree = [a == b for a, b in zip(t0, t1f)]
-print(f"decision-row logits over {STEPS} teacher-forced steps: max |diff| {dl.max():.3e}, rms {np.sqrt((dl ** 2).mean()):.3e} "
-      f"(logit std {l0.std():.3f}); arg-max equal {sum(agree)}/{STEPS}; bf16 top-2 margin min {margin.min():.3e}, "
-      f"at the disagreeing steps {[round(float(m), 4) for m, a in zip(margin, agree) if not a]}")
-first = next((i for i, (a, b) in enumerate(zip(t0, t1)) if a != b), STEPS)
-print(f"greedy text, each engine on its own ids: equal for the first {first} of {STEPS} tokens")
+for head in HEADS:
+    eng = engine(FMT, head)
+    print(f"mlp_weights={FMT}{'' if head == 'bf16' else f' lm_head_weights={head}'} against bf16:")
+    p1, l1, t1f = flow(eng, forced=t0)
+    _, _, t1 = flow(eng)
+    del eng
+    torch.cuda.empty_cache()
+    dp = np.abs(p1 - p0)
+    print(f"state probs over {len(p0)} chunks: max |diff| {dp.max():.2e}, mean {dp.mean():.2e} "
+          f"(bf16 state_1 range {p0[:, 1].min():.3f}..{p0[:, 1].max():.3f})")
+    dl = np.abs(l1 - l0)
+    s = np.sort(l0, axis=1)
+    margin = s[:, -1] - s[:, -2]
+    agree = [a == b for a, b in zip(t0, t1f)]
+    print(f"decision-row logits over {STEPS} teacher-forced steps: max |diff| {dl.max():.3e}, rms {np.sqrt((dl ** 2).mean()):.3e} "
+          f"(logit std {l0.std():.3f}); arg-max equal {sum(agree)}/{STEPS}; bf16 top-2 margin min {margin.min():.3e}, "
+          f"at the disagreeing steps {[round(float(m), 4) for m, a in zip(margin, agree) if not a]}")
+    first = next((i for i, (a, b) in enumerate(zip(t0, t1)) if a != b), STEPS)
+    print(f"greedy text, each engine on its own ids: equal for the first {first} of {STEPS} tokens")
