@@ -60,6 +60,9 @@ def get_args(argv=None):
     p.add_argument("--llm_lm_head_weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
                    help="Qwen2 output head (lm_head) weights: bf16, weight-only FP8 (e4m3 codes x a power of two per "
                         "vocabulary row) or weight-only MXFP4 (e2m1 codes x a power of two per 32 columns)")
+    p.add_argument("--llm_attn_weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
+                   help="Qwen2 attention projection (q, k, v, o) weights: bf16, weight-only FP8 (e4m3 codes x a power of "
+                        "two per output row) or weight-only MXFP4 (e2m1 codes x a power of two per 32 columns)")
     p.add_argument("--role", default="You are a helpful assistant.")
     p.add_argument("--max_text_tokens", type=int, default=MAX_TEXT_TOKENS)
     args = p.parse_args(argv)

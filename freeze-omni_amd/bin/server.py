@@ -340,6 +340,7 @@ def dialog_session_factory(args):
     cfg["llm_mlp_mxfp4_rows"] = getattr(args, "llm_mlp_mxfp4_rows", None) or cfg.get("llm_mlp_mxfp4_rows", 16)
     cfg["llm_kv"] = getattr(args, "llm_kv", None) or cfg.get("llm_kv", "fp32")
     cfg["llm_lm_head_weights"] = getattr(args, "llm_lm_head_weights", None) or cfg.get("llm_lm_head_weights", "bf16")
+    cfg["llm_attn_weights"] = getattr(args, "llm_attn_weights", None) or cfg.get("llm_attn_weights", "bf16")
     ic = cfg.setdefault("inference_control", {})
     ic.update(top_k=args.top_k, top_p=args.top_p, temperature=args.temperature)
     DialogStateParams.DIALOG_STATE_PRED_CONFIGS = cfg
@@ -386,6 +387,9 @@ def get_parser():
                    help="Qwen2 paged KV cache element: fp32 (default), or bf16 (half the memory and attention bytes)")
     p.add_argument("--llm_lm_head_weights", choices=["bf16", "fp8", "mxfp4"], default=None,
                    help="Qwen2 output head (lm_head) weights: bf16 (default), weight-only FP8, or weight-only MXFP4")
+    p.add_argument("--llm_attn_weights", choices=["bf16", "fp8", "mxfp4"], default=None,
+                   help="Qwen2 attention projection (q, k, v, o) weights: bf16 (default), weight-only FP8, or "
+                        "weight-only MXFP4")
     p.add_argument("--config", default=None, help="duplex YAML (configs/dialog_state_pred_config.yaml form)")
     return p
 

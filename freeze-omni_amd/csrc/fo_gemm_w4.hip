@@ -17,7 +17,8 @@
 // Code layout (include/fo_hip.h): [tile][K128][64 lanes][16 bytes], a lane's dword j being its 8-element MFMA
 // B fragment of k-step 4 s + j (two codes per byte, the lower column in the low nibble), K padded to a multiple of
 // 128 with zero codes; scale bytes [tile][K128][16 rows][4].  fo_gemm_w4: k_w4 (general), k_w4_xs (the SwiGLU pair at
-// K = 3584) or k_w4_sk (long-K plain), the forms of fo_gemm_w8.hip; fo_gemm_w4_rows: k_w4_rows, then k_w8_rows_merge
+// K = 3584) or k_w4_sk (long-K plain), the forms of fo_gemm_w8.hip; fo_gemm_w4_qkv_rope: k_w4_qkv, k_w4's pair form
+// with the fused q|k|v epilogue (bias, RoPE, paged-KV append: fo_gemm_wq.h); fo_gemm_w4_rows: k_w4_rows, then k_w8_rows_merge
 // (fo_gemm_wq.h) where K is split.
 #include <stdlib.h>
 
@@ -135,6 +136,39 @@ __global__ __launch_bounds__(NW * 64) void k_w4(W8Args a) {
       if constexpr (SW) x2 += part[w][1][rr][c];
     }
     w8_epilogue<SW, false>(a, u, gridDim.x, rr, c, x1, x2, rstd_s);
+  }
+}
+
+// ---- the fused q|k|v projection (fo_gemm_w4_qkv_rope), as k_w8_qkv: k_w4's pair form with the RoPE + paged-KV
+// epilogue in place of SwiGLU.  Workgroup P = rope tile pair P (packed tiles 2P, 2P + 1: columns (i, i + hd/2) of one
+// head); the waves split the code steps as in k_w4 and the cross-wave sum runs in wave order.
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void k_w4_qkv(W8Args a, QkvRopeArgs r) {
+  constexpr int U = 1;
+  __shared__ float part[NW][2][16][17];
+  __shared__ float rstd_s[16];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int P = blockIdx.x;
+  const W4Srd d = w4_srd(a);
+  const int kb = (int)((long)a.KK * wave / NW), ke = (int)((long)a.KK * (wave + 1) / NW);
+  const int row = min(lane & 15, a.M - 1);
+  const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
+  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
+  f32x4 acc[2];
+  w4_accumulate<2, U>(a, d, xp, lane, 2 * P, kb, ke, acc);
+  w8_store_tile(part[wave][0], acc[0], lane);
+  w8_store_tile(part[wave][1], acc[1], lane);
+  __syncthreads();
+  const int e = threadIdx.x;
+  if (e < 256) {
+    const int rr = e >> 4, c = e & 15;
+    float x1 = 0.f, x2 = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      x1 += part[w][0][rr][c];
+      x2 += part[w][1][rr][c];
+    }
+    wq_rope_epilogue<false>(a, r, P, rr, c, x1, x2, rstd_s);
   }
 }
 
@@ -512,6 +546,8 @@ std::atomic<long long> g_w4_launches[3];
 std::atomic<long long> g_w4_rows_calls;
 // the launches of the two lm_head streams (fo_gemm_head_counts): fo_gemm_w8_head, fo_gemm_w4_head
 std::atomic<long long> g_head_launches[2];
+// the launches of the two quantised q|k|v streams (fo_gemm_qkv_quant_counts): fo_gemm_w8_qkv_rope, fo_gemm_w4_qkv_rope
+std::atomic<long long> g_qkv_launches[2];
 
 // What the two GEMM entries share: the checks of everything but the workspace (all before the entry's first HIP call),
 // then W8Args (with KK) and the output tile count.  `fn` is the entry's name, [m_lo, m_hi] its row band and `serves`
@@ -546,6 +582,7 @@ int w4_args(const char* fn, int m_lo, int m_hi, const char* serves, const float*
 }  // namespace
 
 void fo::count_head(int slot) { g_head_launches[slot].fetch_add(1, std::memory_order_relaxed); }
+void fo::count_qkv_quant(int slot) { g_qkv_launches[slot].fetch_add(1, std::memory_order_relaxed); }
 
 extern "C" {
 
@@ -651,6 +688,38 @@ int fo_gemm_w4_head(const float* X, int ldx, int M, int K, const void* Q, const 
   hipLaunchKernelGGL((k_w4_xs<14, 2, false>), dim3(G), dim3(896), 0, stream, a, units);
   fo::count_head(1);
   return fo::check_launch("fo_gemm_w4_head");
+}
+
+int fo_gemm_qkv_quant_counts(long long* out, int n) {
+  for (int i = 0; out && i < n && i < 2; ++i) out[i] = g_qkv_launches[i].load(std::memory_order_relaxed);
+  return 2;
+}
+int fo_gemm_qkv_quant_counts_reset(void) {
+  for (int i = 0; i < 2; ++i) g_qkv_launches[i].store(0, std::memory_order_relaxed);
+  return 0;
+}
+
+int fo_gemm_w4_qkv_rope(const float* X, int ldx, int M, int K, const void* Q, const void* scale, int ntiles, int N,
+                        const float* bias, const float* rstats, int rgroups, float eps, const int* pos, const int* slot,
+                        const float* cos_t, const float* sin_t, float* q_out, void* kc, void* vc, int H, int KVH, int hd,
+                        int PS, int kv_bytes, hipStream_t stream) {
+  // every check before the first HIP call (q_out stands where w4_args expects an output: N floats per row)
+  W8Args a;
+  QkvRopeArgs r;
+  int tiles;
+  if (const int rc = w4_args("fo_gemm_w4_qkv_rope", 1, 16,
+                             "the MXFP4 q|k|v stream serves M <= 16 (more rows run the bf16 image)", X, ldx, M, K, Q,
+                             scale, ntiles, N, 0, q_out, N, 0, rstats, rgroups, eps, nullptr, nullptr, nullptr, a, tiles))
+    return rc;
+  if (const int rc = qkv_rope_args("fo_gemm_w4_qkv_rope", N, bias, pos, slot, cos_t, sin_t, q_out, kc, vc, H, KVH, hd,
+                                   PS, kv_bytes, r))
+    return rc;
+  // one workgroup per rope tile pair (Qwen2-7B: 144); 16 waves where each still gets a code step
+  const int pairs = ntiles / 2;
+  if (a.KK >= 16) hipLaunchKernelGGL((k_w4_qkv<16>), dim3(pairs), dim3(1024), 0, stream, a, r);
+  else hipLaunchKernelGGL((k_w4_qkv<4>), dim3(pairs), dim3(256), 0, stream, a, r);
+  fo::count_qkv_quant(1);
+  return fo::check_launch("fo_gemm_w4_qkv_rope");
 }
 
 int fo_gemm_w4_rows(const float* X, int ldx, int M, int K, const void* Q, const void* scale, int ntiles, int N,

@@ -14,6 +14,8 @@
 // band, each kernel's design above the kernel:
 //  * fo_gemm_w8, <= 16 rows: k_w8 (general), k_w8_xs (the SwiGLU pair at K = 3584) or k_w8_sk (long-K plain);
 //  * fo_gemm_w8_head, <= 16 rows: k_w8_xs's plain form at K = 3584 (the Qwen2 lm_head);
+//  * fo_gemm_w8_qkv_rope, <= 16 rows: k_w8_qkv, k_w8's pair form with the fused q|k|v epilogue (bias, RoPE, paged-KV
+//    append: fo_gemm_wq.h) over the rope-paired tile order of PackedLinear(rope_hd=...);
 //  * fo_gemm_w8_rows, 17..64 rows: k_w8_rows, then k_w8_rows_merge where K is split;
 //  * fo_gemm_w8_rows128, 65..128 rows: k_w8_rows128, then k_w8_rows_merge.
 #include <stdlib.h>
@@ -119,6 +121,40 @@ __global__ __launch_bounds__(NW * 64) void k_w8(W8Args a) {
       if constexpr (SW) x2 += part[w][1][rr][c];
     }
     w8_epilogue<SW>(a, u, gridDim.x, rr, c, x1, x2, rstd_s);
+  }
+}
+
+// ---- the fused q|k|v projection (fo_gemm_w8_qkv_rope): k_w8's pair form with the RoPE + paged-KV epilogue in place
+// of SwiGLU.  Workgroup P = rope tile pair P (packed tiles 2P, 2P + 1: columns (i, i + hd/2) of one head); the waves
+// split the code steps as in k_w8 and the cross-wave sum runs in wave order.  No workspace, no tickets.
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void k_w8_qkv(W8Args a, QkvRopeArgs r) {
+  constexpr int U = 2;
+  __shared__ float part[NW][2][16][17];
+  __shared__ float rstd_s[16];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int P = blockIdx.x;
+  const __amdgpu_buffer_rsrc_t srd = rsrc_of(a.Q, a.ntiles * a.KK * 1024);
+  const int kb = (int)((long)a.KK * wave / NW), ke = (int)((long)a.KK * (wave + 1) / NW);
+  const int row = min(lane & 15, a.M - 1);
+  const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
+  const int voff = lane * 16;
+  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
+  f32x4 acc[2];
+  w8_accumulate<2, U>(a, srd, xp, voff, 2 * P, kb, ke, acc);
+  w8_store_tile(part[wave][0], acc[0], lane);
+  w8_store_tile(part[wave][1], acc[1], lane);
+  __syncthreads();
+  const int e = threadIdx.x;
+  if (e < 256) {
+    const int rr = e >> 4, c = e & 15;
+    float x1 = 0.f, x2 = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      x1 += part[w][0][rr][c];
+      x2 += part[w][1][rr][c];
+    }
+    wq_rope_epilogue<true>(a, r, P, rr, c, x1, x2, rstd_s);
   }
 }
 
@@ -746,6 +782,29 @@ int fo_gemm_w8_head(const float* X, int ldx, int M, int K, const void* Q, const 
   hipLaunchKernelGGL((k_w8_xs<14, 4, false>), dim3(G), dim3(896), 0, stream, a, units);
   fo::count_head(0);
   return fo::check_launch("fo_gemm_w8_head");
+}
+
+int fo_gemm_w8_qkv_rope(const float* X, int ldx, int M, int K, const void* Q, const float* scale, int ntiles, int N,
+                        const float* bias, const float* rstats, int rgroups, float eps, const int* pos, const int* slot,
+                        const float* cos_t, const float* sin_t, float* q_out, void* kc, void* vc, int H, int KVH, int hd,
+                        int PS, int kv_bytes, hipStream_t stream) {
+  // every check before the first HIP call (q_out stands where w8_args expects an output: N floats per row)
+  W8Args a;
+  QkvRopeArgs r;
+  int tiles;
+  if (const int rc = w8_args("fo_gemm_w8_qkv_rope", 1, 16,
+                             "the FP8 q|k|v stream serves M <= 16 (more rows run the bf16 image)", X, ldx, M, K, Q,
+                             scale, ntiles, N, 0, q_out, N, 0, rstats, rgroups, eps, nullptr, nullptr, nullptr, a, tiles))
+    return rc;
+  if (const int rc = qkv_rope_args("fo_gemm_w8_qkv_rope", N, bias, pos, slot, cos_t, sin_t, q_out, kc, vc, H, KVH, hd,
+                                   PS, kv_bytes, r))
+    return rc;
+  // one workgroup per rope tile pair (Qwen2-7B: 144); 16 waves where each still gets two code steps
+  const int pairs = ntiles / 2;
+  if (a.KK >= 32) hipLaunchKernelGGL((k_w8_qkv<16>), dim3(pairs), dim3(1024), 0, stream, a, r);
+  else hipLaunchKernelGGL((k_w8_qkv<4>), dim3(pairs), dim3(256), 0, stream, a, r);
+  fo::count_qkv_quant(0);
+  return fo::check_launch("fo_gemm_w8_qkv_rope");
 }
 
 int fo_gemm_w8_rows(const float* X, int ldx, int M, int K, const void* Q, const float* scale, int ntiles, int N,

@@ -8,6 +8,9 @@ namespace fo {
 // the launch counters of the lm_head streams (fo_gemm_head_counts, fo_gemm_w4.hip): slot 0 fo_gemm_w8_head, slot 1
 // fo_gemm_w4_head.  Counters of their own: these kernels have no FoLaunchKind.
 void count_head(int slot);
+// the launch counters of the quantised q|k|v streams (fo_gemm_qkv_quant_counts, fo_gemm_w4.hip): slot 0
+// fo_gemm_w8_qkv_rope, slot 1 fo_gemm_w4_qkv_rope
+void count_qkv_quant(int slot);
 }  // namespace fo
 
 namespace {
@@ -33,6 +36,78 @@ struct W8Args {
   int rgroups;
   float reps;
 };
+
+// The fused q|k|v projection's epilogue on the code streams (fo_gemm_w8_qkv_rope / fo_gemm_w4_qkv_rope): what
+// fo_gemm_qkv_rope_kv's GemmArgs carry in their r* fields (fo_gemm.hip), beside W8Args.
+struct QkvRopeArgs {
+  const float* bias;   // [N] or NULL
+  const int* pos;      // [M] the token's position
+  const int* slot;     // [M] the token's slot of the paged cache
+  const float* cos_t;  // [pos][hd/2]
+  const float* sin_t;
+  float* q_out;        // [M][H * hd]
+  void* kc;            // one layer's pages [page][KVH][PS][hd]: fp32, or bf16 elements (kv16)
+  void* vc;
+  int H, KVH, hd, PS;
+  int kv16;            // the cache holds bf16: K / V stored as f2bf(x)
+  int kvb;             // an fp32 cache takes the bf16 value of K / V (fo_set_kv_bf16)
+};
+
+// Elements o and o + half of the paged cache `base`, as fo_gemm.hip's kv_store
+__device__ __forceinline__ void wq_kv_store(const QkvRopeArgs& r, void* base, size_t o, int half, float x1, float x2) {
+  if (r.kv16) {
+    bf16_t* d = reinterpret_cast<bf16_t*>(base) + o;
+    d[0] = f2bf(x1);
+    d[half] = f2bf(x2);
+  } else {
+    float* d = reinterpret_cast<float*>(base) + o;
+    d[0] = r.kvb ? bf2f(f2bf(x1)) : x1;
+    d[half] = r.kvb ? bf2f(f2bf(x2)) : x2;
+  }
+}
+
+// Output elements (row rr, logical columns n and n + hd/2) of rope tile pair P, n = rope_col(P, c): x1 / x2 are the
+// fp32 sums of packed tiles 2P / 2P + 1.  In this order: the FP8 column scales (SCALED; the MXFP4 sums carry their
+// block scales already), the consumer's rstd, the bias, rotate_half RoPE at pos[rr] for q and k heads, the store: q to
+// q_out, K and V to the paged cache at slot[rr].  Rows >= M (computed from a clamped row) are never stored.
+template <bool SCALED>
+__device__ __forceinline__ void wq_rope_epilogue(const W8Args& a, const QkvRopeArgs& r, int P, int rr, int c, float x1,
+                                                 float x2, const float* rstd_s) {
+  if (rr >= a.M) return;
+  const int hd = r.hd, half = hd >> 1, per = hd >> 5;   // per: tile pairs per head
+  const int h = P / per, i = (P - h * per) * 16 + c;
+  const int n = h * hd + i;
+  if constexpr (SCALED) {
+    x1 *= a.scale[(2 * P) * 16 + c];
+    x2 *= a.scale[(2 * P + 1) * 16 + c];
+  }
+  if (a.rstats) {
+    x1 *= rstd_s[rr];
+    x2 *= rstd_s[rr];
+  }
+  if (r.bias) {
+    x1 += r.bias[n];
+    x2 += r.bias[n + half];
+  }
+  if (h < r.H + r.KVH) {
+    const int p = r.pos[rr];
+    const float cs = r.cos_t[(size_t)p * half + i], sn = r.sin_t[(size_t)p * half + i];
+    const float o1 = x1 * cs - x2 * sn, o2 = x2 * cs + x1 * sn;
+    x1 = o1;
+    x2 = o2;
+  }
+  if (h < r.H) {
+    float* d = r.q_out + (size_t)rr * r.H * hd + (size_t)h * hd;
+    d[i] = x1;
+    d[i + half] = x2;
+    return;
+  }
+  const int sl = r.slot[rr];
+  const int page = sl / r.PS, off = sl - page * r.PS;
+  const bool isk = h < r.H + r.KVH;
+  const int kvh = h - r.H - (isk ? 0 : r.KVH);
+  wq_kv_store(r, isk ? r.kc : r.vc, (((size_t)page * r.KVH + kvh) * r.PS + off) * hd + i, half, x1, x2);
+}
 
 __device__ __forceinline__ void split8(const float4 p0, const float4 p1, bf16x8& hi, bf16x8& lo) {
   const float f[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
@@ -146,6 +221,24 @@ void launch_merge(const W8Args& a, int swiglu, int units, int RB, int S, const f
     hipLaunchKernelGGL((k_w8_rows_merge<true, SCALED>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
   else
     hipLaunchKernelGGL((k_w8_rows_merge<false, SCALED>), dim3(units, RB), dim3(256), 0, stream, a, S, ws, RB * 16);
+}
+
+// What the two quantised q|k|v entries check beside w8_args / w4_args (all on the host, before any HIP call), then
+// QkvRopeArgs.  `fn` is the entry's name.
+inline int qkv_rope_args(const char* fn, int N, const float* bias, const int* pos, const int* slot, const float* cos_t,
+                         const float* sin_t, float* q_out, void* kc, void* vc, int H, int KVH, int hd, int PS,
+                         int kv_bytes, QkvRopeArgs& r) {
+  FO_REQUIRE(pos && slot && cos_t && sin_t && q_out && kc && vc,
+             "%s: NULL pos, slot, cos_t, sin_t, q_out, kc or vc", fn);
+  FO_REQUIRE(kv_bytes == 4 || kv_bytes == 2, "%s: kv_bytes %d (4 = fp32, 2 = bf16)", fn, kv_bytes);
+  FO_REQUIRE(PS > 0, "%s: PS=%d (slots per page)", fn, PS);
+  FO_REQUIRE(hd > 0 && (hd & 31) == 0, "%s: hd=%d must be a multiple of 32 (a tile pair holds columns i, i + hd/2)", fn,
+             hd);
+  FO_REQUIRE(H > 0 && KVH > 0 && (long long)N == ((long long)H + 2ll * KVH) * hd, "%s: N=%d != (H + 2 KVH) * hd (H=%d "
+             "KVH=%d hd=%d)", fn, N, H, KVH, hd);
+  r = QkvRopeArgs{bias, pos, slot, cos_t, sin_t, q_out, kc, vc, H, KVH, hd, PS, kv_bytes == 2 ? 1 : 0,
+                  fo::kv_bf16_values()};
+  return 0;
 }
 
 }  // namespace

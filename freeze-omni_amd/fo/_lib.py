@@ -107,6 +107,12 @@ _SIGS = {
     "fo_gemm_w4_head": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_int, c_vp]),
     "fo_gemm_head_counts": (c_int, [ctypes.POINTER(c_ll), c_int]),
     "fo_gemm_head_counts_reset": (c_int, []),
+    "fo_gemm_w8_qkv_rope": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_float,
+                                    c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
+    "fo_gemm_w4_qkv_rope": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_float,
+                                    c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
+    "fo_gemm_qkv_quant_counts": (c_int, [ctypes.POINTER(c_ll), c_int]),
+    "fo_gemm_qkv_quant_counts_reset": (c_int, []),
     "fo_gemm_pick_split": (c_int, [c_int, c_int, c_int]),
     "fo_gemm": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
                         c_int, c_int, c_vp, c_ll, c_vp, c_int, c_vp]),

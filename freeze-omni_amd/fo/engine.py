@@ -69,8 +69,14 @@ def make_source(cfg, synth, device, model_path=None, llm_path=None, receive=Fals
 class FreezeOmniEngine:
     def __init__(self, model_path, llm_path=None, device="cuda:0", max_sessions=64, llm_kv_tokens=None,
                  tts_kv_tokens=None, source=None, receive_weights=False, train_yaml=None, mlp_weights="bf16",
-                 mlp_fp8_rows=16, llm_kv="fp32", mlp_mxfp4_rows=16, lm_head_weights="bf16"):
-        """lm_head_weights: "bf16" (default), "fp8" or "mxfp4": the Qwen2 output head (lm_head.weight only, never the
+                 mlp_fp8_rows=16, llm_kv="fp32", mlp_mxfp4_rows=16, lm_head_weights="bf16",
+                 attn_weights="bf16"):
+        """attn_weights: "bf16" (default), "fp8" or "mxfp4": self_attn.{q,k,v,o}_proj.weight of every Qwen2 layer under
+        weight-only FP8 per output row or MXFP4, independent of mlp_weights, mlp_*_rows, lm_head_weights
+        and llm_kv; the biases and the AR speech decoder's stack are untouched.  Steps of <= 16 rows stream the codes
+        where ops.ATTN_POLICY says so; everything else runs the exact bf16 image.  `src` serves the dequantised
+        projections (FakeQuantSource(..., attn=...)).
+        lm_head_weights: "bf16" (default), "fp8" or "mxfp4": the Qwen2 output head (lm_head.weight only, never the
         embedding) under weight-only FP8 per vocabulary row or MXFP4, independent of mlp_weights,
         mlp_*_rows and llm_kv.  Calls of <= 16 rows (the captured TextGraph, the eager text_step, LLMEngine.logits)
         stream the codes where ops.HEAD_POLICY says so; more rows run the exact bf16 image.  `src` serves the
@@ -113,6 +119,9 @@ class FreezeOmniEngine:
             raise ValueError(f"llm_kv must be 'fp32' or 'bf16', got {llm_kv!r}")
         if lm_head_weights not in ("bf16", "fp8", "mxfp4"):
             raise ValueError(f"lm_head_weights must be 'bf16', 'fp8' or 'mxfp4', got {lm_head_weights!r}")
+        if attn_weights not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"attn_weights must be 'bf16', 'fp8' or 'mxfp4', got {attn_weights!r}")
+        self.attn_weights = attn_weights
         self.lm_head_weights = lm_head_weights
         self.mlp_weights = mlp_weights
         self.mlp_fp8_rows = mlp_fp8_rows
@@ -143,7 +152,7 @@ class FreezeOmniEngine:
                              kv_tokens=llm_kv_tokens or min(max_sessions * 4096, 1 << 17),
                              mlp_w8=mlp_weights == "fp8", mlp_w8_rows=mlp_fp8_rows, kv_dtype=llm_kv,
                              mlp_w4=mlp_weights == "mxfp4", mlp_w4_rows=mlp_mxfp4_rows,
-                             lm_head_weights=lm_head_weights)
+                             lm_head_weights=lm_head_weights, attn_weights=attn_weights)
         self.tts = TTSEngine(src, self.cfg["decoder_json"], self.device,
                              kv_tokens=tts_kv_tokens or min(max_sessions * 2048, 1 << 17))
         self.codec = CodecEngine(src, self.cfg["codec_json"], self.device)
@@ -160,14 +169,15 @@ class FreezeOmniEngine:
         self._chat_template(ty["model_conf"].get("chat_template"))
 
     def _model_source(self, raw):
-        """`raw` as the model this engine computes: the MLP and / or the head replaced by their quantised images
-        (fo.weights.FakeQuantSource; the engines themselves quantise the raw weights)."""
+        """`raw` as the model this engine computes: the MLP, the head and / or the attention projections replaced by
+        their quantised images (fo.weights.FakeQuantSource; the engines themselves quantise the raw weights)."""
         mlp = self.mlp_weights if self.mlp_weights != "bf16" else None
         head = self.lm_head_weights if self.lm_head_weights != "bf16" else None
-        if mlp is None and head is None:
+        attn = self.attn_weights if self.attn_weights != "bf16" else None
+        if mlp is None and head is None and attn is None:
             return raw
         from .weights import FakeQuantSource
-        return FakeQuantSource(raw, mlp, lm_head=head)
+        return FakeQuantSource(raw, mlp, lm_head=head, attn=attn)
 
     # ------------------------------------------------------------------ models/utils.py:11-28
     def rebind_audiollm(self, state):
@@ -201,7 +211,8 @@ class FreezeOmniEngine:
             self.llm = LLMEngine(src, self.cfg["llm"], self.device, kv_tokens=kv_tokens,
                                  mlp_w8=self.mlp_weights == "fp8", mlp_w8_rows=self.mlp_fp8_rows,
                                  kv_dtype=self.llm_kv, mlp_w4=self.mlp_weights == "mxfp4",
-                                 mlp_w4_rows=self.mlp_mxfp4_rows, lm_head_weights=self.lm_head_weights)
+                                 mlp_w4_rows=self.mlp_mxfp4_rows, lm_head_weights=self.lm_head_weights,
+                                 attn_weights=self.attn_weights)
         elif "predictor_head.weight" in src:
             self.llm.head_w, self.llm.head_b = src.get("predictor_head.weight"), src.get("predictor_head.bias")
         self.src = self._model_source(src) if fq else src

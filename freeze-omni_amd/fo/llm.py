@@ -15,8 +15,12 @@ from .weights import ReceiveSource
 
 class LLMEngine:
     def __init__(self, src, llm_cfg, device, head_src=None, kv_tokens=65536, page_size=16, max_pos=None,
-                 mlp_w8=False, mlp_w8_rows=16, kv_dtype="fp32", mlp_w4=False, mlp_w4_rows=16, lm_head_weights="bf16"):
-        """lm_head_weights: "bf16" (default), "fp8" or "mxfp4" -- lm_head.weight under weight-only FP8 / MXFP4 (DESIGN
+                 mlp_w8=False, mlp_w8_rows=16, kv_dtype="fp32", mlp_w4=False, mlp_w4_rows=16, lm_head_weights="bf16",
+                 attn_weights="bf16"):
+        """attn_weights: "bf16" (default), "fp8" or "mxfp4" -- self_attn.{q,k,v,o}_proj.weight of every layer under
+        weight-only FP8 / MXFP4 (DecoderStack attn_w): steps of <= 16 rows stream the codes where
+        ops.ATTN_POLICY says so, everything else runs the exact bf16 image.  The biases are untouched.
+        lm_head_weights: "bf16" (default), "fp8" or "mxfp4" -- lm_head.weight under weight-only FP8 / MXFP4 (DESIGN
         §5.8): calls of <= 16 rows stream the codes where ops.HEAD_POLICY says so, every other call runs the exact
         bf16 image.  embed_tokens is never quantised.  Over a ReceiveSource the head's storages are allocated and nothing
         is quantised (a replica whose weights arrive by broadcast fills codes, scales and image).
@@ -26,6 +30,9 @@ class LLMEngine:
             raise ValueError(f'kv_dtype must be "fp32" or "bf16", got {kv_dtype!r}')
         if lm_head_weights not in ("bf16", "fp8", "mxfp4"):
             raise ValueError(f"lm_head_weights must be 'bf16', 'fp8' or 'mxfp4', got {lm_head_weights!r}")
+        if attn_weights not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"attn_weights must be 'bf16', 'fp8' or 'mxfp4', got {attn_weights!r}")
+        self.attn_weights = attn_weights
         self.lm_head_weights = lm_head_weights
         self.kv_dtype = kv_dtype
         c = llm_cfg
@@ -42,7 +49,8 @@ class LLMEngine:
                            dtype=torch.bfloat16 if kv_dtype == "bf16" else torch.float32)
         self.stack = DecoderStack(src, "model.layers.", c["num_hidden_layers"], self.D, self.H, self.KVH, self.eps,
                                   True, self.rope, self.pool, first_fp16=True, mlp_w8=mlp_w8,
-                                  mlp_w8_rows=mlp_w8_rows, mlp_w4=mlp_w4, mlp_w4_rows=mlp_w4_rows)
+                                  mlp_w8_rows=mlp_w8_rows, mlp_w4=mlp_w4, mlp_w4_rows=mlp_w4_rows,
+                                  attn_w=None if attn_weights == "bf16" else attn_weights)
         self.embed_tokens = src.get("model.embed_tokens.weight", torch.bfloat16)
         self.norm = src.get("model.norm.weight")
         if lm_head_weights == "bf16":
@@ -66,6 +74,14 @@ class LLMEngine:
     @property
     def mlp_fp4_bytes(self):
         return self.stack.mlp_fp4_bytes
+
+    @property
+    def attn_fp8_bytes(self):
+        return self.stack.attn_fp8_bytes
+
+    @property
+    def attn_fp4_bytes(self):
+        return self.stack.attn_fp4_bytes
 
     @property
     def lm_head_fp8_bytes(self):

@@ -335,12 +335,35 @@ HEAD_POLICY = {"fp8": True, "mxfp4": True}
 HEAD_K = 3584   # the K the X-stationary plain forms are compiled for
 
 
+# Which <= 16-row GEMMs of the quantised Qwen2 attention projections (attn_weights; PackedQKVQuant, and PackedLinearW8 /
+# PackedLinearW4 with kind="attn_o") stream the codes: a (format, GEMM) pair enters only if, at both 8 and 16 rows, its
+# median beat the bf16 image on today's kernel by more than that arm's repeat-to-repeat spread (DESIGN 5.5's rule;
+# scripts/gemm_attn_ab.py, profiles/attn_quant_gemm_ab.txt).  A pair that is false keeps the model and runs
+# the image at every row count.  Builder-run at real geometry, every arm cycling over more than 512 MB of its own
+# copies (medians, us, bf16 image / fp8 / mxfp4; the bf16 spread was 0.0-0.1 us everywhere):
+#   q|k|v (4608 x 3584, fo_gemm_w8_qkv_rope / fo_gemm_w4_qkv_rope): 12.9 / 9.6 / 9.9 at 8 rows, 13.1 / 11.8 / 11.6 at 16
+#   (11.6 / 8.7 / 8.5 at 1 row): both formats entered;
+#   o (3584 x 3584, fo_gemm_w8 / fo_gemm_w4's general form): 9.7 / 8.2 / 8.2 at 8 rows but 10.4 / 10.6 / 10.5 at 16, where
+#   the image reads the attention's packed output: neither format entered.
+# The one place the policy lives.
+ATTN_POLICY = {"fp8": {"qkv": True, "o": False}, "mxfp4": {"qkv": True, "o": False}}
+
+
 def _head_kind(kind, swiglu_up, stream_rows):
-    if kind not in (None, "head"):
-        raise ValueError(f"kind must be None or 'head', got {kind!r}")
-    if kind == "head" and (swiglu_up is not None or stream_rows != 16):
-        raise ValueError("a head is a plain projection with stream_rows=16")
+    if kind not in (None, "head", "attn_o"):
+        raise ValueError(f"kind must be None, 'head' or 'attn_o', got {kind!r}")
+    if kind is not None and (swiglu_up is not None or stream_rows != 16):
+        raise ValueError("a head or an attention output is a plain projection with stream_rows=16")
     return kind
+
+
+def _kind_stream(kind, fmt, K, default):
+    """Whether a <= 16-row call of a PackedLinearW8 / W4 of this kind streams the codes."""
+    if kind == "head":
+        return bool(HEAD_POLICY[fmt]) if K == HEAD_K else True
+    if kind == "attn_o":
+        return bool(ATTN_POLICY[fmt]["o"])
+    return default
 
 
 # Which 17..64-row launches of a PackedLinearW8(stream_rows=64) stream the codes: per GEMM, the row-block counts
@@ -365,7 +388,9 @@ class PackedLinearW8:
     128 calls of 65..128 rows as well (fo_gemm_w8_rows128), for the row-block counts in `rows_rb`: W8_ROWS_POLICY's for
     this GEMM, the pairs that measured faster than the image.  Setting `rows_rb = tuple(range(2, 9))` on an instance
     sends every call of 17 rows up to stream_rows there (tests, A/B scripts).
-    kind="head": the Qwen2 output head (see _head_kind): plain, stream_rows 16, no row-stream policy of its own."""
+    kind="head": the Qwen2 output head (see _head_kind): plain, stream_rows 16, no row-stream policy of its own.
+    kind="attn_o": a Qwen2 attention output projection (attn_weights): plain, stream_rows 16, `stream` from
+    ATTN_POLICY; its <= 16-row calls run fo_gemm_w8's general form with the residual and stats_out."""
 
     bias = None
 
@@ -377,7 +402,7 @@ class PackedLinearW8:
         self.N, self.K = w.shape
         self.kind = _head_kind(kind, swiglu_up, stream_rows)
         self.rows_rb = () if self.kind else W8_ROWS_POLICY["gate_up" if swiglu_up is not None else "down"]
-        self.stream = bool(HEAD_POLICY["fp8"]) if self.kind and self.K == HEAD_K else True
+        self.stream = _kind_stream(self.kind, "fp8", self.K, True)
         self.Kp = (self.K + 31) // 32 * 32
         self.swiglu = swiglu_up is not None
         self.device = w.device
@@ -501,7 +526,9 @@ class PackedLinearW4:
     the row-block counts in `rows_rb`: W4_ROWS_POLICY's for this GEMM, the pairs that measured faster than the image.
     Setting `stream = True` on an instance sends every <= 16-row call to the codes, `rows_rb = (2, 3, 4)` every call of
     17 rows up to stream_rows (tests, A/B scripts).
-    kind="head": the Qwen2 output head (see _head_kind): plain, stream_rows 16, no entry in either policy above."""
+    kind="head": the Qwen2 output head (see _head_kind): plain, stream_rows 16, no entry in either policy above.
+    kind="attn_o": a Qwen2 attention output projection (attn_weights): plain, stream_rows 16, `stream` from
+    ATTN_POLICY; its <= 16-row calls run fo_gemm_w4's general form with the residual and stats_out."""
 
     bias = None
 
@@ -517,10 +544,7 @@ class PackedLinearW4:
             raise ValueError(f"PackedLinearW4 needs K % 32 == 0 (the scale block), got K={self.K}")
         self.Kp = self.K
         self.swiglu = swiglu_up is not None
-        if self.kind:
-            self.stream = bool(HEAD_POLICY["mxfp4"]) if self.K == HEAD_K else True
-        else:
-            self.stream = bool(W4_POLICY["gate_up" if self.swiglu else "down"])
+        self.stream = _kind_stream(self.kind, "mxfp4", self.K, bool(W4_POLICY["gate_up" if self.swiglu else "down"]))
         self.device = w.device
         self.ntiles = (self.N + 15) // 16 * (2 if self.swiglu else 1)
         KK = (self.K + 127) // 128
@@ -611,6 +635,106 @@ def quant_w4(w, tile_base=0, tile_stride=1):
     q = torch.zeros(nt * KK * 1024, dtype=torch.uint8, device=w.device)
     scales = torch.full((nt * KK * 64,), 127, dtype=torch.uint8, device=w.device)
     return q, scales, _quant_w4(w, q, scales, tile_base, tile_stride)
+
+
+class PackedQKVQuant:
+    """A fused q|k|v projection under weight-only FP8 or MXFP4 (attn_weights; fmt "fp8" / "mxfp4"): the [N, K] weight,
+    N = (H + 2 KVH) * hd, becomes W' = q * 2^e; the bias stays fp32 and untouched.  Holds the packed codes `q` and
+    `scales` in the rope-paired tile order (fo.quant.pack_codes_rope: one fo_quant_* call per (head, half) with
+    tile_stride 2) and `bf16` = PackedLinear(W'_dq, bias, rope_hd=hd).  qkv_rope calls of <= 16 fp32 rows stream the
+    codes (fo_gemm_w8_qkv_rope / fo_gemm_w4_qkv_rope) where ATTN_POLICY[fmt]["qkv"] says so; every other call forwards
+    to the bf16 image unchanged, xpack included.  Setting `stream = True` on an instance forces streaming (tests, A/B
+    scripts).  receive=True: storages allocated, nothing quantised (a replica whose weights arrive by broadcast)."""
+
+    def __init__(self, w, bias, hd, fmt, receive=False):
+        _check_dev(w)
+        if fmt not in ("fp8", "mxfp4"):
+            raise ValueError(f"fmt must be 'fp8' or 'mxfp4', got {fmt!r}")
+        self.fmt, self.rope_hd = fmt, hd
+        self.N, self.K = w.shape
+        if hd % 32 or self.N % hd or self.K % 32:
+            raise ValueError(f"a quantised q|k|v needs hd % 32 == 0, N % hd == 0 and K % 32 == 0 (N={self.N}, "
+                             f"K={self.K}, hd={hd})")
+        self.Kp = self.K
+        self.device = w.device
+        self.stream = bool(ATTN_POLICY[fmt]["qkv"])
+        self.ntiles = self.N // 16
+        w8 = fmt == "fp8"
+        KK = (self.K + 63) // 64 if w8 else (self.K + 127) // 128
+        self.q = torch.empty(self.ntiles * KK * 1024, dtype=torch.uint8, device=w.device)
+        self.scales = (torch.empty(self.ntiles * 16, dtype=F32, device=w.device) if w8 else
+                       torch.empty(self.ntiles * KK * 64, dtype=torch.uint8, device=w.device))
+        if receive:
+            self.bf16 = PackedLinear(w, bias, rope_hd=hd)
+            return
+        if w.dtype not in (BF16, F32):
+            w = w.float()
+        w = w.contiguous()
+        dq = torch.empty(self.N, self.K, dtype=BF16, device=w.device)
+        half, es, s = hd // 2, w.element_size(), stream(w.device)
+        for h in range(self.N // hd):
+            for p in (0, 1):
+                r0 = h * hd + p * half
+                _lib.call("fo_quant_w8" if w8 else "fo_quant_w4", w.data_ptr() + r0 * self.K * es,
+                          1 if w.dtype == BF16 else 0, half, self.K, self.K, self.q.data_ptr(), self.scales.data_ptr(),
+                          dq.data_ptr() + r0 * self.K * 2, h * (hd // 16) + p, 2, s)
+        self.bf16 = PackedLinear(dq, bias, rope_hd=hd)
+
+    @property
+    def bias(self):
+        return self.bf16.bias
+
+    @property
+    def packed(self):
+        return self.bf16.packed
+
+    @property
+    def nbytes(self):
+        """The bf16 image (what `weight_bytes` has always counted); the codes are fp8_nbytes / fp4_nbytes."""
+        return self.bf16.nbytes
+
+    @property
+    def fp8_nbytes(self):
+        return self.q.numel() + self.scales.numel() * 4 if self.fmt == "fp8" else 0
+
+    @property
+    def fp4_nbytes(self):
+        return self.q.numel() + self.scales.numel() if self.fmt == "mxfp4" else 0
+
+    def streams(self, rows):
+        """Whether a qkv_rope call of `rows` fp32 rows streams the codes (else it runs the bf16 image)."""
+        return rows <= 16 and self.stream
+
+    def qkv_rope(self, x, M, pos, slot, cos_t, sin_t, q_out, kc, vc, H, KVH, PS, norm=None, splitk=0, xpack=None):
+        if not self.streams(M) or x.dtype != F32:
+            return self.bf16.qkv_rope(x, M, pos, slot, cos_t, sin_t, q_out, kc, vc, H, KVH, PS, norm=norm,
+                                      splitk=splitk, xpack=xpack)
+        _check_dev(x)
+        if x.stride(-1) != 1 or x.shape[-1] < self.K:
+            raise ValueError(f"qkv_rope input needs unit stride and >= {self.K} columns, got {tuple(x.shape)}")
+        rst, rg, eps = _norm_args(norm)[:3]
+        # (x is read as fp32 rows: xpack stays untouched)
+        _lib.call("fo_gemm_w8_qkv_rope" if self.fmt == "fp8" else "fo_gemm_w4_qkv_rope", x.data_ptr(), x.stride(0), M,
+                  self.K, self.q.data_ptr(), self.scales.data_ptr(), self.ntiles, self.N, ptr(self.bias), rst, rg, eps,
+                  pos.data_ptr(), slot.data_ptr(), cos_t.data_ptr(), sin_t.data_ptr(), q_out.data_ptr(), kc.data_ptr(),
+                  vc.data_ptr(), H, KVH, self.rope_hd, PS, kv_bytes(kc, vc), stream(x.device))
+        return q_out
+
+
+QKV_QUANT_LAUNCH_KINDS = ("w8_qkv_rope", "w4_qkv_rope")
+
+
+def qkv_quant_launch_counts():
+    """{entry: fo_gemm_w8_qkv_rope / fo_gemm_w4_qkv_rope launches issued since the last reset} (host-side counters of
+    their own; a captured graph counts at capture, a refused call not at all)."""
+    import ctypes
+    buf = (ctypes.c_longlong * 2)()
+    _lib.load().fo_gemm_qkv_quant_counts(buf, 2)
+    return {k: int(buf[i]) for i, k in enumerate(QKV_QUANT_LAUNCH_KINDS)}
+
+
+def qkv_quant_launch_counts_reset():
+    _lib.call("fo_gemm_qkv_quant_counts_reset")
 
 
 W4_LAUNCH_KINDS = ("w4", "w4_xs", "w4_sk")

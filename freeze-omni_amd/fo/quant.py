@@ -129,3 +129,42 @@ def pack_scales_w4(e, tile_base=0, tile_stride=1, out=None):
         out = torch.full(((tile_base + (nt - 1) * tile_stride + 1) * KK * 64,), 127, dtype=torch.uint8)
     out.view(-1, KK * 64)[tile_base::tile_stride][:nt] = s
     return out
+
+
+# ---------------------------------------------------------------- the fused q|k|v weight (attn_weights; hd % 32 == 0)
+# The rope-paired tile order of PackedLinear(rope_hd=hd) and of fo_gemm_w8_qkv_rope / fo_gemm_w4_qkv_rope: for head h
+# and half p in {0, 1}, the hd/2 rows from h * hd + p * hd/2 go to packed tiles h * (hd/16) + p, + 2, ..., so adjacent
+# packed tiles (2P, 2P + 1) hold columns (i, i + hd/2) of one head.  One pack_* call per (head, half).
+def _rope_pack(pack, x, hd, out):
+    N = x.shape[0]
+    if hd % 32 or N % hd:
+        raise ValueError(f"rope packing needs hd % 32 == 0 and N % hd == 0 (N={N}, hd={hd})")
+    half = hd // 2
+    for h in range(N // hd):
+        for p in (0, 1):
+            r0 = h * hd + p * half
+            out = pack(x[r0:r0 + half], tile_base=h * (hd // 16) + p, tile_stride=2, out=out)
+    return out
+
+
+def pack_codes_rope(q, hd):
+    """q uint8 [N, K] e4m3fn codes of a fused q|k|v weight -> fo_quant_w8's packed codes in the rope-paired order."""
+    N, K = q.shape
+    return _rope_pack(pack_codes, q, hd, torch.zeros(N // 16 * ((K + 63) // 64) * 1024, dtype=torch.uint8))
+
+
+def pack_scales_rope(e, hd):
+    """e int32 [N] -> fp32 2^e at [tile][16] in the rope-paired order."""
+    return _rope_pack(pack_scales, e, hd, torch.ones(e.shape[0], dtype=torch.float32))
+
+
+def pack_codes_rope_w4(q, hd):
+    """q uint8 [N, K] e2m1 codes of a fused q|k|v weight -> fo_quant_w4's packed codes in the rope-paired order."""
+    N, K = q.shape
+    return _rope_pack(pack_codes_w4, q, hd, torch.zeros(N // 16 * ((K + 127) // 128) * 1024, dtype=torch.uint8))
+
+
+def pack_scales_rope_w4(e, hd):
+    """e int32 [N, K // 32] -> E8M0 bytes at [tile][ceil(K/128)][16 rows][4] in the rope-paired order."""
+    N, KB = e.shape
+    return _rope_pack(pack_scales_w4, e, hd, torch.full((N // 16 * ((KB + 3) // 4) * 64,), 127, dtype=torch.uint8))

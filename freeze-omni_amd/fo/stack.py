@@ -14,7 +14,7 @@ import torch
 
 from . import ops
 from .kv import BatchMeta
-from .ops import F32, PackedLinear, PackedLinearW4, PackedLinearW8
+from .ops import F32, PackedLinear, PackedLinearW4, PackedLinearW8, PackedQKVQuant
 from .weights import ReceiveSource
 
 # FO_ATTN_DENSE=0 passes the item table even for one-token-per-sequence batches (A/B against a
@@ -33,8 +33,13 @@ class Layer:
 
 class DecoderStack:
     def __init__(self, src, prefix, n_layers, D, H, KVH, eps, bias, rope, pool, kv_layer0=0, first_fp16=False,
-                 attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT, mlp_w8=False, mlp_w8_rows=16, mlp_w4=False, mlp_w4_rows=16):
-        """mlp_w8: gate/up and down under weight-only FP8 (ops.PackedLinearW8: the model's MLP weights become
+                 attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT, mlp_w8=False, mlp_w8_rows=16, mlp_w4=False, mlp_w4_rows=16,
+                 attn_w=None):
+        """attn_w: None, "fp8" or "mxfp4": the q|k|v and o projections under weight-only FP8 / MXFP4
+        (ops.PackedQKVQuant, and ops.PackedLinearW8 / W4 with kind="attn_o": the four projection weights become
+        q * 2^e, the biases stay; forwards of <= 16 rows stream the codes where ops.ATTN_POLICY says so, everything else
+        runs the exact bf16 image).  Independent of the MLP options.
+        mlp_w8: gate/up and down under weight-only FP8 (ops.PackedLinearW8: the model's MLP weights become
         q * 2^e; forwards of <= 16 rows stream the codes, larger ones the exact bf16 image of the same weights).
         mlp_w8_rows: 16, 64 or 128, PackedLinearW8's stream_rows (64: 17..64-row forwards stream the codes too; 128:
         65..128-row ones as well).
@@ -45,6 +50,9 @@ class DecoderStack:
         pairs of ops.W4_ROWS_POLICY)."""
         if mlp_w8 and mlp_w4:
             raise ValueError("mlp_w8 and mlp_w4 are two models of the same weights: pick one")
+        if attn_w not in (None, "fp8", "mxfp4"):
+            raise ValueError(f"attn_w must be None, 'fp8' or 'mxfp4', got {attn_w!r}")
+        self.attn_w = attn_w
         self.mlp_w4 = bool(mlp_w4)
         self.mlp_w8 = bool(mlp_w8)
         self.mlp_w8_rows = mlp_w8_rows
@@ -66,9 +74,18 @@ class DecoderStack:
             if bias:
                 b = torch.cat([src.get(q + "self_attn.q_proj.bias"), src.get(q + "self_attn.k_proj.bias"),
                                src.get(q + "self_attn.v_proj.bias")])
-            L.qkv = PackedLinear(torch.cat([wq, wk, wv]), b, rope_hd=self.hd)
+            recv = isinstance(src, ReceiveSource)   # storages only: the broadcast fills codes, scales and image
+            if attn_w is None:
+                L.qkv = PackedLinear(torch.cat([wq, wk, wv]), b, rope_hd=self.hd)
+            else:
+                L.qkv = PackedQKVQuant(torch.cat([wq, wk, wv]), b, self.hd, attn_w, receive=recv)
             del wq, wk, wv
-            L.o = PackedLinear(src.get(q + "self_attn.o_proj.weight", torch.bfloat16))
+            wo = src.get(q + "self_attn.o_proj.weight", torch.bfloat16)
+            if attn_w is None:
+                L.o = PackedLinear(wo)
+            else:
+                L.o = (PackedLinearW8 if attn_w == "fp8" else PackedLinearW4)(wo, receive=recv, kind="attn_o")
+            del wo
             if self.mlp_w8:
                 recv = isinstance(src, ReceiveSource)   # storages only: the broadcast fills codes, scales and image
                 L.gu = PackedLinearW8(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
@@ -111,6 +128,16 @@ class DecoderStack:
     def mlp_fp4_bytes(self):
         """The MXFP4 codes and scale bytes held beside the bf16 image (0 without mlp_w4)."""
         return sum(getattr(L.gu, "fp4_nbytes", 0) + getattr(L.down, "fp4_nbytes", 0) for L in self.layers)
+
+    @property
+    def attn_fp8_bytes(self):
+        """The FP8 codes and scales of q|k|v and o, held beside the bf16 image (0 without attn_w="fp8")."""
+        return sum(getattr(L.qkv, "fp8_nbytes", 0) + getattr(L.o, "fp8_nbytes", 0) for L in self.layers)
+
+    @property
+    def attn_fp4_bytes(self):
+        """The MXFP4 codes and scale bytes of q|k|v and o, held beside the bf16 image (0 without attn_w="mxfp4")."""
+        return sum(getattr(L.qkv, "fp4_nbytes", 0) + getattr(L.o, "fp4_nbytes", 0) for L in self.layers)
 
     def workspace(self, T, nsplit, device):
         """Preallocated per-forward buffers for T tokens (graph capture must not allocate)."""
@@ -180,6 +207,14 @@ class DecoderStack:
                 xgp_qkv = None
         # (a captured graph's meta carries its capacity, not the replay's keys: graphs keep 128-key splits, which fill
         # the chip at the listen / text shapes, r03c; eager launches -- duplex ticks, prefills -- size them per launch)
+        # attn_w likewise at <= 16 rows, per GEMM that streams the codes: a streaming q|k|v reads the fp32 x*gamma, so the
+        # previous down writes none packed; a streaming o reads the fp32 attention output, so the attention writes none
+        # packed, and writes no packed x*gamma itself, so a bf16 gate/up reads the fp32 rows
+        if self.attn_w and self.layers:
+            if self.layers[0].qkv.streams(T):
+                xgp_qkv = None
+            if self.layers[0].o.streams(T):
+                attp = xgp_gu = None
         eager = x.is_cuda and not torch.cuda.is_current_stream_capturing()
         kps = self.attn_kps or (ops.attn_keys_per_split(meta.max_keys, meta.n_items, KVH, hd, x.device) if eager else 128)
         for i, L in enumerate(self.layers):

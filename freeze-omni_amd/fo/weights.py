@@ -130,16 +130,23 @@ class FakeQuantSource:
     32-column block (fo.quant.quantize_blocks_e2m1).
     lm_head: None (default), "fp8" or "mxfp4": `lm_head.weight` is replaced by its image in that format too, the
     model of an engine with lm_head_weights (model.embed_tokens.weight is never touched).
-    fmt=None (with lm_head): the MLP weights pass through unchanged -- a quantised head over a bf16 MLP."""
+    attn: None (default), "fp8" or "mxfp4": self_attn.{q,k,v,o}_proj.weight of every model.layers.N are replaced by
+    their image in that format, the model of an engine with attn_weights (the biases are never touched).  The scales
+    are per row or per (row, block), so quantising q, k and v one by one equals quantising their concatenation.
+    fmt=None (with lm_head or attn): the MLP weights pass through unchanged."""
 
     MLP = ("mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
+    ATTN = ("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight",
+            "self_attn.o_proj.weight")
 
-    def __init__(self, inner, fmt="fp8", lm_head=None):
-        if fmt not in ("fp8", "mxfp4") and not (fmt is None and lm_head is not None):
+    def __init__(self, inner, fmt="fp8", lm_head=None, attn=None):
+        if fmt not in ("fp8", "mxfp4") and not (fmt is None and (lm_head is not None or attn is not None)):
             raise ValueError(f"FakeQuantSource format must be 'fp8' or 'mxfp4', got {fmt!r}")
         if lm_head not in (None, "fp8", "mxfp4"):
             raise ValueError(f"FakeQuantSource lm_head must be None, 'fp8' or 'mxfp4', got {lm_head!r}")
-        self.inner, self.fmt, self.lm_head = inner, fmt, lm_head
+        if attn not in (None, "fp8", "mxfp4"):
+            raise ValueError(f"FakeQuantSource attn must be None, 'fp8' or 'mxfp4', got {attn!r}")
+        self.inner, self.fmt, self.lm_head, self.attn = inner, fmt, lm_head, attn
 
     def __contains__(self, name):
         return name in self.inner
@@ -149,6 +156,8 @@ class FakeQuantSource:
             fmt = self.lm_head
         elif name.startswith("model.layers.") and name.endswith(self.MLP):
             fmt = self.fmt
+        elif name.startswith("model.layers.") and name.endswith(self.ATTN):
+            fmt = self.attn
         else:
             fmt = None
         if fmt is None:

@@ -33,7 +33,9 @@ class inferencePipeline:
         args["llm_mlp_mxfp4_rows"]: 16 (default) or 64, its mlp_mxfp4_rows;
         args["llm_kv"]: "fp32" (default) or "bf16", its llm_kv (the Qwen2 paged KV's element);
         args["llm_lm_head_weights"]: "bf16" (default), "fp8" or "mxfp4", its lm_head_weights (the Qwen2 output head; as
-        with llm_mlp_weights, every replica of a pool takes the same value)."""
+        with llm_mlp_weights, every replica of a pool takes the same value);
+        args["llm_attn_weights"]: "bf16" (default), "fp8" or "mxfp4", its attn_weights (the Qwen2 q, k, v and o
+        projections; every replica of a pool takes the same value)."""
         if isinstance(args, argparse.Namespace):
             args = vars(args)
         self.args = args
@@ -50,7 +52,8 @@ class inferencePipeline:
                                              mlp_fp8_rows=args.get("llm_mlp_fp8_rows") or 16,
                                              mlp_mxfp4_rows=args.get("llm_mlp_mxfp4_rows") or 16,
                                              llm_kv=args.get("llm_kv") or "fp32",
-                                             lm_head_weights=args.get("llm_lm_head_weights") or "bf16")
+                                             lm_head_weights=args.get("llm_lm_head_weights") or "bf16",
+                                             attn_weights=args.get("llm_attn_weights") or "bf16")
         if weights_from is not None:
             from fo.replica import copy_frozen
             copy_frozen(weights_from.model.engine, self.model.engine)

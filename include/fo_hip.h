@@ -202,7 +202,9 @@ int fo_launch_counts_reset(void);
  *   swiglu (Y = silu(s_g g) * (s_u u)), the RMSNorm consumer (rstats / rgroups / eps) and producer (sout, gnext, yg;
  *   *sgroups = ceil(N/16) groups per row).  The column scale multiplies the fp32 sum before anything else; rows >= M
  *   are neither stored nor summed.  No bias, affine, activation, bf16 output, RoPE, LayerNorm-on-load or packed X / Y:
- *   those, and more rows than the caller's band, run the bf16 image through fo_gemm.  ws / ws_floats / counters are
+ *   those, and more rows than the caller's band, run the bf16 image through fo_gemm (the fused q|k|v epilogue -- bias,
+ *   RoPE, paged-KV append -- has entries of its own at <= 16 rows: fo_gemm_w8_qkv_rope below).  ws / ws_floats /
+ *   counters are
  *   fo_gemm's (scratch floats, and zeroed ints that are left zeroed).  Where K is split over workgroups the partial
  *   sums are added in split order: deterministic in every form.  Every launch is capture-safe.
  *   - fo_gemm_w8, M <= 16: one workgroup per output tile, its waves splitting K (k_w8); the SwiGLU pair at K = 3584
@@ -305,6 +307,37 @@ int fo_gemm_w4_head(const float* X, int ldx, int M, int K, const void* q, const 
                     float* Y, int ldy, hipStream_t stream);
 int fo_gemm_head_counts(long long* out, int n);
 int fo_gemm_head_counts_reset(void);
+/* The fused q|k|v projection of a Qwen2 layer under the same two formats, for calls of <= 16 rows:
+ * fo_gemm_qkv_rope_kv's arguments with codes and scales in place of Wp, and no workspace, tickets or split.
+ * Layout: q and scale are fo_quant_w8's / fo_quant_w4's packed codes and scales of the [N][K] fused weight,
+ * N = (H + 2 KVH) * hd, in the tile order of the bf16 rope packing: for head h and half p in {0, 1} the hd/2 rows from
+ * h * hd + p * hd/2 go to packed tiles h * (hd/16) + p, + 2, ... (one fo_quant_* call per (head, half) with tile_base
+ * h * (hd/16) + p and tile_stride 2), so adjacent packed tiles (2P, 2P + 1) hold columns (i, i + hd/2) of one head;
+ * ntiles = N / 16 is their extent.  X is fp32 [M][ldx] (split into bf16 hi + lo).
+ * Kernel: the pair form of the general kernels (k_w8 / k_w4): workgroup P owns tile pair P (N / 32 workgroups), the
+ * waves split the code steps and the cross-wave sum runs in wave order.  Thread (rr, c) holds x1 / x2 of logical
+ * columns n / n + hd/2 and applies, in this order: the FP8 column scales (MXFP4: none; the block scales are applied in
+ * the decode); the consumer's rstd = rsqrt(sum(rstats[rr][0 .. rgroups)) / K + eps), where rstats is given; the bias,
+ * where given; rotate_half RoPE with cos_t / sin_t ([pos][hd/2]) at pos[rr], for q and k heads; the store: q to
+ * q_out[rr][h * hd + i] (fp32), K and V to the paged cache ([page][KVH][PS][hd]) at slot[rr], as fp32 (kv_bytes 4;
+ * rounded to a bf16 value under fo_set_kv_bf16) or as bf16 elements rounded once to nearest even (kv_bytes 2).
+ * Rows >= M are computed from a clamped row and never stored.  Deterministic, capture-safe.
+ * Refused on the host before any HIP call, with the entry's name: M outside 1..16, K % 32 != 0, hd % 32 != 0,
+ * N != (H + 2 KVH) * hd, ntiles != N / 16, kv_bytes not 2 or 4, PS <= 0, a NULL X, q, scale, pos, slot, cos_t, sin_t,
+ * q_out, kc or vc, ldx < K or ldx % 4 != 0 or X not 16-byte aligned, rstats without rgroups, codes of 2 GiB or more.
+ * bias may be NULL.  More rows run the bf16 image through fo_gemm_qkv_rope_kv.
+ * fo_gemm_qkv_quant_counts: the launches issued by (fo_gemm_w8_qkv_rope, fo_gemm_w4_qkv_rope) since the last reset
+ *   into out[0 .. min(n, 2)); returns 2.  A refused call is not counted.  These kernels have no FoLaunchKind. */
+int fo_gemm_w8_qkv_rope(const float* X, int ldx, int M, int K, const void* q, const float* scale, int ntiles, int N,
+                        const float* bias, const float* rstats, int rgroups, float eps, const int* pos, const int* slot,
+                        const float* cos_t, const float* sin_t, float* q_out, void* kc, void* vc, int H, int KVH, int hd,
+                        int PS, int kv_bytes, hipStream_t stream);
+int fo_gemm_w4_qkv_rope(const float* X, int ldx, int M, int K, const void* q, const void* scale, int ntiles, int N,
+                        const float* bias, const float* rstats, int rgroups, float eps, const int* pos, const int* slot,
+                        const float* cos_t, const float* sin_t, float* q_out, void* kc, void* vc, int H, int KVH, int hd,
+                        int PS, int kv_bytes, hipStream_t stream);
+int fo_gemm_qkv_quant_counts(long long* out, int n);
+int fo_gemm_qkv_quant_counts_reset(void);
 /* Software-pipelined one-row-tile fp32-X weight-stream GEMMs (M <= 16, >= 64 MiB of weights: the next
  * k-group's weights + X in flight during this group's MFMAs).  3 (default): the measured policy; 0: plain
  * loops; 1 / 2: every such GEMM pipelined with 4 / 2 k-steps per group (sweeps).  Unset, the

@@ -4,9 +4,11 @@ reference's fbank features, tests/golden/fbank.npz) with the user chat prefix, t
 steps.  Prints the state-probability differences per chunk, the decision-row logit differences under teacher forcing
 with the bf16 engine's ids (and how often the arg-max agrees, against the bf16 top-2 margin), and where the two
 engines' own greedy texts part.  A measurement, not a test.
-python scripts/mlp_fp8_accuracy.py [steps] [fp8|mxfp4|bf16] [heads] (GPU only).  The optional third argument is a
+python scripts/mlp_fp8_accuracy.py [steps] [fp8|mxfp4|bf16] [heads] [attns] (GPU only).  The optional third argument is a
 comma-separated list of lm_head_weights formats (`fp8,mxfp4`): each is measured against the bf16 engine in the same
-process, over the MLP mode of the second argument (`bf16`: the head alone is quantised)."""
+process, over the MLP mode of the second argument (`bf16`: the head alone is quantised).  The optional fourth is a
+comma-separated list of attn_weights formats, each measured under every head of the third (`bf16 bf16 fp8,mxfp4`: the
+attention projections alone are quantised)."""
 import os
 import sys
 
@@ -20,6 +22,7 @@ from fo.engine import FreezeOmniEngine  # noqa: E402
 STEPS = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 FMT = sys.argv[2] if len(sys.argv) > 2 else "fp8"
 HEADS = sys.argv[3].split(",") if len(sys.argv) > 3 else ["bf16"]
+ATTNS = sys.argv[4].split(",") if len(sys.argv) > 4 else ["bf16"]
 SYS_IDS = list(range(1, 16))
 USER_PREFIX = [151645, 198, 151644, 872, 198]
 ASSIST_PREFIX = [151645, 198, 151644, 77091, 198]
@@ -56,18 +59,19 @@ def flow(eng, forced=None):
     return np.stack(probs), np.stack(logits), toks
 
 
-def engine(mode, head="bf16"):
+def engine(mode, head="bf16", attn="bf16"):
     return FreezeOmniEngine(os.path.join(ROOT, "configs", "real"), device=dev, max_sessions=2, mlp_weights=mode,
-                            lm_head_weights=head)
+                            lm_head_weights=head, attn_weights=attn)
 
 
 eng = engine("bf16")
 p0, l0, t0 = flow(eng)
 del eng
 torch.cuda.empty_cache()
-for head in HEADS:
-    eng = engine(FMT, head)
-    print(f"mlp_weights={FMT}{'' if head == 'bf16' else f' lm_head_weights={head}'} against bf16:")
+for head, attn in ((h, a) for h in HEADS for a in ATTNS):
+    eng = engine(FMT, head, attn)
+    print(f"mlp_weights={FMT}{'' if head == 'bf16' else f' lm_head_weights={head}'}"
+          f"{'' if attn == 'bf16' else f' attn_weights={attn}'} against bf16:")
     p1, l1, t1f = flow(eng, forced=t0)
     _, _, t1 = flow(eng)
     del eng
