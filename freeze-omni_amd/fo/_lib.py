@@ -107,6 +107,14 @@ _SIGS = {
     "fo_gemm_w4_head": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_int, c_vp]),
     "fo_gemm_head_counts": (c_int, [ctypes.POINTER(c_ll), c_int]),
     "fo_gemm_head_counts_reset": (c_int, []),
+    "fo_quant_w6_bytes": (c_ll, [c_int, c_int]),
+    "fo_quant_w6_scale_bytes": (c_ll, [c_int, c_int]),
+    "fo_quant_w6": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
+    "fo_gemm_w6": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_ll,
+                           c_vp, c_vp, c_int, c_float, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), c_vp]),
+    "fo_gemm_w6_head": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_int, c_vp]),
+    "fo_gemm_w6_counts": (c_int, [ctypes.POINTER(c_ll), c_int]),
+    "fo_gemm_w6_counts_reset": (c_int, []),
     "fo_gemm_w8_qkv_rope": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_float,
                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "fo_gemm_w4_qkv_rope": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_float,

@@ -76,8 +76,8 @@ class FreezeOmniEngine:
         and llm_kv; the biases and the AR speech decoder's stack are untouched.  Steps of <= 16 rows stream the codes
         where ops.ATTN_POLICY says so; everything else runs the exact bf16 image.  `src` serves the dequantised
         projections (FakeQuantSource(..., attn=...)).
-        lm_head_weights: "bf16" (default), "fp8" or "mxfp4": the Qwen2 output head (lm_head.weight only, never the
-        embedding) under weight-only FP8 per vocabulary row or MXFP4, independent of mlp_weights,
+        lm_head_weights: "bf16" (default), "fp8", "mxfp4" or "mxfp6": the Qwen2 output head (lm_head.weight only, never
+        the embedding) under weight-only FP8 per vocabulary row, MXFP4 or MXFP6, independent of mlp_weights,
         mlp_*_rows and llm_kv.  Calls of <= 16 rows (the captured TextGraph, the eager text_step, LLMEngine.logits)
         stream the codes where ops.HEAD_POLICY says so; more rows run the exact bf16 image.  `src` serves the
         dequantised head (FakeQuantSource(..., lm_head=...)).
@@ -90,7 +90,10 @@ class FreezeOmniEngine:
         `src` serves the dequantised weights (fo.weights.FakeQuantSource), so an oracle or a second engine can be
         built on the same model.  "mxfp4": the same weights under weight-only MXFP4 instead (e2m1 codes times a power
         of two per block of 32 columns): Qwen2 steps of <= 16 rows stream the codes for the GEMMs of
-        ops.W4_POLICY, every other launch runs the exact bf16 image; mlp_fp8_rows stays 16.
+        ops.W4_POLICY, every other launch runs the exact bf16 image; mlp_fp8_rows stays 16.  "mxfp6": the same weights
+        under weight-only MXFP6 (e2m3 codes under the same block scales, DESIGN §5.10: FP8's accuracy at 0.78 of its
+        bytes): Qwen2 steps of <= 16 rows stream the codes for the GEMMs of ops.W6_POLICY, every other launch runs the
+        exact bf16 image; mlp_fp8_rows and mlp_mxfp4_rows stay 16.
         mlp_fp8_rows: 16 (default), 64 or 128, with mlp_weights="fp8" only: 64 lets Qwen2 steps of 17..64 rows (duplex
         ticks, prefixed first chunks, one-chunk listens of more than 8 sessions) stream the codes too, 128 steps of
         65..128 rows as well (the grouped offline listen, duplex ticks whose sessions start a turn), for the GEMMs
@@ -105,8 +108,8 @@ class FreezeOmniEngine:
         (models/utils.py:31-38)."""
         if not torch.cuda.is_available():
             raise RuntimeError("FreezeOmniEngine needs an MI355X (gfx950) device: there is no CPU fallback")
-        if mlp_weights not in ("bf16", "fp8", "mxfp4"):
-            raise ValueError(f"mlp_weights must be 'bf16', 'fp8' or 'mxfp4', got {mlp_weights!r}")
+        if mlp_weights not in ("bf16", "fp8", "mxfp4", "mxfp6"):
+            raise ValueError(f"mlp_weights must be 'bf16', 'fp8', 'mxfp4' or 'mxfp6', got {mlp_weights!r}")
         if mlp_fp8_rows not in (16, 64, 128):
             raise ValueError(f"mlp_fp8_rows must be 16, 64 or 128, got {mlp_fp8_rows!r}")
         if mlp_fp8_rows != 16 and mlp_weights != "fp8":
@@ -117,8 +120,8 @@ class FreezeOmniEngine:
             raise ValueError(f"mlp_mxfp4_rows={mlp_mxfp4_rows} needs mlp_weights='mxfp4'")
         if llm_kv not in ("fp32", "bf16"):
             raise ValueError(f"llm_kv must be 'fp32' or 'bf16', got {llm_kv!r}")
-        if lm_head_weights not in ("bf16", "fp8", "mxfp4"):
-            raise ValueError(f"lm_head_weights must be 'bf16', 'fp8' or 'mxfp4', got {lm_head_weights!r}")
+        if lm_head_weights not in ("bf16", "fp8", "mxfp4", "mxfp6"):
+            raise ValueError(f"lm_head_weights must be 'bf16', 'fp8', 'mxfp4' or 'mxfp6', got {lm_head_weights!r}")
         if attn_weights not in ("bf16", "fp8", "mxfp4"):
             raise ValueError(f"attn_weights must be 'bf16', 'fp8' or 'mxfp4', got {attn_weights!r}")
         self.attn_weights = attn_weights
@@ -152,7 +155,8 @@ class FreezeOmniEngine:
                              kv_tokens=llm_kv_tokens or min(max_sessions * 4096, 1 << 17),
                              mlp_w8=mlp_weights == "fp8", mlp_w8_rows=mlp_fp8_rows, kv_dtype=llm_kv,
                              mlp_w4=mlp_weights == "mxfp4", mlp_w4_rows=mlp_mxfp4_rows,
-                             lm_head_weights=lm_head_weights, attn_weights=attn_weights)
+                             lm_head_weights=lm_head_weights, attn_weights=attn_weights,
+                             mlp_w6=mlp_weights == "mxfp6")
         self.tts = TTSEngine(src, self.cfg["decoder_json"], self.device,
                              kv_tokens=tts_kv_tokens or min(max_sessions * 2048, 1 << 17))
         self.codec = CodecEngine(src, self.cfg["codec_json"], self.device)
@@ -212,7 +216,7 @@ class FreezeOmniEngine:
                                  mlp_w8=self.mlp_weights == "fp8", mlp_w8_rows=self.mlp_fp8_rows,
                                  kv_dtype=self.llm_kv, mlp_w4=self.mlp_weights == "mxfp4",
                                  mlp_w4_rows=self.mlp_mxfp4_rows, lm_head_weights=self.lm_head_weights,
-                                 attn_weights=self.attn_weights)
+                                 attn_weights=self.attn_weights, mlp_w6=self.mlp_weights == "mxfp6")
         elif "predictor_head.weight" in src:
             self.llm.head_w, self.llm.head_b = src.get("predictor_head.weight"), src.get("predictor_head.bias")
         self.src = self._model_source(src) if fq else src

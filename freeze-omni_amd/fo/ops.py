@@ -331,6 +331,7 @@ class PackedLinear:
 # 172.2 / 88.8 / 55.4 at 8 rows (bf16 spread 2.3) and 188.1 / 95.2 / 59.0 at 16 (spread 1.1): both formats entered.
 # A head of any other K (the tiny config's 128) streams through the general plain form of fo_gemm_w8 / fo_gemm_w4.
 # The one place the policy lives.
+# (The MXFP6 head's entry is W6_POLICY["head"], below: this table keeps the two formats of DESIGN 5.8.)
 HEAD_POLICY = {"fp8": True, "mxfp4": True}
 HEAD_K = 3584   # the K the X-stationary plain forms are compiled for
 
@@ -360,7 +361,7 @@ def _head_kind(kind, swiglu_up, stream_rows):
 def _kind_stream(kind, fmt, K, default):
     """Whether a <= 16-row call of a PackedLinearW8 / W4 of this kind streams the codes."""
     if kind == "head":
-        return bool(HEAD_POLICY[fmt]) if K == HEAD_K else True
+        return bool(W6_POLICY["head"] if fmt == "mxfp6" else HEAD_POLICY[fmt]) if K == HEAD_K else True
     if kind == "attn_o":
         return bool(ATTN_POLICY[fmt]["o"])
     return default
@@ -637,6 +638,137 @@ def quant_w4(w, tile_base=0, tile_stride=1):
     return q, scales, _quant_w4(w, q, scales, tile_base, tile_stride)
 
 
+# Which <= 16-row GEMMs of a PackedLinearW6 stream the MXFP6 codes: W4_POLICY's rule against the bf16 image of the same
+# W' (scripts/gemm_w6_ab.py, profiles/mlp_mxfp6_gemm_ab.txt).  "head": HEAD_POLICY's entry for this format
+# (fo_gemm_w6_head at K = HEAD_K), by the same rule.  Builder-run, all arms in one process (medians, us, bf16 image / fp8 /
+# mxfp6 / mxfp4; the bf16 spread in brackets):
+#   gate/up: 45.1 / 27.7 / 27.1 / 20.7 at 8 rows (1.4), 47.3 / 29.7 / 28.9 / 22.8 at 16 (0.1): entered;
+#   down:    27.8 / 22.0 / 22.3 / 19.3 at 8 rows (0.1), 28.5 / 26.1 / 24.0 / 20.8 at 16 (0.1): entered;
+#   head:    175.6 / 87.0 / 70.7 / 53.4 at 8 rows (0.7), 193.3 / 90.7 / 77.7 / 58.7 at 16 (0.5): entered.
+# Against the FP8 stream MXFP6's 22 % fewer bytes show on the head (0.81-0.86x) and barely on the MLP (0.92-1.02x).
+# The one place the policy lives.
+W6_POLICY = {"gate_up": True, "down": True, "head": True}
+
+
+class PackedLinearW6:
+    """A bias-free linear layer under weight-only MXFP6 (fo.quant, include/fo_hip.h fo_quant_w6): the weight is
+    W'[n, k] = q[n, k] * 2^e[n, k // 32] with q an e2m3 code.  Holds the packed codes `q`, the E8M0 block `scales` and
+    `bf16`, a PackedLinear over the dequantised weight (W' is exactly a bf16 matrix).  Calls of <= 16 fp32 rows stream
+    the codes (fo_gemm_w6) where W6_POLICY lists this GEMM; every other call forwards to the bf16 image, so both
+    compute X . W'^T.
+
+    w: [N, K] device weight (bf16 or fp32, K % 32 == 0), quantised on the device; swiglu_up as PackedLinear.
+    receive=True: storages allocated, nothing quantised (a replica whose weights arrive by broadcast).
+    stream_rows is 16: this format has no row streams.  Setting `stream = True` on an instance sends every <= 16-row
+    call to the codes (tests, A/B scripts).
+    kind="head": the Qwen2 output head (see _head_kind): plain, `stream` from W6_POLICY["head"] at K = HEAD_K
+    (fo_gemm_w6_head), the general plain form at any other K."""
+
+    bias = None
+    stream_rows = 16
+    rows_rb = ()
+
+    def __init__(self, w, swiglu_up=None, receive=False, kind=None):
+        _check_dev(w)
+        if kind not in (None, "head"):
+            raise ValueError(f"kind must be None or 'head', got {kind!r}")
+        self.kind = _head_kind(kind, swiglu_up, 16)
+        self.N, self.K = w.shape
+        if self.K % 32:
+            raise ValueError(f"PackedLinearW6 needs K % 32 == 0 (the scale block), got K={self.K}")
+        self.Kp = self.K
+        self.swiglu = swiglu_up is not None
+        self.stream = _kind_stream(self.kind, "mxfp6", self.K, bool(W6_POLICY["gate_up" if self.swiglu else "down"]))
+        self.device = w.device
+        self.ntiles = (self.N + 15) // 16 * (2 if self.swiglu else 1)
+        KK = (self.K + 127) // 128
+        self.q = torch.empty(self.ntiles * KK * 1536, dtype=torch.uint8, device=w.device)
+        self.scales = torch.empty(self.ntiles * KK * 64, dtype=torch.uint8, device=w.device)
+        if receive:
+            self.bf16 = PackedLinear(w, swiglu_up=swiglu_up)
+            return
+        dq = [_quant_w6(w, self.q, self.scales, 0, 2 if self.swiglu else 1)]
+        if self.swiglu:
+            dq.append(_quant_w6(swiglu_up, self.q, self.scales, 1, 2))
+        self.bf16 = PackedLinear(dq[0], swiglu_up=dq[1] if self.swiglu else None)
+
+    @property
+    def packed(self):
+        return self.bf16.packed
+
+    @property
+    def nbytes(self):
+        """The bf16 image (what `weight_bytes` has always counted); the codes and scales are fp6_nbytes."""
+        return self.bf16.nbytes
+
+    @property
+    def fp6_nbytes(self):
+        return self.q.numel() + self.scales.numel()
+
+    def streams(self, rows):
+        """Whether a call of `rows` fp32 rows streams the codes (else it runs the bf16 image)."""
+        return rows <= 16 and self.stream
+
+    def __call__(self, x, out=None, act="none", residual=False, out_dtype=F32, splitk=0, M=None, norm=None,
+                 stats_out=None, xpack=None, ypack=None):
+        rows = x.shape[0] if M is None else M
+        head = self.kind == "head" and self.K == HEAD_K   # (the head entry is plain: anything else runs the image)
+        if (not self.streams(rows) or x.dtype != F32 or act != "none" or out_dtype != F32 or
+                (out is not None and out.dtype != F32) or
+                (head and (residual or norm is not None or stats_out is not None))):
+            return self.bf16(x, out=out, act=act, residual=residual, out_dtype=out_dtype, splitk=splitk, M=M, norm=norm,
+                             stats_out=stats_out, xpack=xpack, ypack=ypack)
+        import ctypes
+        _check_dev(x)
+        if x.stride(-1) != 1 or x.shape[-1] < self.Kp:
+            raise ValueError(f"PackedLinearW6 input needs unit stride and >= {self.Kp} columns, got {tuple(x.shape)}")
+        if out is None:
+            out = torch.empty(rows, self.N, dtype=F32, device=x.device)
+        if head:
+            _lib.call("fo_gemm_w6_head", x.data_ptr(), x.stride(0), rows, self.Kp, self.q.data_ptr(),
+                      self.scales.data_ptr(), self.ntiles, self.N, out.data_ptr(), out.stride(0), stream(x.device))
+            return out
+        rst, rg, eps, so, gn, yg = _norm_args(norm, stats_out, out)
+        if stats_out is not None and (self.N + 15) // 16 > stats_out.max_groups:
+            raise RuntimeError(f"RowStats holds {stats_out.max_groups} groups per row, fo_gemm_w6 writes "
+                               f"{(self.N + 15) // 16}")
+        sg = ctypes.c_int(0)
+        rt = Runtime.get(x.device)
+        # (x is read as fp32 rows and the output is written row-major only: xpack / ypack stay untouched)
+        _lib.call("fo_gemm_w6", x.data_ptr(), x.stride(0), rows, self.Kp, self.q.data_ptr(), self.scales.data_ptr(),
+                  self.ntiles, self.N, 1 if self.swiglu else 0, out.data_ptr(), out.stride(0), 1 if residual else 0,
+                  rt.ws.data_ptr(), rt.ws.numel(), rt.counters.data_ptr(), rst, rg, eps, so, gn, yg, ctypes.byref(sg),
+                  stream(x.device))
+        if stats_out is not None:
+            stats_out.groups = sg.value
+        return out
+
+
+def _quant_w6(w, q, scales, base, stride):
+    """fo_quant_w6 of the [N, K] weight w into packed tiles base, base + stride, ... of q / scales; returns the
+    dequantised weight (bf16 [N, K])."""
+    if w.dtype not in (BF16, F32):
+        w = w.float()
+    w = w.contiguous()
+    N, K = w.shape
+    dq = torch.empty(N, K, dtype=BF16, device=w.device)
+    _lib.call("fo_quant_w6", w.data_ptr(), 1 if w.dtype == BF16 else 0, N, K, K, q.data_ptr(), scales.data_ptr(),
+              dq.data_ptr(), base, stride, stream(w.device))
+    return dq
+
+
+def quant_w6(w, tile_base=0, tile_stride=1):
+    """fo_quant_w6 of one [N, K] device weight (bf16 or fp32) -> (packed codes uint8, packed E8M0 scale bytes uint8,
+    dequantised weight bf16 [N, K]); the CPU reference is fo.quant.quantize_blocks_e2m3.  tile_base / tile_stride place
+    the source tiles in storages sized for them (the other tiles: zero codes, scale byte 127)."""
+    N, K = w.shape
+    nt = tile_base + ((N + 15) // 16 - 1) * tile_stride + 1
+    KK = (K + 127) // 128
+    q = torch.zeros(nt * KK * 1536, dtype=torch.uint8, device=w.device)
+    scales = torch.full((nt * KK * 64,), 127, dtype=torch.uint8, device=w.device)
+    return q, scales, _quant_w6(w, q, scales, tile_base, tile_stride)
+
+
 class PackedQKVQuant:
     """A fused q|k|v projection under weight-only FP8 or MXFP4 (attn_weights; fmt "fp8" / "mxfp4"): the [N, K] weight,
     N = (H + 2 KVH) * hd, becomes W' = q * 2^e; the bias stays fp32 and untouched.  Holds the packed codes `q` and
@@ -751,6 +883,22 @@ def w4_launch_counts():
 
 def w4_launch_counts_reset():
     _lib.call("fo_gemm_w4_counts_reset")
+
+
+W6_LAUNCH_KINDS = ("w6", "w6_xs", "w6_sk", "w6_head")
+
+
+def w6_launch_counts():
+    """{form: launches issued since the last reset} for fo_gemm_w6's general, X-stationary and split-K forms and for
+    fo_gemm_w6_head (host-side counters of their own: these kernels have no FoLaunchKind)."""
+    import ctypes
+    buf = (ctypes.c_longlong * 4)()
+    _lib.load().fo_gemm_w6_counts(buf, 4)
+    return {k: int(buf[i]) for i, k in enumerate(W6_LAUNCH_KINDS)}
+
+
+def w6_launch_counts_reset():
+    _lib.call("fo_gemm_w6_counts_reset")
 
 
 HEAD_LAUNCH_KINDS = ("w8_head", "w4_head")

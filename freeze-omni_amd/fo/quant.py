@@ -9,7 +9,8 @@ W * 2^-e is exact, so the rounding to e4m3fn (nearest-even) never saturates; q *
 is therefore exactly a bf16 value.
 
 Below it, the same for the weight-only MXFP4 quantiser (fo_quant_w4, `mlp_weights="mxfp4"`): e2m1 codes with one
-exponent per block of 32 columns.
+exponent per block of 32 columns; and for the weight-only MXFP6 quantiser (fo_quant_w6, `mlp_weights="mxfp6"`): e2m3
+codes under the same block scales.
 """
 import torch
 
@@ -129,6 +130,75 @@ def pack_scales_w4(e, tile_base=0, tile_stride=1, out=None):
         out = torch.full(((tile_base + (nt - 1) * tile_stride + 1) * KK * 64,), 127, dtype=torch.uint8)
     out.view(-1, KK * 64)[tile_base::tile_stride][:nt] = s
     return out
+
+
+# ---------------------------------------------------------------- MXFP6 (mlp_weights="mxfp6"; fo_quant_w6)
+#     W'[n, k] = q[n, k] * 2^e[n, k // 32]
+# q is an OCP e2m3 code: bit 5 the sign (copied from the weight's sign bit even where the magnitude rounds to 0), bits
+# 4..3 the exponent (bias 1), bits 2..0 the mantissa: magnitudes 0, 0.125 .. 0.875 (subnormal), 1 .. 1.875 in steps of
+# 0.125, 2 .. 3.75 in steps of 0.25, 4 .. 7.5 in steps of 0.5.  e is one integer per (output row, block of 32 consecutive
+# k): the smallest with max|W[n, block]| * 2^-e <= 7.5, taken from the float's exponent and mantissa (7.5 = 1.875 * 2^2),
+# at least -123 (so that every non-zero q * 2^e is a normal bf16) and 0 for an all-zero block.  W * 2^-e is exact (or an
+# underflow that rounds to 0 anyway) and is rounded to the nearest grid point, ties to the even code; nothing saturates,
+# the scaled block maximum lies in (3.75, 7.5].  q * 2^e has 4 significant bits and is therefore exactly a bf16 value.
+E2M3_GRID = tuple(m * 0.125 if ex == 0 else (8 + m) * 0.125 * 2.0 ** (ex - 1) for ex in range(4) for m in range(8))
+
+
+def block_exponents_e2m3(w):
+    """e[n, k // 32] (int32) of a [N, K] weight under MXFP6, K % 32 == 0."""
+    N, K = w.shape
+    if K % MX_BLOCK:
+        raise ValueError(f"MXFP6 needs K % 32 == 0, got K={K}")
+    amax = w.detach().float().abs().view(N, K // MX_BLOCK, MX_BLOCK).amax(dim=2)
+    bits = amax.contiguous().view(torch.int32)
+    e = (bits >> 23) - 127 - 2 + ((bits & 0x7FFFFF) > 0x700000).to(torch.int32)
+    e = e.clamp(min=-123)
+    return torch.where(amax > 0, e, torch.zeros_like(e))
+
+
+def quantize_blocks_e2m3(w):
+    """w [N, K] (bf16 or fp32, CPU) -> (q uint8 [N, K] e2m3 codes 0..63, e int32 [N, K // 32], w_dq bf16 [N, K])."""
+    w32 = w.detach().float()
+    e = block_exponents_e2m3(w32)
+    ek = e.repeat_interleave(MX_BLOCK, dim=1)
+    m = torch.ldexp(w32, -ek).abs()
+    # the grid's step is 1/8 below 2, 1/4 below 4 and 1/2 up to 7.5; torch.round is nearest with ties to the even
+    # integer, which is the even code (the offsets 0, 8, 16 are even): 0.0625 -> 0, 0.1875 -> 0.25, 7.25 -> 7.0
+    code = torch.where(m < 2, torch.round(m * 8), torch.where(m < 4, 8 + torch.round(m * 4), 16 + torch.round(m * 2)))
+    code = code.to(torch.uint8)
+    neg = torch.signbit(w32)
+    mag = torch.tensor(E2M3_GRID)[code.long()]
+    w_dq = torch.ldexp(torch.where(neg, -mag, mag), ek).to(torch.bfloat16)
+    return code | (neg.to(torch.uint8) << 5), e, w_dq
+
+
+W6_STEP = 1536      # bytes of one code step of one packed tile: 2 planes x 64 lanes x 12
+
+
+def pack_codes_w6(q, tile_base=0, tile_stride=1, out=None):
+    """q uint8 [N, K] (codes 0..63) -> the packed order fo_quant_w6 writes ([tile][ceil(K/128)][2 planes][64 lanes]
+    [12 bytes], flat uint8): lane 16 g + r of code step s holds columns 128 s + 32 g .. + 31 of row r, column j at bits
+    [6 j, 6 j + 6) of its 24 bytes (little-endian), the first 12 bytes in plane 0 and the last 12 in plane 1; tiles
+    placed as pack_codes does."""
+    N, K = q.shape
+    nt, KK = (N + 15) // 16, (K + 127) // 128
+    p = torch.zeros(nt * 16, KK * 128, dtype=torch.int32)
+    p[:N, :K] = q
+    c = p.view(nt * 16, KK * 32, 4)             # four codes -> three bytes
+    b = torch.stack((c[..., 0] | ((c[..., 1] & 3) << 6), (c[..., 1] >> 2) | ((c[..., 2] & 15) << 4),
+                     (c[..., 2] >> 4) | (c[..., 3] << 2)), dim=-1).to(torch.uint8)
+    # [tile][row r][step s][lane group g][plane p][byte b] -> [tile][s][p][lane 16 g + r][b]
+    b = b.view(nt, 16, KK, 4, 2, 12).permute(0, 2, 4, 3, 1, 5).reshape(nt, KK * W6_STEP)
+    if out is None:
+        out = torch.zeros((tile_base + (nt - 1) * tile_stride + 1) * KK * W6_STEP, dtype=torch.uint8)
+    out.view(-1, KK * W6_STEP)[tile_base::tile_stride][:nt] = b
+    return out
+
+
+def pack_scales_w6(e, tile_base=0, tile_stride=1, out=None):
+    """e int32 [N, K // 32] -> E8M0 bytes e + 127 at [tile][ceil(K/128)][16 rows][4]: pack_scales_w4's order (byte g of
+    row r's dword is lane (r, g)'s scale)."""
+    return pack_scales_w4(e, tile_base, tile_stride, out)
 
 
 # ---------------------------------------------------------------- the fused q|k|v weight (attn_weights; hd % 32 == 0)

@@ -14,7 +14,7 @@ import torch
 
 from . import ops
 from .kv import BatchMeta
-from .ops import F32, PackedLinear, PackedLinearW4, PackedLinearW8, PackedQKVQuant
+from .ops import F32, PackedLinear, PackedLinearW4, PackedLinearW6, PackedLinearW8, PackedQKVQuant
 from .weights import ReceiveSource
 
 # FO_ATTN_DENSE=0 passes the item table even for one-token-per-sequence batches (A/B against a
@@ -34,7 +34,7 @@ class Layer:
 class DecoderStack:
     def __init__(self, src, prefix, n_layers, D, H, KVH, eps, bias, rope, pool, kv_layer0=0, first_fp16=False,
                  attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT, mlp_w8=False, mlp_w8_rows=16, mlp_w4=False, mlp_w4_rows=16,
-                 attn_w=None):
+                 attn_w=None, mlp_w6=False):
         """attn_w: None, "fp8" or "mxfp4": the q|k|v and o projections under weight-only FP8 / MXFP4
         (ops.PackedQKVQuant, and ops.PackedLinearW8 / W4 with kind="attn_o": the four projection weights become
         q * 2^e, the biases stay; forwards of <= 16 rows stream the codes where ops.ATTN_POLICY says so, everything else
@@ -47,13 +47,18 @@ class DecoderStack:
         e per 32-column block; forwards of <= 16 rows stream the codes for the GEMMs of ops.W4_POLICY, everything else
         runs the exact bf16 image).
         mlp_w4_rows: 16 or 64, PackedLinearW4's stream_rows (64: 17..64-row forwards stream the codes too, for the
-        pairs of ops.W4_ROWS_POLICY)."""
-        if mlp_w8 and mlp_w4:
-            raise ValueError("mlp_w8 and mlp_w4 are two models of the same weights: pick one")
+        pairs of ops.W4_ROWS_POLICY).
+        mlp_w6: gate/up and down under weight-only MXFP6 instead (ops.PackedLinearW6: e2m3 codes under the same block
+        scales; forwards of <= 16 rows stream the codes for the GEMMs of ops.W6_POLICY, everything else runs the exact
+        bf16 image)."""
+        if bool(mlp_w8) + bool(mlp_w4) + bool(mlp_w6) > 1:
+            raise ValueError("mlp_w8, mlp_w4 and mlp_w6 are models of the same weights: pick one"
+                             if mlp_w6 else "mlp_w8 and mlp_w4 are two models of the same weights: pick one")
         if attn_w not in (None, "fp8", "mxfp4"):
             raise ValueError(f"attn_w must be None, 'fp8' or 'mxfp4', got {attn_w!r}")
         self.attn_w = attn_w
         self.mlp_w4 = bool(mlp_w4)
+        self.mlp_w6 = bool(mlp_w6)
         self.mlp_w8 = bool(mlp_w8)
         self.mlp_w8_rows = mlp_w8_rows
         self.mlp_w4_rows = mlp_w4_rows
@@ -100,6 +105,11 @@ class DecoderStack:
                                       stream_rows=mlp_w4_rows)
                 L.down = PackedLinearW4(src.get(q + "mlp.down_proj.weight", torch.bfloat16), receive=recv,
                                         stream_rows=mlp_w4_rows)
+            elif self.mlp_w6:
+                recv = isinstance(src, ReceiveSource)
+                L.gu = PackedLinearW6(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
+                                      swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16), receive=recv)
+                L.down = PackedLinearW6(src.get(q + "mlp.down_proj.weight", torch.bfloat16), receive=recv)
             else:
                 L.gu = PackedLinear(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
                                     swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16))
@@ -128,6 +138,11 @@ class DecoderStack:
     def mlp_fp4_bytes(self):
         """The MXFP4 codes and scale bytes held beside the bf16 image (0 without mlp_w4)."""
         return sum(getattr(L.gu, "fp4_nbytes", 0) + getattr(L.down, "fp4_nbytes", 0) for L in self.layers)
+
+    @property
+    def mlp_fp6_bytes(self):
+        """The MXFP6 codes and scale bytes held beside the bf16 image (0 without mlp_w6)."""
+        return sum(getattr(L.gu, "fp6_nbytes", 0) + getattr(L.down, "fp6_nbytes", 0) for L in self.layers)
 
     @property
     def attn_fp8_bytes(self):
@@ -199,8 +214,9 @@ class DecoderStack:
         # (17..64 rows under mlp_w8_rows=64 likewise, per GEMM: an FP8 gate/up leaves the o's packed x*gamma unread,
         # an FP8 down fills none for the next q|k|v; 65..128 rows under mlp_w8_rows=128 pack nothing either way)
         # (mlp_w4 likewise at <= 16 rows and, under mlp_w4_rows=64, at 17..64 rows, per GEMM that streams the MXFP4 codes)
+        # (mlp_w6 likewise at <= 16 rows)
         xgp_gu = xgp_qkv = xgp
-        if (self.mlp_w8 or self.mlp_w4) and self.layers:
+        if (self.mlp_w8 or self.mlp_w4 or self.mlp_w6) and self.layers:
             if self.layers[0].gu.streams(T):
                 xgp_gu = None
             if self.layers[0].down.streams(T):

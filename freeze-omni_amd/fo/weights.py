@@ -127,8 +127,9 @@ class FakeQuantSource:
     dequantised -- exactly bf16 values).  An engine with mlp_weights="fp8" serves its weights through this, so the
     oracle, or a second engine of either mode, can be built on the same model.
     fmt: "fp8" (default) or "mxfp4", the image of mlp_weights="mxfp4": W' = q * 2^e with e2m1 codes and one e per
-    32-column block (fo.quant.quantize_blocks_e2m1).
-    lm_head: None (default), "fp8" or "mxfp4": `lm_head.weight` is replaced by its image in that format too, the
+    32-column block (fo.quant.quantize_blocks_e2m1); or "mxfp6", the image of mlp_weights="mxfp6": e2m3 codes under the
+    same block scales (fo.quant.quantize_blocks_e2m3).
+    lm_head: None (default), "fp8", "mxfp4" or "mxfp6": `lm_head.weight` is replaced by its image in that format too, the
     model of an engine with lm_head_weights (model.embed_tokens.weight is never touched).
     attn: None (default), "fp8" or "mxfp4": self_attn.{q,k,v,o}_proj.weight of every model.layers.N are replaced by
     their image in that format, the model of an engine with attn_weights (the biases are never touched).  The scales
@@ -140,10 +141,10 @@ class FakeQuantSource:
             "self_attn.o_proj.weight")
 
     def __init__(self, inner, fmt="fp8", lm_head=None, attn=None):
-        if fmt not in ("fp8", "mxfp4") and not (fmt is None and (lm_head is not None or attn is not None)):
-            raise ValueError(f"FakeQuantSource format must be 'fp8' or 'mxfp4', got {fmt!r}")
-        if lm_head not in (None, "fp8", "mxfp4"):
-            raise ValueError(f"FakeQuantSource lm_head must be None, 'fp8' or 'mxfp4', got {lm_head!r}")
+        if fmt not in ("fp8", "mxfp4", "mxfp6") and not (fmt is None and (lm_head is not None or attn is not None)):
+            raise ValueError(f"FakeQuantSource format must be 'fp8', 'mxfp4' or 'mxfp6', got {fmt!r}")
+        if lm_head not in (None, "fp8", "mxfp4", "mxfp6"):
+            raise ValueError(f"FakeQuantSource lm_head must be None, 'fp8', 'mxfp4' or 'mxfp6', got {lm_head!r}")
         if attn not in (None, "fp8", "mxfp4"):
             raise ValueError(f"FakeQuantSource attn must be None, 'fp8' or 'mxfp4', got {attn!r}")
         self.inner, self.fmt, self.lm_head, self.attn = inner, fmt, lm_head, attn
@@ -162,5 +163,5 @@ class FakeQuantSource:
             fmt = None
         if fmt is None:
             return self.inner.get(name, dtype)
-        quant = ops.quant_w4 if fmt == "mxfp4" else ops.quant_w8
+        quant = {"mxfp4": ops.quant_w4, "mxfp6": ops.quant_w6}.get(fmt, ops.quant_w8)
         return quant(self.inner.get(name, torch.bfloat16))[2].to(dtype)

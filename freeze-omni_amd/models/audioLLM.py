@@ -96,8 +96,8 @@ class AudioLLM:
                        attn_weights="bf16", **kw):
         """attn_weights: "bf16", "fp8" or "mxfp4" (FreezeOmniEngine: the Qwen2 q, k, v and o projections under
         weight-only FP8 or MXFP4, independent of the options below).
-        lm_head_weights: "bf16", "fp8" or "mxfp4" (FreezeOmniEngine: the Qwen2 output head under weight-only FP8 or
-        MXFP4, independent of the options below).  llm_kv: "fp32" or "bf16" (FreezeOmniEngine: the Qwen2 paged KV's element).  mlp_weights: "bf16", "fp8" or "mxfp4" (FreezeOmniEngine: the Qwen2 MLP under weight-only FP8 or MXFP4); mlp_fp8_rows: 16,
+        lm_head_weights: "bf16", "fp8", "mxfp4" or "mxfp6" (FreezeOmniEngine: the Qwen2 output head under weight-only FP8 or
+        MXFP4, independent of the options below).  llm_kv: "fp32" or "bf16" (FreezeOmniEngine: the Qwen2 paged KV's element).  mlp_weights: "bf16", "fp8", "mxfp4" or "mxfp6" (FreezeOmniEngine: the Qwen2 MLP under weight-only FP8 or MXFP4); mlp_fp8_rows: 16,
         64 or 128 (FreezeOmniEngine: with fp8, 64 lets 17..64-row Qwen2 steps stream the codes too, 128 65..128-row
         ones as well); mlp_mxfp4_rows: 16 or 64 (FreezeOmniEngine: with mxfp4, 64 lets 17..64-row Qwen2 steps stream
         the MXFP4 codes too)."""

@@ -28,11 +28,11 @@ class inferencePipeline:
         """weights_from: another inferencePipeline (any device) whose frozen weights this replica copies
         instead of reading / generating its own (fo.replica.copy_frozen: the in-process form of the
         start-up broadcast, bin/pool.py's `devices` replicas).
-        args["llm_mlp_weights"]: "bf16" (default), "fp8" or "mxfp4", the engine's mlp_weights (every replica of a pool takes
+        args["llm_mlp_weights"]: "bf16" (default), "fp8", "mxfp4" or "mxfp6", the engine's mlp_weights (every replica of a pool takes
         the same value, so the copied layouts match); args["llm_mlp_fp8_rows"]: 16 (default), 64 or 128, its mlp_fp8_rows;
         args["llm_mlp_mxfp4_rows"]: 16 (default) or 64, its mlp_mxfp4_rows;
         args["llm_kv"]: "fp32" (default) or "bf16", its llm_kv (the Qwen2 paged KV's element);
-        args["llm_lm_head_weights"]: "bf16" (default), "fp8" or "mxfp4", its lm_head_weights (the Qwen2 output head; as
+        args["llm_lm_head_weights"]: "bf16" (default), "fp8", "mxfp4" or "mxfp6", its lm_head_weights (the Qwen2 output head; as
         with llm_mlp_weights, every replica of a pool takes the same value);
         args["llm_attn_weights"]: "bf16" (default), "fp8" or "mxfp4", its attn_weights (the Qwen2 q, k, v and o
         projections; every replica of a pool takes the same value)."""

@@ -307,6 +307,44 @@ int fo_gemm_w4_head(const float* X, int ldx, int M, int K, const void* q, const 
                     float* Y, int ldy, hipStream_t stream);
 int fo_gemm_head_counts(long long* out, int n);
 int fo_gemm_head_counts_reset(void);
+/* Weight-only MXFP6 (OCP e2m3 codes, one power-of-two scale per 32 elements) for <= 16-row launches of the Qwen2 MLP
+ * (fo_gemm_w6) and output head (fo_gemm_w6_head):
+ *   W'[n][k] = q[n][k] * 2^e[n][k / 32], q an e2m3 code (bit 5 the sign, 2 exponent bits of bias 1, 3 mantissa bits:
+ *   magnitudes 0, 0.125 .. 0.875, 1 .. 1.875, 2 .. 3.75, 4 .. 7.5), e the smallest integer with
+ *   max|W[n][block]| * 2^-e <= 7.5, taken from the float's exponent and mantissa (mantissa > 0x700000 adds one), at
+ *   least -123, 0 for an all-zero block; nearest grid point, ties to the even code, the sign bit copied.  q * 2^e has 4
+ *   significant bits, so W' is exactly a bf16 matrix.  The CPU definition is fo/quant.py (quantize_blocks_e2m3,
+ *   pack_codes_w6, pack_scales_w6).
+ * Packed layout: codes [tile][ceil(K/128)][2 planes][64 lanes][12 bytes] (fo_quant_w6_bytes(N, K): 1536 bytes per tile
+ * and code step).  Lane 16 g + r of code step s holds the 32 consecutive columns 128 s + 32 g .. + 31 of row r of the
+ * tile -- one scale block -- as a 192-bit field, column j at bits [6 j, 6 j + 6) counted from bit 0 of the first dword
+ * (the order v_cvt_scalef32_pk32_bf16_fp6 reads); plane p holds dwords 3 p .. 3 p + 2 of every lane's field (columns
+ * 16 p .. + 15), so a wave's 12-byte loads are contiguous.  The lane's values 8 t .. 8 t + 7 are its MFMA B fragment
+ * of sub-step t; the A fragment of lane (r, g) there is X[row][128 s + 32 g + 8 t .. + 7].  K is padded to a multiple
+ * of 128 with zero codes.  Scales: E8M0 bytes e + 127 at [tile][ceil(K/128)][16 rows][4] (fo_quant_w6_scale_bytes(N, K),
+ * MXFP4's layout), byte g of row r's dword being lane (r, g)'s; 127 for rows beyond N and blocks beyond K.
+ * fo_quant_w6: as fo_quant_w4 (tile_base / tile_stride interleave the SwiGLU pair; wdq, optional, receives W' as bf16
+ *   [N][K]); bit-equal to the CPU definition.
+ * fo_gemm_w6: fo_gemm_w4's arguments, epilogue semantics and refusals (M outside 1..16, K % 32 != 0, NULL pointers, an
+ *   ntiles that is not the packed tile count, codes of 2 GiB or more, ...: all on the host before any HIP call, with
+ *   the entry's name).  One workgroup per output tile or SwiGLU pair, its waves splitting the code steps (k_w6); the
+ *   SwiGLU pair at K = 3584 X-stationary and persistent (k_w6_xs); long-K plain launches split K across workgroups and
+ *   merge inside the launch in split order where ws and counters are given (k_w6_sk; the tickets are left zeroed).  A
+ *   lane whose block lies at or past K reads no X and feeds zero A fragments.  Deterministic, capture-safe.
+ * fo_gemm_w6_head: fo_gemm_w4_head's arguments and refusals (K must be 3584): the plain form of k_w6_xs.
+ * fo_gemm_w6_counts: the launches issued per form since the last reset (general, xs, sk, head) into
+ *   out[0 .. min(n, 4)); returns 4.  A refused call is not counted.  These kernels have no FoLaunchKind. */
+long long fo_quant_w6_bytes(int N, int K);
+long long fo_quant_w6_scale_bytes(int N, int K);
+int fo_quant_w6(const void* W, int src_bf16, int N, int K, int ldw, void* q, void* scale, void* wdq, int tile_base,
+                int tile_stride, hipStream_t stream);
+int fo_gemm_w6(const float* X, int ldx, int M, int K, const void* q, const void* scale, int ntiles, int N, int swiglu,
+               float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters, const float* rstats,
+               int rgroups, float eps, float* sout, const float* gnext, float* yg, int* sgroups, hipStream_t stream);
+int fo_gemm_w6_head(const float* X, int ldx, int M, int K, const void* q, const void* scale, int ntiles, int N,
+                    float* Y, int ldy, hipStream_t stream);
+int fo_gemm_w6_counts(long long* out, int n);
+int fo_gemm_w6_counts_reset(void);
 /* The fused q|k|v projection of a Qwen2 layer under the same two formats, for calls of <= 16 rows:
  * fo_gemm_qkv_rope_kv's arguments with codes and scales in place of Wp, and no workspace, tickets or split.
  * Layout: q and scale are fo_quant_w8's / fo_quant_w4's packed codes and scales of the [N][K] fused weight,

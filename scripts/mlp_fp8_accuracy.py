@@ -1,10 +1,12 @@
-"""What mlp_weights="fp8" (or, with the second argument, "mxfp4") costs against the unquantised model on the
+"""What mlp_weights="fp8" (or, with the second argument, "mxfp4" or "mxfp6") costs against the unquantised model on the
 full-depth flow of tests/test_full_depth_gpu.py (real geometry, 28 Qwen2 layers, the engine's counter-hash weights): the system prompt, question.wav's 13 chunks (the
 reference's fbank features, tests/golden/fbank.npz) with the user chat prefix, the assistant prefix and greedy text
 steps.  Prints the state-probability differences per chunk, the decision-row logit differences under teacher forcing
 with the bf16 engine's ids (and how often the arg-max agrees, against the bf16 top-2 margin), and where the two
 engines' own greedy texts part.  A measurement, not a test.
-python scripts/mlp_fp8_accuracy.py [steps] [fp8|mxfp4|bf16] [heads] [attns] (GPU only).  The optional third argument is a
+python scripts/mlp_fp8_accuracy.py [steps] [fp8|mxfp4|mxfp6|bf16|a,b,..] [heads] [attns] (GPU only).  A comma-separated
+second argument (`fp8,mxfp6,mxfp4`) measures each MLP mode in turn against the one bf16 engine of the process; a head
+`same` then stands for the head of the MLP mode's own format.  The optional third argument is a
 comma-separated list of lm_head_weights formats (`fp8,mxfp4`): each is measured against the bf16 engine in the same
 process, over the MLP mode of the second argument (`bf16`: the head alone is quantised).  The optional fourth is a
 comma-separated list of attn_weights formats, each measured under every head of the third (`bf16 bf16 fp8,mxfp4`: the
@@ -68,7 +70,7 @@ eng = engine("bf16")
 p0, l0, t0 = flow(eng)
 del eng
 torch.cuda.empty_cache()
-for head, attn in ((h, a) for h in HEADS for a in ATTNS):
+for FMT, head, attn in ((f, f if h == "same" else h, a) for f in FMT.split(",") for h in HEADS for a in ATTNS):
     eng = engine(FMT, head, attn)
     print(f"mlp_weights={FMT}{'' if head == 'bf16' else f' lm_head_weights={head}'}"
           f"{'' if attn == 'bf16' else f' attn_weights={attn}'} against bf16:")
