@@ -14,6 +14,7 @@ import yaml
 
 from bin.pool import pipelineObjectPool
 from fo.duplex import DEFAULT_CONFIG, DuplexScheduler, DuplexSession
+from fo.quant import check_format
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -44,6 +45,8 @@ class DialogStateParams(DuplexSession):
                 cls.DIALOG_STATE_PRED_CONFIGS = get_args()
             c = cls.DIALOG_STATE_PRED_CONFIGS
             ic = c.get("inference_control", {})
+            for opt in ("mlp_weights", "lm_head_weights", "attn_weights"):   # the YAML's values, before a replica is built
+                check_format(opt, c.get("llm_" + opt, "bf16"))
             cls.PIPELINE_POOL = pipelineObjectPool(size=cls.MAX_PIPELINE_NUN, configs={
                 "model_path": c["model_path"], "llm_path": c.get("llm_path"), "device": c.get("device", "cuda:0"),
                 "top_k": ic.get("top_k", 1), "top_p": ic.get("top_p", 0.0), "temperature": ic.get("temperature", 1.0),

@@ -30,6 +30,7 @@ _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
+from fo.quant import FORMATS  # noqa: E402
 from models.audio_processor import audioEncoderProcessor  # noqa: E402
 from models.decoder.llm2tts import llm2TTS  # noqa: E402
 from models.pipeline import inferencePipeline  # noqa: E402
@@ -48,20 +49,20 @@ def get_args(argv=None):
     p.add_argument("--input_wav", required=True, help="input wav")
     p.add_argument("--output_wav", required=True, help="output wav")
     p.add_argument("--device", default="cuda:0")
-    p.add_argument("--llm_mlp_weights", choices=["bf16", "fp8", "mxfp4", "mxfp6"], default="bf16",
+    p.add_argument("--llm_mlp_weights", choices=FORMATS["mlp_weights"], default="bf16",
                    help="Qwen2 gate/up/down weights: bf16, weight-only FP8 (e4m3 codes x a power of two per row) or "
                         "weight-only MXFP4 / MXFP6 (e2m1 / e2m3 codes x a power of two per 32 columns)")
     p.add_argument("--llm_mlp_fp8_rows", type=int, choices=[16, 64, 128], default=16,
                    help="with --llm_mlp_weights fp8: the most rows of a Qwen2 step that stream the FP8 codes")
     p.add_argument("--llm_mlp_mxfp4_rows", type=int, choices=[16, 64], default=16,
                    help="with --llm_mlp_weights mxfp4: the most rows of a Qwen2 step that stream the MXFP4 codes")
-    p.add_argument("--llm_kv", choices=["fp32", "bf16"], default="fp32",
+    p.add_argument("--llm_kv", choices=FORMATS["llm_kv"], default="fp32",
                    help="Qwen2 paged KV cache element: fp32, or bf16 (half the memory and attention bytes)")
-    p.add_argument("--llm_lm_head_weights", choices=["bf16", "fp8", "mxfp4", "mxfp6"], default="bf16",
+    p.add_argument("--llm_lm_head_weights", choices=FORMATS["lm_head_weights"], default="bf16",
                    help="Qwen2 output head (lm_head) weights: bf16, weight-only FP8 (e4m3 codes x a power of two per "
                         "vocabulary row) or weight-only MXFP4 / MXFP6 (e2m1 / e2m3 codes x a power of two per 32 "
                         "columns)")
-    p.add_argument("--llm_attn_weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
+    p.add_argument("--llm_attn_weights", choices=FORMATS["attn_weights"], default="bf16",
                    help="Qwen2 attention projection (q, k, v, o) weights: bf16, weight-only FP8 (e4m3 codes x a power of "
                         "two per output row) or weight-only MXFP4 (e2m1 codes x a power of two per 32 columns)")
     p.add_argument("--role", default="You are a helpful assistant.")

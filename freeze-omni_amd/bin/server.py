@@ -45,6 +45,7 @@ if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from fo.duplex import DuplexScheduler, EnergyVAD, ScriptedVAD  # noqa: E402
+from fo.quant import FORMATS  # noqa: E402
 
 TICK_SLEEP = 0.005   # DialogStateParams.SLEEP_INTERVAL: the reference threads poll every 5 ms
 
@@ -377,17 +378,17 @@ def get_parser():
     p.add_argument("--top_p", type=float, default=0.8)
     p.add_argument("--top_k", type=int, default=20)
     p.add_argument("--temperature", type=float, default=0.8)
-    p.add_argument("--llm_mlp_weights", choices=["bf16", "fp8", "mxfp4", "mxfp6"], default=None,
+    p.add_argument("--llm_mlp_weights", choices=FORMATS["mlp_weights"], default=None,
                    help="Qwen2 gate/up/down weights: bf16 (default), weight-only FP8, MXFP4 or MXFP6")
     p.add_argument("--llm_mlp_fp8_rows", type=int, choices=[16, 64, 128], default=None,
                    help="with FP8 weights: the most rows of a Qwen2 step that stream the codes (default 16)")
     p.add_argument("--llm_mlp_mxfp4_rows", type=int, choices=[16, 64], default=None,
                    help="with MXFP4 weights: the most rows of a Qwen2 step that stream the codes (default 16)")
-    p.add_argument("--llm_kv", choices=["fp32", "bf16"], default=None,
+    p.add_argument("--llm_kv", choices=FORMATS["llm_kv"], default=None,
                    help="Qwen2 paged KV cache element: fp32 (default), or bf16 (half the memory and attention bytes)")
-    p.add_argument("--llm_lm_head_weights", choices=["bf16", "fp8", "mxfp4", "mxfp6"], default=None,
+    p.add_argument("--llm_lm_head_weights", choices=FORMATS["lm_head_weights"], default=None,
                    help="Qwen2 output head (lm_head) weights: bf16 (default), weight-only FP8, MXFP4 or MXFP6")
-    p.add_argument("--llm_attn_weights", choices=["bf16", "fp8", "mxfp4"], default=None,
+    p.add_argument("--llm_attn_weights", choices=FORMATS["attn_weights"], default=None,
                    help="Qwen2 attention projection (q, k, v, o) weights: bf16 (default), weight-only FP8, or "
                         "weight-only MXFP4")
     p.add_argument("--config", default=None, help="duplex YAML (configs/dialog_state_pred_config.yaml form)")

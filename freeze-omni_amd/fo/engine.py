@@ -23,6 +23,7 @@ from .kv import GroupMeta
 from .llm import LLMEngine
 from .ops import F32, I32
 from .params import all_shapes
+from .quant import check_format
 from .speech import AdapterEngine, FbankGPU, SpeechEncoderEngine
 from .tokenizer import load_tokenizer
 from .tts import TTSEngine
@@ -77,8 +78,8 @@ class FreezeOmniEngine:
         where ops.ATTN_POLICY says so; everything else runs the exact bf16 image.  `src` serves the dequantised
         projections (FakeQuantSource(..., attn=...)).
         lm_head_weights: "bf16" (default), "fp8", "mxfp4" or "mxfp6": the Qwen2 output head (lm_head.weight only, never
-        the embedding) under weight-only FP8 per vocabulary row, MXFP4 or MXFP6, independent of mlp_weights,
-        mlp_*_rows and llm_kv.  Calls of <= 16 rows (the captured TextGraph, the eager text_step, LLMEngine.logits)
+        the embedding) under weight-only FP8 per vocabulary row, MXFP4 or MXFP6, independent of
+        mlp_weights, mlp_*_rows and llm_kv.  Calls of <= 16 rows (the captured TextGraph, the eager text_step, LLMEngine.logits)
         stream the codes where ops.HEAD_POLICY says so; more rows run the exact bf16 image.  `src` serves the
         dequantised head (FakeQuantSource(..., lm_head=...)).
         llm_kv: "fp32" (default) or "bf16": the element of the Qwen2 stack's paged KV.  "bf16" is the
@@ -108,28 +109,13 @@ class FreezeOmniEngine:
         (models/utils.py:31-38)."""
         if not torch.cuda.is_available():
             raise RuntimeError("FreezeOmniEngine needs an MI355X (gfx950) device: there is no CPU fallback")
-        if mlp_weights not in ("bf16", "fp8", "mxfp4", "mxfp6"):
-            raise ValueError(f"mlp_weights must be 'bf16', 'fp8', 'mxfp4' or 'mxfp6', got {mlp_weights!r}")
-        if mlp_fp8_rows not in (16, 64, 128):
-            raise ValueError(f"mlp_fp8_rows must be 16, 64 or 128, got {mlp_fp8_rows!r}")
-        if mlp_fp8_rows != 16 and mlp_weights != "fp8":
-            raise ValueError(f"mlp_fp8_rows={mlp_fp8_rows} needs mlp_weights='fp8'")
-        if mlp_mxfp4_rows not in (16, 64):
-            raise ValueError(f"mlp_mxfp4_rows must be 16 or 64, got {mlp_mxfp4_rows!r}")
-        if mlp_mxfp4_rows != 16 and mlp_weights != "mxfp4":
-            raise ValueError(f"mlp_mxfp4_rows={mlp_mxfp4_rows} needs mlp_weights='mxfp4'")
-        if llm_kv not in ("fp32", "bf16"):
-            raise ValueError(f"llm_kv must be 'fp32' or 'bf16', got {llm_kv!r}")
-        if lm_head_weights not in ("bf16", "fp8", "mxfp4", "mxfp6"):
-            raise ValueError(f"lm_head_weights must be 'bf16', 'fp8', 'mxfp4' or 'mxfp6', got {lm_head_weights!r}")
-        if attn_weights not in ("bf16", "fp8", "mxfp4"):
-            raise ValueError(f"attn_weights must be 'bf16', 'fp8' or 'mxfp4', got {attn_weights!r}")
-        self.attn_weights = attn_weights
-        self.lm_head_weights = lm_head_weights
-        self.mlp_weights = mlp_weights
-        self.mlp_fp8_rows = mlp_fp8_rows
-        self.mlp_mxfp4_rows = mlp_mxfp4_rows
-        self.llm_kv = llm_kv
+        self.mlp_weights = check_format("mlp_weights", mlp_weights)
+        self.mlp_fp8_rows = check_format("mlp_fp8_rows", mlp_fp8_rows, ops.QUANT_FORMATS["fp8"].stream_rows)
+        self.mlp_mxfp4_rows = check_format("mlp_mxfp4_rows", mlp_mxfp4_rows, ops.QUANT_FORMATS["mxfp4"].stream_rows)
+        self.llm_kv = check_format("llm_kv", llm_kv)
+        self.lm_head_weights = check_format("lm_head_weights", lm_head_weights)
+        self.attn_weights = check_format("attn_weights", attn_weights)
+        self._llm_options()   # (refuses a *_rows option without its format before anything is loaded)
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         self.cfg, self.synth, self.llm_path = load_model_dir(model_path, llm_path)
@@ -152,11 +138,7 @@ class FreezeOmniEngine:
         self.ada = {i: AdapterEngine(src, self.cfg, i, self.device, max_sessions) for i in ("user", "system")}
         V = self.cfg["llm"]["vocab_size"]
         self.llm = LLMEngine(src, self.cfg["llm"], self.device,
-                             kv_tokens=llm_kv_tokens or min(max_sessions * 4096, 1 << 17),
-                             mlp_w8=mlp_weights == "fp8", mlp_w8_rows=mlp_fp8_rows, kv_dtype=llm_kv,
-                             mlp_w4=mlp_weights == "mxfp4", mlp_w4_rows=mlp_mxfp4_rows,
-                             lm_head_weights=lm_head_weights, attn_weights=attn_weights,
-                             mlp_w6=mlp_weights == "mxfp6")
+                             kv_tokens=llm_kv_tokens or min(max_sessions * 4096, 1 << 17), **self._llm_options())
         self.tts = TTSEngine(src, self.cfg["decoder_json"], self.device,
                              kv_tokens=tts_kv_tokens or min(max_sessions * 2048, 1 << 17))
         self.codec = CodecEngine(src, self.cfg["codec_json"], self.device)
@@ -171,6 +153,16 @@ class FreezeOmniEngine:
         self.use_graphs = True
         self.predict_usr_state = ty["model_conf"].get("predict_usr_state", 0)
         self._chat_template(ty["model_conf"].get("chat_template"))
+
+    def _llm_options(self):
+        """This engine's Qwen2 options as LLMEngine's keywords: mlp_fp8_rows / mlp_mxfp4_rows, each of which needs its
+        own format, become the one mlp_rows."""
+        rows = {"fp8": self.mlp_fp8_rows, "mxfp4": self.mlp_mxfp4_rows}
+        for fmt, r in rows.items():
+            if r != 16 and self.mlp_weights != fmt:
+                raise ValueError(f"mlp_{fmt}_rows={r} needs mlp_weights={fmt!r}")
+        return dict(mlp_weights=self.mlp_weights, mlp_rows=rows.get(self.mlp_weights, 16), kv_dtype=self.llm_kv,
+                    lm_head_weights=self.lm_head_weights, attn_weights=self.attn_weights)
 
     def _model_source(self, raw):
         """`raw` as the model this engine computes: the MLP, the head and / or the attention projections replaced by
@@ -212,11 +204,7 @@ class FreezeOmniEngine:
             kv_tokens = self.llm.pool.n_pages * self.llm.pool.PS
             self.llm = None   # release the old weights and pool first (15 GB at Qwen2-7B size)
             torch.cuda.empty_cache()
-            self.llm = LLMEngine(src, self.cfg["llm"], self.device, kv_tokens=kv_tokens,
-                                 mlp_w8=self.mlp_weights == "fp8", mlp_w8_rows=self.mlp_fp8_rows,
-                                 kv_dtype=self.llm_kv, mlp_w4=self.mlp_weights == "mxfp4",
-                                 mlp_w4_rows=self.mlp_mxfp4_rows, lm_head_weights=self.lm_head_weights,
-                                 attn_weights=self.attn_weights, mlp_w6=self.mlp_weights == "mxfp6")
+            self.llm = LLMEngine(src, self.cfg["llm"], self.device, kv_tokens=kv_tokens, **self._llm_options())
         elif "predictor_head.weight" in src:
             self.llm.head_w, self.llm.head_b = src.get("predictor_head.weight"), src.get("predictor_head.bias")
         self.src = self._model_source(src) if fq else src

@@ -8,33 +8,34 @@ import torch
 
 from . import ops, tables
 from .kv import BatchMeta, KVPool, KVSeq
-from .ops import F32, I32, PackedLinear, PackedLinearW4, PackedLinearW6, PackedLinearW8
+from .ops import F32, I32, QUANT_LINEAR, PackedLinear
+from .quant import check_format
 from .stack import DecoderStack
 from .weights import ReceiveSource
 
 
 class LLMEngine:
     def __init__(self, src, llm_cfg, device, head_src=None, kv_tokens=65536, page_size=16, max_pos=None,
-                 mlp_w8=False, mlp_w8_rows=16, kv_dtype="fp32", mlp_w4=False, mlp_w4_rows=16, lm_head_weights="bf16",
-                 attn_weights="bf16", mlp_w6=False):
-        """mlp_w6: the MLP under weight-only MXFP6 (DecoderStack mlp_w6).
+                 mlp_weights="bf16", mlp_rows=16, kv_dtype="fp32", lm_head_weights="bf16", attn_weights="bf16"):
+        """mlp_weights: "bf16" (default), "fp8", "mxfp4" or "mxfp6" -- mlp.{gate,up,down}_proj.weight of every layer
+        under that weight-only format, and mlp_rows, the most rows of a step that stream
+        the codes: DecoderStack's options of the same names.
         attn_weights: "bf16" (default), "fp8" or "mxfp4" -- self_attn.{q,k,v,o}_proj.weight of every layer under
-        weight-only FP8 / MXFP4 (DecoderStack attn_w): steps of <= 16 rows stream the codes where
+        weight-only FP8 / MXFP4 (DecoderStack attn_weights): steps of <= 16 rows stream the codes where
         ops.ATTN_POLICY says so, everything else runs the exact bf16 image.  The biases are untouched.
         lm_head_weights: "bf16" (default), "fp8", "mxfp4" or "mxfp6" -- lm_head.weight under weight-only FP8 / MXFP4 /
-        MXFP6: calls of <= 16 rows stream the codes where ops.HEAD_POLICY says so, every other call runs the exact
-        bf16 image.  embed_tokens is never quantised.  Over a ReceiveSource the head's storages are allocated and nothing
-        is quantised (a replica whose weights arrive by broadcast fills codes, scales and image).
+        MXFP6: calls of <= 16 rows stream the codes where ops.HEAD_POLICY (ops.W6_POLICY for
+        MXFP6) says so, every other call runs the exact bf16 image.  embed_tokens is never quantised.  Over a
+        ReceiveSource the head's storages are allocated and nothing is quantised (a replica whose weights arrive by
+        broadcast fills codes, scales and image).
         kv_dtype: "fp32" (default) or "bf16" -- the paged KV's element: K / V rounded once to bf16
         as they are appended and read as bf16 by the attention; kv_tokens keeps meaning tokens (half the bytes)."""
         if kv_dtype not in ("fp32", "bf16"):
             raise ValueError(f'kv_dtype must be "fp32" or "bf16", got {kv_dtype!r}')
-        if lm_head_weights not in ("bf16", "fp8", "mxfp4", "mxfp6"):
-            raise ValueError(f"lm_head_weights must be 'bf16', 'fp8', 'mxfp4' or 'mxfp6', got {lm_head_weights!r}")
-        if attn_weights not in ("bf16", "fp8", "mxfp4"):
-            raise ValueError(f"attn_weights must be 'bf16', 'fp8' or 'mxfp4', got {attn_weights!r}")
-        self.attn_weights = attn_weights
-        self.lm_head_weights = lm_head_weights
+        self.mlp_weights = check_format("mlp_weights", mlp_weights)
+        self.lm_head_weights = check_format("lm_head_weights", lm_head_weights)
+        self.attn_weights = check_format("attn_weights", attn_weights)
+        self.mlp_rows = mlp_rows
         self.kv_dtype = kv_dtype
         c = llm_cfg
         self.device = torch.device(device)
@@ -49,17 +50,15 @@ class LLMEngine:
         self.pool = KVPool(c["num_hidden_layers"], self.KVH, self.hd, n_pages, page_size, self.device,
                            dtype=torch.bfloat16 if kv_dtype == "bf16" else torch.float32)
         self.stack = DecoderStack(src, "model.layers.", c["num_hidden_layers"], self.D, self.H, self.KVH, self.eps,
-                                  True, self.rope, self.pool, first_fp16=True, mlp_w8=mlp_w8,
-                                  mlp_w8_rows=mlp_w8_rows, mlp_w4=mlp_w4, mlp_w4_rows=mlp_w4_rows,
-                                  attn_w=None if attn_weights == "bf16" else attn_weights, mlp_w6=mlp_w6)
+                                  True, self.rope, self.pool, first_fp16=True, mlp_weights=mlp_weights,
+                                  mlp_rows=mlp_rows, attn_weights=attn_weights)
         self.embed_tokens = src.get("model.embed_tokens.weight", torch.bfloat16)
         self.norm = src.get("model.norm.weight")
         if lm_head_weights == "bf16":
             self.lm_head = PackedLinear(src.get("lm_head.weight", torch.bfloat16))
         else:
-            quantised = {"fp8": PackedLinearW8, "mxfp4": PackedLinearW4, "mxfp6": PackedLinearW6}[lm_head_weights]
-            self.lm_head = quantised(src.get("lm_head.weight", torch.bfloat16),
-                                     receive=isinstance(src, ReceiveSource), kind="head")
+            self.lm_head = QUANT_LINEAR[lm_head_weights](src.get("lm_head.weight", torch.bfloat16),
+                                                         receive=isinstance(src, ReceiveSource), kind="head")
         hs = head_src or src
         self.head_w = hs.get("predictor_head.weight") if "predictor_head.weight" in hs else None
         self.head_b = hs.get("predictor_head.bias") if self.head_w is not None else None
@@ -68,40 +67,18 @@ class LLMEngine:
     def weight_bytes(self):
         return self.stack.weight_bytes
 
-    @property
-    def mlp_fp8_bytes(self):
-        return self.stack.mlp_fp8_bytes
+    def head_code_bytes(self, fmt):
+        """The head's codes and scales of format `fmt`, held beside its bf16 image (0 unless lm_head_weights is fmt)."""
+        return getattr(self.lm_head, ops.QUANT_FORMATS[fmt].nbytes_attr, 0)
 
-    @property
-    def mlp_fp4_bytes(self):
-        return self.stack.mlp_fp4_bytes
-
-    @property
-    def mlp_fp6_bytes(self):
-        return self.stack.mlp_fp6_bytes
-
-    @property
-    def lm_head_fp6_bytes(self):
-        """The MXFP6 head's codes and scales, held beside its bf16 image (0 without lm_head_weights="mxfp6")."""
-        return self.lm_head.fp6_nbytes if self.lm_head_weights == "mxfp6" else 0
-
-    @property
-    def attn_fp8_bytes(self):
-        return self.stack.attn_fp8_bytes
-
-    @property
-    def attn_fp4_bytes(self):
-        return self.stack.attn_fp4_bytes
-
-    @property
-    def lm_head_fp8_bytes(self):
-        """The FP8 head's codes and scales, held beside its bf16 image (0 without lm_head_weights="fp8")."""
-        return self.lm_head.fp8_nbytes if self.lm_head_weights == "fp8" else 0
-
-    @property
-    def lm_head_fp4_bytes(self):
-        """The MXFP4 head's codes and scales, held beside its bf16 image (0 without lm_head_weights="mxfp4")."""
-        return self.lm_head.fp4_nbytes if self.lm_head_weights == "mxfp4" else 0
+    mlp_fp8_bytes = property(lambda self: self.stack.code_bytes("mlp", "fp8"))
+    mlp_fp4_bytes = property(lambda self: self.stack.code_bytes("mlp", "mxfp4"))
+    mlp_fp6_bytes = property(lambda self: self.stack.code_bytes("mlp", "mxfp6"))
+    attn_fp8_bytes = property(lambda self: self.stack.code_bytes("attn", "fp8"))
+    attn_fp4_bytes = property(lambda self: self.stack.code_bytes("attn", "mxfp4"))
+    lm_head_fp8_bytes = property(lambda self: self.head_code_bytes("fp8"))
+    lm_head_fp4_bytes = property(lambda self: self.head_code_bytes("mxfp4"))
+    lm_head_fp6_bytes = property(lambda self: self.head_code_bytes("mxfp6"))
 
     def new_seq(self):
         return KVSeq(self.pool)

@@ -3,6 +3,8 @@
 torch is used only for device memory and the current stream (plumbing); every computation
 below is a hand-written gfx950 kernel in libfo_hip.so.
 """
+import ctypes
+import dataclasses
 import os
 import threading
 
@@ -10,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .quant import check_format
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -350,23 +353,6 @@ HEAD_K = 3584   # the K the X-stationary plain forms are compiled for
 ATTN_POLICY = {"fp8": {"qkv": True, "o": False}, "mxfp4": {"qkv": True, "o": False}}
 
 
-def _head_kind(kind, swiglu_up, stream_rows):
-    if kind not in (None, "head", "attn_o"):
-        raise ValueError(f"kind must be None, 'head' or 'attn_o', got {kind!r}")
-    if kind is not None and (swiglu_up is not None or stream_rows != 16):
-        raise ValueError("a head or an attention output is a plain projection with stream_rows=16")
-    return kind
-
-
-def _kind_stream(kind, fmt, K, default):
-    """Whether a <= 16-row call of a PackedLinearW8 / W4 of this kind streams the codes."""
-    if kind == "head":
-        return bool(W6_POLICY["head"] if fmt == "mxfp6" else HEAD_POLICY[fmt]) if K == HEAD_K else True
-    if kind == "attn_o":
-        return bool(ATTN_POLICY[fmt]["o"])
-    return default
-
-
 # Which 17..64-row launches of a PackedLinearW8(stream_rows=64) stream the codes: per GEMM, the row-block counts
 # (ceil(rows / 16)) at which fo_gemm_w8_rows beat the bf16 image by more than that arm's spread -- for the down, by
 # more than the packed input it costs the next q|k|v as well (scripts/gemm_w8_rows_ab.py,
@@ -375,128 +361,6 @@ def _kind_stream(kind, fmt, K, default):
 # lost at every pair, gate/up 1.13-1.20x and down 1.15-1.23x -- so 65..128 rows stay on the image.  The one place the
 # policy lives.
 W8_ROWS_POLICY = {"gate_up": (2, 3, 4), "down": (2,)}
-
-
-class PackedLinearW8:
-    """A bias-free linear layer under weight-only FP8 (fo.quant, include/fo_hip.h fo_quant_w8): the weight is
-    W'[n, k] = q[n, k] * 2^e[n] with q an e4m3fn code.  Holds the packed codes `q`, the per-column `scales` and
-    `bf16`, a PackedLinear over the dequantised weight (W' is exactly a bf16 matrix).  Calls of <= 16 fp32 rows stream
-    the codes (fo_gemm_w8); every other call forwards to the bf16 image, so both compute X . W'^T.
-
-    w: [N, K] device weight (bf16 or fp32), quantised on the device; swiglu_up as PackedLinear.
-    receive=True: storages allocated, nothing quantised (a replica whose weights arrive by broadcast).
-    stream_rows: 16 (default), 64 or 128.  64 also lets calls of 17..64 fp32 rows stream the codes (fo_gemm_w8_rows),
-    128 calls of 65..128 rows as well (fo_gemm_w8_rows128), for the row-block counts in `rows_rb`: W8_ROWS_POLICY's for
-    this GEMM, the pairs that measured faster than the image.  Setting `rows_rb = tuple(range(2, 9))` on an instance
-    sends every call of 17 rows up to stream_rows there (tests, A/B scripts).
-    kind="head": the Qwen2 output head (see _head_kind): plain, stream_rows 16, no row-stream policy of its own.
-    kind="attn_o": a Qwen2 attention output projection (attn_weights): plain, stream_rows 16, `stream` from
-    ATTN_POLICY; its <= 16-row calls run fo_gemm_w8's general form with the residual and stats_out."""
-
-    bias = None
-
-    def __init__(self, w, swiglu_up=None, receive=False, stream_rows=16, kind=None):
-        _check_dev(w)
-        if stream_rows not in (16, 64, 128):
-            raise ValueError(f"stream_rows must be 16, 64 or 128, got {stream_rows!r}")
-        self.stream_rows = stream_rows
-        self.N, self.K = w.shape
-        self.kind = _head_kind(kind, swiglu_up, stream_rows)
-        self.rows_rb = () if self.kind else W8_ROWS_POLICY["gate_up" if swiglu_up is not None else "down"]
-        self.stream = _kind_stream(self.kind, "fp8", self.K, True)
-        self.Kp = (self.K + 31) // 32 * 32
-        self.swiglu = swiglu_up is not None
-        self.device = w.device
-        self.ntiles = (self.N + 15) // 16 * (2 if self.swiglu else 1)
-        self.q = torch.empty(self.ntiles * ((self.K + 63) // 64) * 1024, dtype=torch.uint8, device=w.device)
-        self.scales = torch.empty(self.ntiles * 16, dtype=F32, device=w.device)
-        if receive:
-            self.bf16 = PackedLinear(w, swiglu_up=swiglu_up)
-            return
-        dq = [self._quant(w, 0, 2 if self.swiglu else 1)]
-        if self.swiglu:
-            dq.append(self._quant(swiglu_up, 1, 2))
-        self.bf16 = PackedLinear(dq[0], swiglu_up=dq[1] if self.swiglu else None)
-
-    def _quant(self, w, base, stride):
-        return _quant_w8(w, self.q, self.scales, base, stride)
-
-    @property
-    def packed(self):
-        return self.bf16.packed
-
-    @property
-    def nbytes(self):
-        """The bf16 image (what `weight_bytes` has always counted); the codes are fp8_nbytes."""
-        return self.bf16.nbytes
-
-    @property
-    def fp8_nbytes(self):
-        return self.q.numel() + self.scales.numel() * 4
-
-    def streams(self, rows):
-        """Whether a call of `rows` fp32 rows streams the codes (else it runs the bf16 image)."""
-        if rows <= 16:
-            return self.stream
-        return rows <= self.stream_rows and (rows + 15) // 16 in self.rows_rb
-
-    def __call__(self, x, out=None, act="none", residual=False, out_dtype=F32, splitk=0, M=None, norm=None,
-                 stats_out=None, xpack=None, ypack=None):
-        rows = x.shape[0] if M is None else M
-        head = self.kind == "head" and self.K == HEAD_K   # (the head entry is plain: anything else runs the image)
-        if (not self.streams(rows) or x.dtype != F32 or act != "none" or out_dtype != F32 or
-                (out is not None and out.dtype != F32) or
-                (head and (residual or norm is not None or stats_out is not None))):
-            return self.bf16(x, out=out, act=act, residual=residual, out_dtype=out_dtype, splitk=splitk, M=M, norm=norm,
-                             stats_out=stats_out, xpack=xpack, ypack=ypack)
-        import ctypes
-        _check_dev(x)
-        if x.stride(-1) != 1 or x.shape[-1] < self.Kp:
-            raise ValueError(f"PackedLinearW8 input needs unit stride and >= {self.Kp} columns, got {tuple(x.shape)}")
-        if out is None:
-            out = torch.empty(rows, self.N, dtype=F32, device=x.device)
-        if head:
-            _lib.call("fo_gemm_w8_head", x.data_ptr(), x.stride(0), rows, self.Kp, self.q.data_ptr(),
-                      self.scales.data_ptr(), self.ntiles, self.N, out.data_ptr(), out.stride(0), stream(x.device))
-            return out
-        rst, rg, eps, so, gn, yg = _norm_args(norm, stats_out, out)
-        if stats_out is not None and (self.N + 15) // 16 > stats_out.max_groups:
-            raise RuntimeError(f"RowStats holds {stats_out.max_groups} groups per row, fo_gemm_w8 writes "
-                               f"{(self.N + 15) // 16}")
-        sg = ctypes.c_int(0)
-        rt = Runtime.get(x.device)
-        # (x is read as fp32 rows and the output is written row-major only: xpack / ypack stay untouched)
-        entry = "fo_gemm_w8" if rows <= 16 else ("fo_gemm_w8_rows" if rows <= 64 else "fo_gemm_w8_rows128")
-        _lib.call(entry, x.data_ptr(), x.stride(0), rows, self.Kp,
-                  self.q.data_ptr(), self.scales.data_ptr(), self.ntiles, self.N, 1 if self.swiglu else 0, out.data_ptr(), out.stride(0), 1 if residual else 0,
-                  rt.ws.data_ptr(), rt.ws.numel(), rt.counters.data_ptr(), rst, rg, eps, so, gn, yg, ctypes.byref(sg),
-                  stream(x.device))
-        if stats_out is not None:
-            stats_out.groups = sg.value
-        return out
-
-
-def _quant_w8(w, q, scales, base, stride):
-    """fo_quant_w8 of the [N, K] weight w into packed tiles base, base + stride, ... of q / scales; returns the
-    dequantised weight (bf16 [N, K])."""
-    if w.dtype not in (BF16, F32):
-        w = w.float()
-    w = w.contiguous()
-    N, K = w.shape
-    dq = torch.empty(N, K, dtype=BF16, device=w.device)
-    _lib.call("fo_quant_w8", w.data_ptr(), 1 if w.dtype == BF16 else 0, N, K, K, q.data_ptr(), scales.data_ptr(),
-              dq.data_ptr(), base, stride, stream(w.device))
-    return dq
-
-
-def quant_w8(w):
-    """fo_quant_w8 of one [N, K] device weight (bf16 or fp32) -> (packed codes uint8, packed scales fp32 [tiles * 16],
-    dequantised weight bf16 [N, K]); the CPU reference is fo.quant.quantize_rows_e4m3."""
-    N, K = w.shape
-    nt = (N + 15) // 16
-    q = torch.empty(nt * ((K + 63) // 64) * 1024, dtype=torch.uint8, device=w.device)
-    scales = torch.empty(nt * 16, dtype=F32, device=w.device)
-    return q, scales, _quant_w8(w, q, scales, 0, 1)
 
 
 # Which <= 16-row GEMMs of a PackedLinearW4 stream the MXFP4 codes: a GEMM enters only if, at both 8 and 16 rows, its
@@ -514,130 +378,6 @@ W4_POLICY = {"gate_up": True, "down": True}
 W4_ROWS_POLICY = {"gate_up": (2, 3, 4), "down": (2, 3)}
 
 
-class PackedLinearW4:
-    """A bias-free linear layer under weight-only MXFP4 (fo.quant, include/fo_hip.h fo_quant_w4): the weight is
-    W'[n, k] = q[n, k] * 2^e[n, k // 32] with q an e2m1 code.  Holds the packed codes `q`, the E8M0 block `scales` and
-    `bf16`, a PackedLinear over the dequantised weight (W' is exactly a bf16 matrix).  Calls of <= 16 fp32 rows stream
-    the codes (fo_gemm_w4) where W4_POLICY lists this GEMM; every other call forwards to the bf16 image, so both
-    compute X . W'^T.
-
-    w: [N, K] device weight (bf16 or fp32, K % 32 == 0), quantised on the device; swiglu_up as PackedLinear.
-    receive=True: storages allocated, nothing quantised (a replica whose weights arrive by broadcast).
-    stream_rows: 16 (default) or 64.  64 also lets calls of 17..64 fp32 rows stream the codes (fo_gemm_w4_rows), for
-    the row-block counts in `rows_rb`: W4_ROWS_POLICY's for this GEMM, the pairs that measured faster than the image.
-    Setting `stream = True` on an instance sends every <= 16-row call to the codes, `rows_rb = (2, 3, 4)` every call of
-    17 rows up to stream_rows (tests, A/B scripts).
-    kind="head": the Qwen2 output head (see _head_kind): plain, stream_rows 16, no entry in either policy above.
-    kind="attn_o": a Qwen2 attention output projection (attn_weights): plain, stream_rows 16, `stream` from
-    ATTN_POLICY; its <= 16-row calls run fo_gemm_w4's general form with the residual and stats_out."""
-
-    bias = None
-
-    def __init__(self, w, swiglu_up=None, receive=False, stream_rows=16, kind=None):
-        _check_dev(w)
-        if stream_rows not in (16, 64):
-            raise ValueError(f"stream_rows must be 16 or 64, got {stream_rows!r}")
-        self.stream_rows = stream_rows
-        self.kind = _head_kind(kind, swiglu_up, stream_rows)
-        self.rows_rb = () if self.kind else W4_ROWS_POLICY["gate_up" if swiglu_up is not None else "down"]
-        self.N, self.K = w.shape
-        if self.K % 32:
-            raise ValueError(f"PackedLinearW4 needs K % 32 == 0 (the scale block), got K={self.K}")
-        self.Kp = self.K
-        self.swiglu = swiglu_up is not None
-        self.stream = _kind_stream(self.kind, "mxfp4", self.K, bool(W4_POLICY["gate_up" if self.swiglu else "down"]))
-        self.device = w.device
-        self.ntiles = (self.N + 15) // 16 * (2 if self.swiglu else 1)
-        KK = (self.K + 127) // 128
-        self.q = torch.empty(self.ntiles * KK * 1024, dtype=torch.uint8, device=w.device)
-        self.scales = torch.empty(self.ntiles * KK * 64, dtype=torch.uint8, device=w.device)
-        if receive:
-            self.bf16 = PackedLinear(w, swiglu_up=swiglu_up)
-            return
-        dq = [_quant_w4(w, self.q, self.scales, 0, 2 if self.swiglu else 1)]
-        if self.swiglu:
-            dq.append(_quant_w4(swiglu_up, self.q, self.scales, 1, 2))
-        self.bf16 = PackedLinear(dq[0], swiglu_up=dq[1] if self.swiglu else None)
-
-    @property
-    def packed(self):
-        return self.bf16.packed
-
-    @property
-    def nbytes(self):
-        """The bf16 image (what `weight_bytes` has always counted); the codes and scales are fp4_nbytes."""
-        return self.bf16.nbytes
-
-    @property
-    def fp4_nbytes(self):
-        return self.q.numel() + self.scales.numel()
-
-    def streams(self, rows):
-        """Whether a call of `rows` fp32 rows streams the codes (else it runs the bf16 image)."""
-        if rows <= 16:
-            return self.stream
-        return rows <= self.stream_rows and (rows + 15) // 16 in self.rows_rb
-
-    def __call__(self, x, out=None, act="none", residual=False, out_dtype=F32, splitk=0, M=None, norm=None,
-                 stats_out=None, xpack=None, ypack=None):
-        rows = x.shape[0] if M is None else M
-        head = self.kind == "head" and self.K == HEAD_K   # (the head entry is plain: anything else runs the image)
-        if (not self.streams(rows) or x.dtype != F32 or act != "none" or out_dtype != F32 or
-                (out is not None and out.dtype != F32) or
-                (head and (residual or norm is not None or stats_out is not None))):
-            return self.bf16(x, out=out, act=act, residual=residual, out_dtype=out_dtype, splitk=splitk, M=M, norm=norm,
-                             stats_out=stats_out, xpack=xpack, ypack=ypack)
-        import ctypes
-        _check_dev(x)
-        if x.stride(-1) != 1 or x.shape[-1] < self.Kp:
-            raise ValueError(f"PackedLinearW4 input needs unit stride and >= {self.Kp} columns, got {tuple(x.shape)}")
-        if out is None:
-            out = torch.empty(rows, self.N, dtype=F32, device=x.device)
-        if head:
-            _lib.call("fo_gemm_w4_head", x.data_ptr(), x.stride(0), rows, self.Kp, self.q.data_ptr(),
-                      self.scales.data_ptr(), self.ntiles, self.N, out.data_ptr(), out.stride(0), stream(x.device))
-            return out
-        rst, rg, eps, so, gn, yg = _norm_args(norm, stats_out, out)
-        if stats_out is not None and (self.N + 15) // 16 > stats_out.max_groups:
-            raise RuntimeError(f"RowStats holds {stats_out.max_groups} groups per row, fo_gemm_w4 writes "
-                               f"{(self.N + 15) // 16}")
-        sg = ctypes.c_int(0)
-        rt = Runtime.get(x.device)
-        # (x is read as fp32 rows and the output is written row-major only: xpack / ypack stay untouched)
-        _lib.call("fo_gemm_w4" if rows <= 16 else "fo_gemm_w4_rows", x.data_ptr(), x.stride(0), rows, self.Kp,
-                  self.q.data_ptr(), self.scales.data_ptr(), self.ntiles, self.N, 1 if self.swiglu else 0,
-                  out.data_ptr(), out.stride(0), 1 if residual else 0, rt.ws.data_ptr(), rt.ws.numel(),
-                  rt.counters.data_ptr(), rst, rg, eps, so, gn, yg, ctypes.byref(sg), stream(x.device))
-        if stats_out is not None:
-            stats_out.groups = sg.value
-        return out
-
-
-def _quant_w4(w, q, scales, base, stride):
-    """fo_quant_w4 of the [N, K] weight w into packed tiles base, base + stride, ... of q / scales; returns the
-    dequantised weight (bf16 [N, K])."""
-    if w.dtype not in (BF16, F32):
-        w = w.float()
-    w = w.contiguous()
-    N, K = w.shape
-    dq = torch.empty(N, K, dtype=BF16, device=w.device)
-    _lib.call("fo_quant_w4", w.data_ptr(), 1 if w.dtype == BF16 else 0, N, K, K, q.data_ptr(), scales.data_ptr(),
-              dq.data_ptr(), base, stride, stream(w.device))
-    return dq
-
-
-def quant_w4(w, tile_base=0, tile_stride=1):
-    """fo_quant_w4 of one [N, K] device weight (bf16 or fp32) -> (packed codes uint8, packed E8M0 scale bytes uint8,
-    dequantised weight bf16 [N, K]); the CPU reference is fo.quant.quantize_blocks_e2m1.  tile_base / tile_stride place
-    the source tiles in storages sized for them (the other tiles: zero codes, scale byte 127)."""
-    N, K = w.shape
-    nt = tile_base + ((N + 15) // 16 - 1) * tile_stride + 1
-    KK = (K + 127) // 128
-    q = torch.zeros(nt * KK * 1024, dtype=torch.uint8, device=w.device)
-    scales = torch.full((nt * KK * 64,), 127, dtype=torch.uint8, device=w.device)
-    return q, scales, _quant_w4(w, q, scales, tile_base, tile_stride)
-
-
 # Which <= 16-row GEMMs of a PackedLinearW6 stream the MXFP6 codes: W4_POLICY's rule against the bf16 image of the same
 # W' (scripts/gemm_w6_ab.py, profiles/mlp_mxfp6_gemm_ab.txt, DESIGN 5.10).  "head": HEAD_POLICY's entry for this format
 # (fo_gemm_w6_head at K = HEAD_K), by the same rule.  Builder-run, all arms in one process (medians, us, bf16 image / fp8 /
@@ -650,47 +390,110 @@ def quant_w4(w, tile_base=0, tile_stride=1):
 W6_POLICY = {"gate_up": True, "down": True, "head": True}
 
 
-class PackedLinearW6:
-    """A bias-free linear layer under weight-only MXFP6 (fo.quant, include/fo_hip.h fo_quant_w6): the weight is
-    W'[n, k] = q[n, k] * 2^e[n, k // 32] with q an e2m3 code.  Holds the packed codes `q`, the E8M0 block `scales` and
-    `bf16`, a PackedLinear over the dequantised weight (W' is exactly a bf16 matrix).  Calls of <= 16 fp32 rows stream
-    the codes (fo_gemm_w6) where W6_POLICY lists this GEMM; every other call forwards to the bf16 image, so both
-    compute X . W'^T.
+# (format -> (the <= 16-row policy of its MLP GEMMs, its row-stream policy); an FP8 MLP GEMM always streams)
+_MLP_POLICY = {"fp8": ({"gate_up": True, "down": True}, W8_ROWS_POLICY), "mxfp4": (W4_POLICY, W4_ROWS_POLICY),
+               "mxfp6": (W6_POLICY, {})}
+_HEAD_POLICY = {**HEAD_POLICY, "mxfp6": W6_POLICY["head"]}
 
-    w: [N, K] device weight (bf16 or fp32, K % 32 == 0), quantised on the device; swiglu_up as PackedLinear.
-    receive=True: storages allocated, nothing quantised (a replica whose weights arrive by broadcast).
-    stream_rows is 16: this format has no row streams.  Setting `stream = True` on an instance sends every <= 16-row
-    call to the codes (tests, A/B scripts).
-    kind="head": the Qwen2 output head (see _head_kind): plain, `stream` from W6_POLICY["head"] at K = HEAD_K
-    (fo_gemm_w6_head), the general plain form at any other K."""
 
-    bias = None
-    stream_rows = 16
-    rows_rb = ()
+def _policy(fmt, gemm, K):
+    """What the tables above say about one GEMM of a format -> (stream, rows_rb): whether its <= 16-row calls stream
+    the codes, and the row-block counts at which its larger calls do.  gemm: "gate_up", "down", "head", "attn_o" or
+    "qkv"; K matters to the head alone, whose policy is about the entry compiled for HEAD_K."""
+    if gemm == "head":
+        return bool(_HEAD_POLICY[fmt]) if K == HEAD_K else True, ()
+    if gemm in ("attn_o", "qkv"):
+        return bool(ATTN_POLICY[fmt][gemm.replace("attn_", "")]), ()
+    streams, rows = _MLP_POLICY[fmt]
+    return bool(streams[gemm]), rows.get(gemm, ())
 
-    def __init__(self, w, swiglu_up=None, receive=False, kind=None):
-        _check_dev(w)
-        if kind not in (None, "head"):
-            raise ValueError(f"kind must be None or 'head', got {kind!r}")
-        self.kind = _head_kind(kind, swiglu_up, 16)
-        self.N, self.K = w.shape
-        if self.K % 32:
-            raise ValueError(f"PackedLinearW6 needs K % 32 == 0 (the scale block), got K={self.K}")
-        self.Kp = self.K
-        self.swiglu = swiglu_up is not None
-        self.stream = _kind_stream(self.kind, "mxfp6", self.K, bool(W6_POLICY["gate_up" if self.swiglu else "down"]))
-        self.device = w.device
-        self.ntiles = (self.N + 15) // 16 * (2 if self.swiglu else 1)
-        KK = (self.K + 127) // 128
-        self.q = torch.empty(self.ntiles * KK * 1536, dtype=torch.uint8, device=w.device)
-        self.scales = torch.empty(self.ntiles * KK * 64, dtype=torch.uint8, device=w.device)
-        if receive:
-            self.bf16 = PackedLinear(w, swiglu_up=swiglu_up)
-            return
-        dq = [_quant_w6(w, self.q, self.scales, 0, 2 if self.swiglu else 1)]
-        if self.swiglu:
-            dq.append(_quant_w6(swiglu_up, self.q, self.scales, 1, 2))
-        self.bf16 = PackedLinear(dq[0], swiglu_up=dq[1] if self.swiglu else None)
+
+@dataclasses.dataclass(frozen=True)
+class QuantFormat:
+    """What differs between the weight-only formats (fo.quant, include/fo_hip.h): the packed layout and the entries."""
+    step_cols: int       # columns of one code step
+    step_bytes: int      # bytes of one code step of one packed tile
+    e8m0: bool           # scales: E8M0 bytes [tiles * steps * 64], one per 32-column block (so K % 32 == 0), or, when
+    #                      false, fp32 [tiles * 16], one per output row (K is padded to 32 like the image's)
+    stream_rows: tuple   # the stream_rows a layer takes
+    kinds: tuple         # the kinds besides None
+    quant: str           # the quantiser entry
+    gemm: str            # the <= 16-row GEMM entry
+    head: str            # the head entry (K = HEAD_K)
+    rows: dict           # the row-stream entries by band: {most rows: entry}
+    qkv_rope: str        # the fused q|k|v + RoPE entry, or None
+    nbytes_attr: str     # the byte-count attribute a layer of this format answers to
+
+
+QUANT_FORMATS = {
+    "fp8": QuantFormat(64, 1024, False, (16, 64, 128), ("head", "attn_o"), "fo_quant_w8", "fo_gemm_w8",
+                       "fo_gemm_w8_head", {64: "fo_gemm_w8_rows", 128: "fo_gemm_w8_rows128"}, "fo_gemm_w8_qkv_rope",
+                       "fp8_nbytes"),
+    "mxfp4": QuantFormat(128, 1024, True, (16, 64), ("head", "attn_o"), "fo_quant_w4", "fo_gemm_w4", "fo_gemm_w4_head",
+                         {64: "fo_gemm_w4_rows"}, "fo_gemm_w4_qkv_rope", "fp4_nbytes"),
+    "mxfp6": QuantFormat(128, 1536, True, (16,), ("head",), "fo_quant_w6", "fo_gemm_w6", "fo_gemm_w6_head", {}, None,
+                         "fp6_nbytes"),
+}
+
+
+def _code_storage(fm, ntiles, K, device):
+    """Uninitialised (codes, scales) of `ntiles` packed tiles of a K-column weight in format record `fm`."""
+    steps = (K + fm.step_cols - 1) // fm.step_cols
+    q = torch.empty(ntiles * steps * fm.step_bytes, dtype=torch.uint8, device=device)
+    if fm.e8m0:
+        return q, torch.empty(ntiles * steps * 64, dtype=torch.uint8, device=device)
+    return q, torch.empty(ntiles * 16, dtype=F32, device=device)
+
+
+def _quant_codes(fmt, w, q, scales, base, stride, dq=None):
+    """The format's quantiser (fo_quant_w8 / _w4 / _w6) of the [N, K] weight w into packed tiles base, base + stride,
+    ... of q / scales; returns the dequantised weight (bf16 [N, K]; written to `dq`, contiguous, when given)."""
+    if w.dtype not in (BF16, F32):
+        w = w.float()
+    w = w.contiguous()
+    N, K = w.shape
+    if dq is None:
+        dq = torch.empty(N, K, dtype=BF16, device=w.device)
+    _lib.call(QUANT_FORMATS[fmt].quant, w.data_ptr(), 1 if w.dtype == BF16 else 0, N, K, K, q.data_ptr(),
+              scales.data_ptr(), dq.data_ptr(), base, stride, stream(w.device))
+    return dq
+
+
+def quant_weight(w, fmt, tile_base=0, tile_stride=1):
+    """One [N, K] device weight (bf16 or fp32) quantised to `fmt` -> (packed codes uint8, packed scales, dequantised
+    weight bf16 [N, K]).  tile_base / tile_stride place the source tiles in storages sized for them; under the MX
+    formats the other tiles hold zero codes and scale byte 127 (FP8 storages start uninitialised: a caller that
+    places FP8 tiles fills every one)."""
+    N, K = w.shape
+    fm = QUANT_FORMATS[fmt]
+    q, scales = _code_storage(fm, tile_base + ((N + 15) // 16 - 1) * tile_stride + 1, K, w.device)
+    if fm.e8m0:
+        q.zero_()
+        scales.fill_(127)
+    return q, scales, _quant_codes(fmt, w, q, scales, tile_base, tile_stride)
+
+
+def quant_w8(w):
+    """fo_quant_w8 of one [N, K] device weight (bf16 or fp32) -> (packed codes uint8, packed scales fp32 [tiles * 16],
+    dequantised weight bf16 [N, K]); the CPU reference is fo.quant.quantize_rows_e4m3."""
+    return quant_weight(w, "fp8")
+
+
+def quant_w4(w, tile_base=0, tile_stride=1):
+    """fo_quant_w4 of one [N, K] device weight (bf16 or fp32) -> (packed codes uint8, packed E8M0 scale bytes uint8,
+    dequantised weight bf16 [N, K]); the CPU reference is fo.quant.quantize_blocks_e2m1."""
+    return quant_weight(w, "mxfp4", tile_base, tile_stride)
+
+
+def quant_w6(w, tile_base=0, tile_stride=1):
+    """fo_quant_w6 of one [N, K] device weight (bf16 or fp32) -> (packed codes uint8, packed E8M0 scale bytes uint8,
+    dequantised weight bf16 [N, K]); the CPU reference is fo.quant.quantize_blocks_e2m3."""
+    return quant_weight(w, "mxfp6", tile_base, tile_stride)
+
+
+class _QuantCodes:
+    """What PackedLinearQuant and PackedQKVQuant share: packed codes `q` and `scales` of format `fmt` beside `bf16`, a
+    PackedLinear over the dequantised weight W' (exactly a bf16 matrix)."""
 
     @property
     def packed(self):
@@ -698,44 +501,102 @@ class PackedLinearW6:
 
     @property
     def nbytes(self):
-        """The bf16 image (what `weight_bytes` has always counted); the codes and scales are fp6_nbytes."""
+        """The bf16 image (what `weight_bytes` has always counted); the codes and scales are fp8_nbytes / fp4_nbytes /
+        fp6_nbytes."""
         return self.bf16.nbytes
 
-    @property
-    def fp6_nbytes(self):
-        return self.q.numel() + self.scales.numel()
+    def code_nbytes(self, fmt):
+        """The bytes of the codes and scales if this layer is of format `fmt`, else 0."""
+        return self.q.numel() + self.scales.numel() * self.scales.element_size() if self.fmt == fmt else 0
+
+    fp8_nbytes = property(lambda self: self.code_nbytes("fp8"))
+    fp4_nbytes = property(lambda self: self.code_nbytes("mxfp4"))
+    fp6_nbytes = property(lambda self: self.code_nbytes("mxfp6"))
+
+
+class PackedLinearQuant(_QuantCodes):
+    """A bias-free linear layer under a weight-only format of QUANT_FORMATS (fo.quant, include/fo_hip.h): the weight
+    becomes W' = q * 2^e.  Holds the packed codes `q`, the `scales` and `bf16`, a PackedLinear over the dequantised
+    weight.  Calls of fp32 rows that `streams(rows)` admits stream the codes; every other call forwards to the bf16
+    image, so both compute X . W'^T.
+
+    w: [N, K] device weight (bf16 or fp32; K % 32 == 0 under the MX formats), quantised on the device; swiglu_up as
+    PackedLinear.
+    receive=True: storages allocated, nothing quantised (a replica whose weights arrive by broadcast).
+    stream_rows: 16 (default), or a larger band the format has row-stream entries for (FP8 64 and 128, MXFP4 64): calls
+    of 17 rows up to it stream the codes too, for the row-block counts in `rows_rb`.
+    kind: None for an MLP GEMM (gate/up with swiglu_up, else down); "head": the Qwen2 output head, at K = HEAD_K on
+    the format's head entry (plain: a call with a residual, norm or stats_out runs the image), at any other K on the
+    general plain form; "attn_o": a Qwen2 attention output projection (attn_weights), on the general form with the
+    residual and stats_out.  Both are plain projections with stream_rows 16.
+    `stream` and `rows_rb` start as _policy sets them for this GEMM.  Setting `stream = True` on an instance sends
+    every <= 16-row call to the codes, `rows_rb = tuple(range(2, 9))` every call of 17 rows up to stream_rows (tests,
+    A/B scripts)."""
+
+    bias = None
+
+    def __init__(self, w, fmt, swiglu_up=None, receive=False, stream_rows=16, kind=None):
+        _check_dev(w)
+        fm = QUANT_FORMATS[check_format("fmt", fmt, tuple(QUANT_FORMATS))]
+        check_format("stream_rows", stream_rows, fm.stream_rows)
+        check_format("kind", kind, (None,) + fm.kinds)
+        if kind is not None and (swiglu_up is not None or stream_rows != 16):
+            raise ValueError("a head or an attention output is a plain projection with stream_rows=16")
+        self.fmt, self.stream_rows, self.kind = fmt, stream_rows, kind
+        self.N, self.K = w.shape
+        if fm.e8m0 and self.K % 32:
+            raise ValueError(f"{type(self).__name__} needs K % 32 == 0 (the scale block), got K={self.K}")
+        self.Kp = (self.K + 31) // 32 * 32
+        self.swiglu = swiglu_up is not None
+        self.stream, self.rows_rb = _policy(fmt, kind or ("gate_up" if self.swiglu else "down"), self.K)
+        self.device = w.device
+        self.ntiles = (self.N + 15) // 16 * (2 if self.swiglu else 1)
+        # the entries, resolved here: __call__ runs once per GEMM of an eager step
+        self._gemm, self._rows64, self._rows128 = fm.gemm, fm.rows.get(64), fm.rows.get(128)
+        self._head = fm.head if kind == "head" and self.K == HEAD_K else None   # (any other K: the general form)
+        self.q, self.scales = _code_storage(fm, self.ntiles, self.K, w.device)
+        if receive:
+            self.bf16 = PackedLinear(w, swiglu_up=swiglu_up)
+            return
+        dq = [_quant_codes(fmt, w, self.q, self.scales, 0, 2 if self.swiglu else 1)]
+        if self.swiglu:
+            dq.append(_quant_codes(fmt, swiglu_up, self.q, self.scales, 1, 2))
+        self.bf16 = PackedLinear(dq[0], swiglu_up=dq[1] if self.swiglu else None)
 
     def streams(self, rows):
         """Whether a call of `rows` fp32 rows streams the codes (else it runs the bf16 image)."""
-        return rows <= 16 and self.stream
+        if rows <= 16:
+            return self.stream
+        return rows <= self.stream_rows and (rows + 15) // 16 in self.rows_rb
 
     def __call__(self, x, out=None, act="none", residual=False, out_dtype=F32, splitk=0, M=None, norm=None,
                  stats_out=None, xpack=None, ypack=None):
         rows = x.shape[0] if M is None else M
-        head = self.kind == "head" and self.K == HEAD_K   # (the head entry is plain: anything else runs the image)
+        head = self._head   # (the head entry is plain: anything else runs the image)
         if (not self.streams(rows) or x.dtype != F32 or act != "none" or out_dtype != F32 or
                 (out is not None and out.dtype != F32) or
                 (head and (residual or norm is not None or stats_out is not None))):
             return self.bf16(x, out=out, act=act, residual=residual, out_dtype=out_dtype, splitk=splitk, M=M, norm=norm,
                              stats_out=stats_out, xpack=xpack, ypack=ypack)
-        import ctypes
         _check_dev(x)
         if x.stride(-1) != 1 or x.shape[-1] < self.Kp:
-            raise ValueError(f"PackedLinearW6 input needs unit stride and >= {self.Kp} columns, got {tuple(x.shape)}")
+            raise ValueError(f"{type(self).__name__} input needs unit stride and >= {self.Kp} columns, got "
+                             f"{tuple(x.shape)}")
         if out is None:
             out = torch.empty(rows, self.N, dtype=F32, device=x.device)
         if head:
-            _lib.call("fo_gemm_w6_head", x.data_ptr(), x.stride(0), rows, self.Kp, self.q.data_ptr(),
-                      self.scales.data_ptr(), self.ntiles, self.N, out.data_ptr(), out.stride(0), stream(x.device))
+            _lib.call(head, x.data_ptr(), x.stride(0), rows, self.Kp, self.q.data_ptr(), self.scales.data_ptr(),
+                      self.ntiles, self.N, out.data_ptr(), out.stride(0), stream(x.device))
             return out
         rst, rg, eps, so, gn, yg = _norm_args(norm, stats_out, out)
         if stats_out is not None and (self.N + 15) // 16 > stats_out.max_groups:
-            raise RuntimeError(f"RowStats holds {stats_out.max_groups} groups per row, fo_gemm_w6 writes "
+            raise RuntimeError(f"RowStats holds {stats_out.max_groups} groups per row, {self._gemm} writes "
                                f"{(self.N + 15) // 16}")
         sg = ctypes.c_int(0)
         rt = Runtime.get(x.device)
         # (x is read as fp32 rows and the output is written row-major only: xpack / ypack stay untouched)
-        _lib.call("fo_gemm_w6", x.data_ptr(), x.stride(0), rows, self.Kp, self.q.data_ptr(), self.scales.data_ptr(),
+        entry = self._gemm if rows <= 16 else (self._rows64 if rows <= 64 else self._rows128)
+        _lib.call(entry, x.data_ptr(), x.stride(0), rows, self.Kp, self.q.data_ptr(), self.scales.data_ptr(),
                   self.ntiles, self.N, 1 if self.swiglu else 0, out.data_ptr(), out.stride(0), 1 if residual else 0,
                   rt.ws.data_ptr(), rt.ws.numel(), rt.counters.data_ptr(), rst, rg, eps, so, gn, yg, ctypes.byref(sg),
                   stream(x.device))
@@ -744,32 +605,37 @@ class PackedLinearW6:
         return out
 
 
-def _quant_w6(w, q, scales, base, stride):
-    """fo_quant_w6 of the [N, K] weight w into packed tiles base, base + stride, ... of q / scales; returns the
-    dequantised weight (bf16 [N, K])."""
-    if w.dtype not in (BF16, F32):
-        w = w.float()
-    w = w.contiguous()
-    N, K = w.shape
-    dq = torch.empty(N, K, dtype=BF16, device=w.device)
-    _lib.call("fo_quant_w6", w.data_ptr(), 1 if w.dtype == BF16 else 0, N, K, K, q.data_ptr(), scales.data_ptr(),
-              dq.data_ptr(), base, stride, stream(w.device))
-    return dq
+class PackedLinearW8(PackedLinearQuant):
+    """PackedLinearQuant under FP8: W'[n, k] = q[n, k] * 2^e[n] with q an e4m3fn code and one fp32 scale per output
+    row (fo_quant_w8).  <= 16-row calls run fo_gemm_w8; stream_rows 64 adds fo_gemm_w8_rows for 17..64 rows, 128
+    fo_gemm_w8_rows128 for 65..128 rows as well, at W8_ROWS_POLICY's row-block counts."""
+
+    def __init__(self, w, swiglu_up=None, receive=False, stream_rows=16, kind=None):
+        super().__init__(w, "fp8", swiglu_up, receive, stream_rows, kind)
 
 
-def quant_w6(w, tile_base=0, tile_stride=1):
-    """fo_quant_w6 of one [N, K] device weight (bf16 or fp32) -> (packed codes uint8, packed E8M0 scale bytes uint8,
-    dequantised weight bf16 [N, K]); the CPU reference is fo.quant.quantize_blocks_e2m3.  tile_base / tile_stride place
-    the source tiles in storages sized for them (the other tiles: zero codes, scale byte 127)."""
-    N, K = w.shape
-    nt = tile_base + ((N + 15) // 16 - 1) * tile_stride + 1
-    KK = (K + 127) // 128
-    q = torch.zeros(nt * KK * 1536, dtype=torch.uint8, device=w.device)
-    scales = torch.full((nt * KK * 64,), 127, dtype=torch.uint8, device=w.device)
-    return q, scales, _quant_w6(w, q, scales, tile_base, tile_stride)
+class PackedLinearW4(PackedLinearQuant):
+    """PackedLinearQuant under MXFP4: W'[n, k] = q[n, k] * 2^e[n, k // 32] with q an e2m1 code and E8M0 block scales
+    (fo_quant_w4).  <= 16-row calls run fo_gemm_w4 where W4_POLICY lists the GEMM; stream_rows 64 adds fo_gemm_w4_rows
+    for 17..64 rows at W4_ROWS_POLICY's row-block counts."""
+
+    def __init__(self, w, swiglu_up=None, receive=False, stream_rows=16, kind=None):
+        super().__init__(w, "mxfp4", swiglu_up, receive, stream_rows, kind)
 
 
-class PackedQKVQuant:
+class PackedLinearW6(PackedLinearQuant):
+    """PackedLinearQuant under MXFP6: W'[n, k] = q[n, k] * 2^e[n, k // 32] with q an e2m3 code under MXFP4's block
+    scales (fo_quant_w6).  <= 16-row calls run fo_gemm_w6 where W6_POLICY lists the GEMM; the format has no row
+    streams (stream_rows is 16) and no attention output."""
+
+    def __init__(self, w, swiglu_up=None, receive=False, kind=None, stream_rows=16):
+        super().__init__(w, "mxfp6", swiglu_up, receive, stream_rows, kind)
+
+
+QUANT_LINEAR = {"fp8": PackedLinearW8, "mxfp4": PackedLinearW4, "mxfp6": PackedLinearW6}
+
+
+class PackedQKVQuant(_QuantCodes):
     """A fused q|k|v projection under weight-only FP8 or MXFP4 (attn_weights; fmt "fp8" / "mxfp4"): the [N, K] weight,
     N = (H + 2 KVH) * hd, becomes W' = q * 2^e; the bias stays fp32 and untouched.  Holds the packed codes `q` and
     `scales` in the rope-paired tile order (fo.quant.pack_codes_rope: one fo_quant_* call per (head, half) with
@@ -780,8 +646,8 @@ class PackedQKVQuant:
 
     def __init__(self, w, bias, hd, fmt, receive=False):
         _check_dev(w)
-        if fmt not in ("fp8", "mxfp4"):
-            raise ValueError(f"fmt must be 'fp8' or 'mxfp4', got {fmt!r}")
+        check_format("fmt", fmt, tuple(f for f, fm in QUANT_FORMATS.items() if fm.qkv_rope))
+        fm = QUANT_FORMATS[fmt]
         self.fmt, self.rope_hd = fmt, hd
         self.N, self.K = w.shape
         if hd % 32 or self.N % hd or self.K % 32:
@@ -789,13 +655,10 @@ class PackedQKVQuant:
                              f"K={self.K}, hd={hd})")
         self.Kp = self.K
         self.device = w.device
-        self.stream = bool(ATTN_POLICY[fmt]["qkv"])
+        self.stream = _policy(fmt, "qkv", self.K)[0]
         self.ntiles = self.N // 16
-        w8 = fmt == "fp8"
-        KK = (self.K + 63) // 64 if w8 else (self.K + 127) // 128
-        self.q = torch.empty(self.ntiles * KK * 1024, dtype=torch.uint8, device=w.device)
-        self.scales = (torch.empty(self.ntiles * 16, dtype=F32, device=w.device) if w8 else
-                       torch.empty(self.ntiles * KK * 64, dtype=torch.uint8, device=w.device))
+        self._qkv_rope = fm.qkv_rope
+        self.q, self.scales = _code_storage(fm, self.ntiles, self.K, w.device)
         if receive:
             self.bf16 = PackedLinear(w, bias, rope_hd=hd)
             return
@@ -803,35 +666,16 @@ class PackedQKVQuant:
             w = w.float()
         w = w.contiguous()
         dq = torch.empty(self.N, self.K, dtype=BF16, device=w.device)
-        half, es, s = hd // 2, w.element_size(), stream(w.device)
+        half = hd // 2
         for h in range(self.N // hd):
             for p in (0, 1):
                 r0 = h * hd + p * half
-                _lib.call("fo_quant_w8" if w8 else "fo_quant_w4", w.data_ptr() + r0 * self.K * es,
-                          1 if w.dtype == BF16 else 0, half, self.K, self.K, self.q.data_ptr(), self.scales.data_ptr(),
-                          dq.data_ptr() + r0 * self.K * 2, h * (hd // 16) + p, 2, s)
+                _quant_codes(fmt, w[r0:r0 + half], self.q, self.scales, h * (hd // 16) + p, 2, dq[r0:r0 + half])
         self.bf16 = PackedLinear(dq, bias, rope_hd=hd)
 
     @property
     def bias(self):
         return self.bf16.bias
-
-    @property
-    def packed(self):
-        return self.bf16.packed
-
-    @property
-    def nbytes(self):
-        """The bf16 image (what `weight_bytes` has always counted); the codes are fp8_nbytes / fp4_nbytes."""
-        return self.bf16.nbytes
-
-    @property
-    def fp8_nbytes(self):
-        return self.q.numel() + self.scales.numel() * 4 if self.fmt == "fp8" else 0
-
-    @property
-    def fp4_nbytes(self):
-        return self.q.numel() + self.scales.numel() if self.fmt == "mxfp4" else 0
 
     def streams(self, rows):
         """Whether a qkv_rope call of `rows` fp32 rows streams the codes (else it runs the bf16 image)."""
@@ -846,23 +690,27 @@ class PackedQKVQuant:
             raise ValueError(f"qkv_rope input needs unit stride and >= {self.K} columns, got {tuple(x.shape)}")
         rst, rg, eps = _norm_args(norm)[:3]
         # (x is read as fp32 rows: xpack stays untouched)
-        _lib.call("fo_gemm_w8_qkv_rope" if self.fmt == "fp8" else "fo_gemm_w4_qkv_rope", x.data_ptr(), x.stride(0), M,
-                  self.K, self.q.data_ptr(), self.scales.data_ptr(), self.ntiles, self.N, ptr(self.bias), rst, rg, eps,
-                  pos.data_ptr(), slot.data_ptr(), cos_t.data_ptr(), sin_t.data_ptr(), q_out.data_ptr(), kc.data_ptr(),
-                  vc.data_ptr(), H, KVH, self.rope_hd, PS, kv_bytes(kc, vc), stream(x.device))
+        _lib.call(self._qkv_rope, x.data_ptr(), x.stride(0), M, self.K, self.q.data_ptr(), self.scales.data_ptr(),
+                  self.ntiles, self.N, ptr(self.bias), rst, rg, eps, pos.data_ptr(), slot.data_ptr(), cos_t.data_ptr(),
+                  sin_t.data_ptr(), q_out.data_ptr(), kc.data_ptr(), vc.data_ptr(), H, KVH, self.rope_hd, PS,
+                  kv_bytes(kc, vc), stream(x.device))
         return q_out
+
+
+def _launch_counts(getter, kinds):
+    """{kind: launches since the last reset} from one of the library's host-side counter sets (kernels without a
+    FoLaunchKind: a captured graph counts at capture, a refused call not at all)."""
+    buf = (ctypes.c_longlong * len(kinds))()
+    getattr(_lib.load(), getter)(buf, len(kinds))
+    return {k: int(buf[i]) for i, k in enumerate(kinds)}
 
 
 QKV_QUANT_LAUNCH_KINDS = ("w8_qkv_rope", "w4_qkv_rope")
 
 
 def qkv_quant_launch_counts():
-    """{entry: fo_gemm_w8_qkv_rope / fo_gemm_w4_qkv_rope launches issued since the last reset} (host-side counters of
-    their own; a captured graph counts at capture, a refused call not at all)."""
-    import ctypes
-    buf = (ctypes.c_longlong * 2)()
-    _lib.load().fo_gemm_qkv_quant_counts(buf, 2)
-    return {k: int(buf[i]) for i, k in enumerate(QKV_QUANT_LAUNCH_KINDS)}
+    """{entry: fo_gemm_w8_qkv_rope / fo_gemm_w4_qkv_rope launches issued since the last reset}."""
+    return _launch_counts("fo_gemm_qkv_quant_counts", QKV_QUANT_LAUNCH_KINDS)
 
 
 def qkv_quant_launch_counts_reset():
@@ -873,12 +721,8 @@ W4_LAUNCH_KINDS = ("w4", "w4_xs", "w4_sk")
 
 
 def w4_launch_counts():
-    """{form: fo_gemm_w4 launches issued since the last reset} for the general, X-stationary and split-K forms
-    (host-side counters of their own: these kernels have no FoLaunchKind)."""
-    import ctypes
-    buf = (ctypes.c_longlong * 3)()
-    _lib.load().fo_gemm_w4_counts(buf, 3)
-    return {k: int(buf[i]) for i, k in enumerate(W4_LAUNCH_KINDS)}
+    """{form: fo_gemm_w4 launches issued since the last reset} for the general, X-stationary and split-K forms."""
+    return _launch_counts("fo_gemm_w4_counts", W4_LAUNCH_KINDS)
 
 
 def w4_launch_counts_reset():
@@ -890,11 +734,8 @@ W6_LAUNCH_KINDS = ("w6", "w6_xs", "w6_sk", "w6_head")
 
 def w6_launch_counts():
     """{form: launches issued since the last reset} for fo_gemm_w6's general, X-stationary and split-K forms and for
-    fo_gemm_w6_head (host-side counters of their own: these kernels have no FoLaunchKind)."""
-    import ctypes
-    buf = (ctypes.c_longlong * 4)()
-    _lib.load().fo_gemm_w6_counts(buf, 4)
-    return {k: int(buf[i]) for i, k in enumerate(W6_LAUNCH_KINDS)}
+    fo_gemm_w6_head."""
+    return _launch_counts("fo_gemm_w6_counts", W6_LAUNCH_KINDS)
 
 
 def w6_launch_counts_reset():
@@ -905,12 +746,8 @@ HEAD_LAUNCH_KINDS = ("w8_head", "w4_head")
 
 
 def head_launch_counts():
-    """{entry: fo_gemm_w8_head / fo_gemm_w4_head launches issued since the last reset} (host-side counters of their
-    own: these kernels have no FoLaunchKind; a captured graph counts at capture, a refused call not at all)."""
-    import ctypes
-    buf = (ctypes.c_longlong * 2)()
-    _lib.load().fo_gemm_head_counts(buf, 2)
-    return {k: int(buf[i]) for i, k in enumerate(HEAD_LAUNCH_KINDS)}
+    """{entry: fo_gemm_w8_head / fo_gemm_w4_head launches issued since the last reset}."""
+    return _launch_counts("fo_gemm_head_counts", HEAD_LAUNCH_KINDS)
 
 
 def head_launch_counts_reset():

@@ -14,6 +14,31 @@ codes under the same block scales.
 """
 import torch
 
+# ---------------------------------------------------------------- the options and the formats each of them takes
+# The one place the lists live: the engines, the weight sources, the facades and the command lines all check an option
+# through check_format and build their `choices=` from FORMATS.
+WEIGHT_FORMATS = ("fp8", "mxfp4", "mxfp6")      # the weight-only formats (ops.QUANT_FORMATS holds their layouts)
+ATTN_WEIGHT_FORMATS = ("fp8", "mxfp4")          # ... those the fused q|k|v + RoPE GEMM is built for
+FORMATS = {"mlp_weights": ("bf16",) + WEIGHT_FORMATS,
+           "lm_head_weights": ("bf16",) + WEIGHT_FORMATS,
+           "attn_weights": ("bf16",) + ATTN_WEIGHT_FORMATS,
+           "llm_kv": ("fp32", "bf16"),
+           "FakeQuantSource format": WEIGHT_FORMATS,
+           "FakeQuantSource lm_head": (None,) + WEIGHT_FORMATS,
+           "FakeQuantSource attn": (None,) + ATTN_WEIGHT_FORMATS}
+
+
+def check_format(option, value, allowed=None):
+    """Raise ValueError("<option> must be 'a', 'b' or 'c', got <value>") unless `value` is one of `allowed` (default:
+    FORMATS[option]); returns the value."""
+    allowed = FORMATS[option] if allowed is None else allowed
+    if value not in allowed:
+        names = [repr(a) for a in allowed]
+        raise ValueError(f"{option} must be {' or '.join(filter(None, (', '.join(names[:-1]), names[-1])))}, "
+                         f"got {value!r}")
+    return value
+
+
 E4M3_MAX = 448.0
 
 

@@ -14,7 +14,8 @@ import torch
 
 from . import ops
 from .kv import BatchMeta
-from .ops import F32, PackedLinear, PackedLinearW4, PackedLinearW6, PackedLinearW8, PackedQKVQuant
+from .ops import F32, QUANT_LINEAR, PackedLinear, PackedQKVQuant
+from .quant import check_format
 from .weights import ReceiveSource
 
 # FO_ATTN_DENSE=0 passes the item table even for one-token-per-sequence batches (A/B against a
@@ -33,40 +34,25 @@ class Layer:
 
 class DecoderStack:
     def __init__(self, src, prefix, n_layers, D, H, KVH, eps, bias, rope, pool, kv_layer0=0, first_fp16=False,
-                 attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT, mlp_w8=False, mlp_w8_rows=16, mlp_w4=False, mlp_w4_rows=16,
-                 attn_w=None, mlp_w6=False):
-        """attn_w: None, "fp8" or "mxfp4": the q|k|v and o projections under weight-only FP8 / MXFP4
+                 attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT, mlp_weights="bf16", mlp_rows=16, attn_weights="bf16"):
+        """attn_weights: "bf16", "fp8" or "mxfp4": the q|k|v and o projections under weight-only FP8 / MXFP4
         (ops.PackedQKVQuant, and ops.PackedLinearW8 / W4 with kind="attn_o": the four projection weights become
         q * 2^e, the biases stay; forwards of <= 16 rows stream the codes where ops.ATTN_POLICY says so, everything else
         runs the exact bf16 image).  Independent of the MLP options.
-        mlp_w8: gate/up and down under weight-only FP8 (ops.PackedLinearW8: the model's MLP weights become
-        q * 2^e; forwards of <= 16 rows stream the codes, larger ones the exact bf16 image of the same weights).
-        mlp_w8_rows: 16, 64 or 128, PackedLinearW8's stream_rows (64: 17..64-row forwards stream the codes too; 128:
-        65..128-row ones as well).
-        mlp_w4: gate/up and down under weight-only MXFP4 instead (ops.PackedLinearW4: q * 2^e with e2m1 codes and one
-        e per 32-column block; forwards of <= 16 rows stream the codes for the GEMMs of ops.W4_POLICY, everything else
-        runs the exact bf16 image).
-        mlp_w4_rows: 16 or 64, PackedLinearW4's stream_rows (64: 17..64-row forwards stream the codes too, for the
-        pairs of ops.W4_ROWS_POLICY).
-        mlp_w6: gate/up and down under weight-only MXFP6 instead (ops.PackedLinearW6: e2m3 codes under the same block
-        scales; forwards of <= 16 rows stream the codes for the GEMMs of ops.W6_POLICY, everything else runs the exact
-        bf16 image)."""
-        if bool(mlp_w8) + bool(mlp_w4) + bool(mlp_w6) > 1:
-            raise ValueError("mlp_w8, mlp_w4 and mlp_w6 are models of the same weights: pick one"
-                             if mlp_w6 else "mlp_w8 and mlp_w4 are two models of the same weights: pick one")
-        if attn_w not in (None, "fp8", "mxfp4"):
-            raise ValueError(f"attn_w must be None, 'fp8' or 'mxfp4', got {attn_w!r}")
-        self.attn_w = attn_w
-        self.mlp_w4 = bool(mlp_w4)
-        self.mlp_w6 = bool(mlp_w6)
-        self.mlp_w8 = bool(mlp_w8)
-        self.mlp_w8_rows = mlp_w8_rows
-        self.mlp_w4_rows = mlp_w4_rows
+        mlp_weights: "bf16", "fp8", "mxfp4" or "mxfp6": gate/up and down under that weight-only format
+        (ops.PackedLinearW8 / W4 / W6: the model's MLP weights become q * 2^e; forwards of <= 16 rows stream the codes
+        for the GEMMs the format's policy lists, everything else runs the exact bf16 image of the same weights).
+        mlp_rows: the layers' stream_rows: 16, or 64 (FP8, MXFP4: 17..64-row forwards stream the codes too, for the
+        pairs of ops.W8_ROWS_POLICY / W4_ROWS_POLICY) or 128 (FP8: 65..128-row ones as well)."""
+        self.mlp_weights = check_format("mlp_weights", mlp_weights)
+        self.attn_weights = check_format("attn_weights", attn_weights)
+        self.mlp_rows = mlp_rows
         self.n, self.D, self.H, self.KVH, self.hd, self.eps = n_layers, D, H, KVH, D // H, eps
         self.attn_kps = attn_keys_per_split
         self.cos, self.sin = rope
         self.pool, self.kv_layer0, self.first_fp16 = pool, kv_layer0, first_fp16
         self.layers = []
+        recv = isinstance(src, ReceiveSource)   # storages only: the broadcast fills codes, scales and image
         for i in range(n_layers):
             q = f"{prefix}{i}."
             L = Layer()
@@ -79,41 +65,29 @@ class DecoderStack:
             if bias:
                 b = torch.cat([src.get(q + "self_attn.q_proj.bias"), src.get(q + "self_attn.k_proj.bias"),
                                src.get(q + "self_attn.v_proj.bias")])
-            recv = isinstance(src, ReceiveSource)   # storages only: the broadcast fills codes, scales and image
-            if attn_w is None:
+            if attn_weights == "bf16":
                 L.qkv = PackedLinear(torch.cat([wq, wk, wv]), b, rope_hd=self.hd)
             else:
-                L.qkv = PackedQKVQuant(torch.cat([wq, wk, wv]), b, self.hd, attn_w, receive=recv)
+                L.qkv = PackedQKVQuant(torch.cat([wq, wk, wv]), b, self.hd, attn_weights, receive=recv)
             del wq, wk, wv
             wo = src.get(q + "self_attn.o_proj.weight", torch.bfloat16)
-            if attn_w is None:
+            if attn_weights == "bf16":
                 L.o = PackedLinear(wo)
             else:
-                L.o = (PackedLinearW8 if attn_w == "fp8" else PackedLinearW4)(wo, receive=recv, kind="attn_o")
+                L.o = QUANT_LINEAR[attn_weights](wo, receive=recv, kind="attn_o")
             del wo
-            if self.mlp_w8:
-                recv = isinstance(src, ReceiveSource)   # storages only: the broadcast fills codes, scales and image
-                L.gu = PackedLinearW8(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
-                                      swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16), receive=recv,
-                                      stream_rows=mlp_w8_rows)
-                L.down = PackedLinearW8(src.get(q + "mlp.down_proj.weight", torch.bfloat16), receive=recv,
-                                        stream_rows=mlp_w8_rows)
-            elif self.mlp_w4:
-                recv = isinstance(src, ReceiveSource)
-                L.gu = PackedLinearW4(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
-                                      swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16), receive=recv,
-                                      stream_rows=mlp_w4_rows)
-                L.down = PackedLinearW4(src.get(q + "mlp.down_proj.weight", torch.bfloat16), receive=recv,
-                                        stream_rows=mlp_w4_rows)
-            elif self.mlp_w6:
-                recv = isinstance(src, ReceiveSource)
-                L.gu = PackedLinearW6(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
-                                      swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16), receive=recv)
-                L.down = PackedLinearW6(src.get(q + "mlp.down_proj.weight", torch.bfloat16), receive=recv)
-            else:
-                L.gu = PackedLinear(src.get(q + "mlp.gate_proj.weight", torch.bfloat16),
-                                    swiglu_up=src.get(q + "mlp.up_proj.weight", torch.bfloat16))
+            gate = src.get(q + "mlp.gate_proj.weight", torch.bfloat16)
+            up = src.get(q + "mlp.up_proj.weight", torch.bfloat16)
+            if mlp_weights == "bf16":
+                L.gu = PackedLinear(gate, swiglu_up=up)
+                del gate, up
                 L.down = PackedLinear(src.get(q + "mlp.down_proj.weight", torch.bfloat16))
+            else:
+                quantised = QUANT_LINEAR[mlp_weights]
+                L.gu = quantised(gate, swiglu_up=up, receive=recv, stream_rows=mlp_rows)
+                del gate, up
+                L.down = quantised(src.get(q + "mlp.down_proj.weight", torch.bfloat16), receive=recv,
+                                   stream_rows=mlp_rows)
             self.layers.append(L)
         # decode steps (one token per sequence) of an MHA stack with a small o projection -- the AR speech decoder, 14
         # heads of 64, o 896 x 896 -- fuse the attention with the o projection (fo_attention_o: each (session, head)
@@ -129,30 +103,18 @@ class DecoderStack:
     def weight_bytes(self):
         return sum(L.qkv.nbytes + L.o.nbytes + L.gu.nbytes + L.down.nbytes for L in self.layers)
 
-    @property
-    def mlp_fp8_bytes(self):
-        """The FP8 codes and scales held beside the bf16 image (0 without mlp_w8)."""
-        return sum(getattr(L.gu, "fp8_nbytes", 0) + getattr(L.down, "fp8_nbytes", 0) for L in self.layers)
+    def code_bytes(self, part, fmt):
+        """The codes and scales of format `fmt` ("fp8", "mxfp4", "mxfp6") that the layers' `part` -- "mlp" (gate/up and
+        down) or "attn" (q|k|v and o) -- hold beside the bf16 image; 0 where that part is not under that format."""
+        a, b = {"mlp": ("gu", "down"), "attn": ("qkv", "o")}[part]
+        attr = ops.QUANT_FORMATS[fmt].nbytes_attr
+        return sum(getattr(getattr(L, a), attr, 0) + getattr(getattr(L, b), attr, 0) for L in self.layers)
 
-    @property
-    def mlp_fp4_bytes(self):
-        """The MXFP4 codes and scale bytes held beside the bf16 image (0 without mlp_w4)."""
-        return sum(getattr(L.gu, "fp4_nbytes", 0) + getattr(L.down, "fp4_nbytes", 0) for L in self.layers)
-
-    @property
-    def mlp_fp6_bytes(self):
-        """The MXFP6 codes and scale bytes held beside the bf16 image (0 without mlp_w6)."""
-        return sum(getattr(L.gu, "fp6_nbytes", 0) + getattr(L.down, "fp6_nbytes", 0) for L in self.layers)
-
-    @property
-    def attn_fp8_bytes(self):
-        """The FP8 codes and scales of q|k|v and o, held beside the bf16 image (0 without attn_w="fp8")."""
-        return sum(getattr(L.qkv, "fp8_nbytes", 0) + getattr(L.o, "fp8_nbytes", 0) for L in self.layers)
-
-    @property
-    def attn_fp4_bytes(self):
-        """The MXFP4 codes and scale bytes of q|k|v and o, held beside the bf16 image (0 without attn_w="mxfp4")."""
-        return sum(getattr(L.qkv, "fp4_nbytes", 0) + getattr(L.o, "fp4_nbytes", 0) for L in self.layers)
+    mlp_fp8_bytes = property(lambda self: self.code_bytes("mlp", "fp8"))
+    mlp_fp4_bytes = property(lambda self: self.code_bytes("mlp", "mxfp4"))
+    mlp_fp6_bytes = property(lambda self: self.code_bytes("mlp", "mxfp6"))
+    attn_fp8_bytes = property(lambda self: self.code_bytes("attn", "fp8"))
+    attn_fp4_bytes = property(lambda self: self.code_bytes("attn", "mxfp4"))
 
     def workspace(self, T, nsplit, device):
         """Preallocated per-forward buffers for T tokens (graph capture must not allocate)."""
@@ -209,24 +171,22 @@ class DecoderStack:
                   meta.block_table.shape[1] * self.pool.PS <= 4096)
         if fuse_o:
             xgp = attp = None
-        # <= 16 rows under mlp_w8: the FP8 gate/up reads fp32 rows and the FP8 down writes none packed, so nobody
-        # fills or reads the packed x*gamma (the next q|k|v reads the fp32 rows); the o input stays packed
-        # (17..64 rows under mlp_w8_rows=64 likewise, per GEMM: an FP8 gate/up leaves the o's packed x*gamma unread,
-        # an FP8 down fills none for the next q|k|v; 65..128 rows under mlp_w8_rows=128 pack nothing either way)
-        # (mlp_w4 likewise at <= 16 rows and, under mlp_w4_rows=64, at 17..64 rows, per GEMM that streams the MXFP4 codes)
-        # (mlp_w6 likewise at <= 16 rows)
+        # a quantised MLP (mlp_weights), per GEMM that streams its codes at T rows: a streaming gate/up reads fp32 rows,
+        # so the o's packed x*gamma would go unread; a streaming down writes none packed, so the next q|k|v reads the
+        # fp32 rows; the o input stays packed (<= 16 rows, and 17 rows up to mlp_rows for the pairs of the format's
+        # row-stream policy; 65..128 rows pack nothing either way)
         xgp_gu = xgp_qkv = xgp
-        if (self.mlp_w8 or self.mlp_w4 or self.mlp_w6) and self.layers:
+        if self.mlp_weights != "bf16" and self.layers:
             if self.layers[0].gu.streams(T):
                 xgp_gu = None
             if self.layers[0].down.streams(T):
                 xgp_qkv = None
         # (a captured graph's meta carries its capacity, not the replay's keys: graphs keep 128-key splits, which fill
         # the chip at the listen / text shapes, r03c; eager launches -- duplex ticks, prefills -- size them per launch)
-        # attn_w likewise at <= 16 rows, per GEMM that streams the codes: a streaming q|k|v reads the fp32 x*gamma, so the
-        # previous down writes none packed; a streaming o reads the fp32 attention output, so the attention writes none
-        # packed, and writes no packed x*gamma itself, so a bf16 gate/up reads the fp32 rows
-        if self.attn_w and self.layers:
+        # attn_weights likewise at <= 16 rows, per GEMM that streams the codes: a streaming q|k|v reads the fp32
+        # x*gamma, so the previous down writes none packed; a streaming o reads the fp32 attention output, so the
+        # attention writes none packed, and writes no packed x*gamma itself, so a bf16 gate/up reads the fp32 rows
+        if self.attn_weights != "bf16" and self.layers:
             if self.layers[0].qkv.streams(T):
                 xgp_qkv = None
             if self.layers[0].o.streams(T):

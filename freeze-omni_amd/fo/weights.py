@@ -15,6 +15,7 @@ import zlib
 import torch
 
 from . import ops
+from .quant import check_format
 
 _M64 = 0xFFFFFFFFFFFFFFFF
 
@@ -141,12 +142,10 @@ class FakeQuantSource:
             "self_attn.o_proj.weight")
 
     def __init__(self, inner, fmt="fp8", lm_head=None, attn=None):
-        if fmt not in ("fp8", "mxfp4", "mxfp6") and not (fmt is None and (lm_head is not None or attn is not None)):
-            raise ValueError(f"FakeQuantSource format must be 'fp8', 'mxfp4' or 'mxfp6', got {fmt!r}")
-        if lm_head not in (None, "fp8", "mxfp4", "mxfp6"):
-            raise ValueError(f"FakeQuantSource lm_head must be None, 'fp8', 'mxfp4' or 'mxfp6', got {lm_head!r}")
-        if attn not in (None, "fp8", "mxfp4"):
-            raise ValueError(f"FakeQuantSource attn must be None, 'fp8' or 'mxfp4', got {attn!r}")
+        if not (fmt is None and (lm_head is not None or attn is not None)):
+            check_format("FakeQuantSource format", fmt)
+        check_format("FakeQuantSource lm_head", lm_head)
+        check_format("FakeQuantSource attn", attn)
         self.inner, self.fmt, self.lm_head, self.attn = inner, fmt, lm_head, attn
 
     def __contains__(self, name):
@@ -163,5 +162,4 @@ class FakeQuantSource:
             fmt = None
         if fmt is None:
             return self.inner.get(name, dtype)
-        quant = {"mxfp4": ops.quant_w4, "mxfp6": ops.quant_w6}.get(fmt, ops.quant_w8)
-        return quant(self.inner.get(name, torch.bfloat16))[2].to(dtype)
+        return ops.quant_weight(self.inner.get(name, torch.bfloat16), fmt)[2].to(dtype)

@@ -18,6 +18,7 @@ import torch
 from fo import ops
 from fo.engine import FreezeOmniEngine
 from fo.ops import F32, I32
+from fo.quant import check_format
 
 
 class PastKeyValues:
@@ -94,13 +95,15 @@ class AudioLLM:
     def from_model_dir(cls, model_path, llm_path=None, device="cuda:0", train_yaml=None, receive_weights=False,
                        mlp_weights="bf16", mlp_fp8_rows=16, llm_kv="fp32", mlp_mxfp4_rows=16, lm_head_weights="bf16",
                        attn_weights="bf16", **kw):
-        """attn_weights: "bf16", "fp8" or "mxfp4" (FreezeOmniEngine: the Qwen2 q, k, v and o projections under
-        weight-only FP8 or MXFP4, independent of the options below).
-        lm_head_weights: "bf16", "fp8", "mxfp4" or "mxfp6" (FreezeOmniEngine: the Qwen2 output head under weight-only FP8 or
-        MXFP4, independent of the options below).  llm_kv: "fp32" or "bf16" (FreezeOmniEngine: the Qwen2 paged KV's element).  mlp_weights: "bf16", "fp8", "mxfp4" or "mxfp6" (FreezeOmniEngine: the Qwen2 MLP under weight-only FP8 or MXFP4); mlp_fp8_rows: 16,
-        64 or 128 (FreezeOmniEngine: with fp8, 64 lets 17..64-row Qwen2 steps stream the codes too, 128 65..128-row
-        ones as well); mlp_mxfp4_rows: 16 or 64 (FreezeOmniEngine: with mxfp4, 64 lets 17..64-row Qwen2 steps stream
-        the MXFP4 codes too)."""
+        """FreezeOmniEngine's options of the same names, each independent of the others:
+        mlp_weights, lm_head_weights, attn_weights: the Qwen2 MLP, output head and q, k, v, o projections as "bf16" or
+        under one of the option's weight-only formats (fo.quant.FORMATS);
+        mlp_fp8_rows: 16, 64 or 128 (with fp8, 64 lets 17..64-row Qwen2 steps stream the codes too, 128 65..128-row
+        ones as well); mlp_mxfp4_rows: 16 or 64 (with mxfp4, 64 lets 17..64-row Qwen2 steps stream the codes too);
+        llm_kv: "fp32" or "bf16", the Qwen2 paged KV's element."""
+        for opt, value in (("mlp_weights", mlp_weights), ("lm_head_weights", lm_head_weights),
+                           ("attn_weights", attn_weights)):
+            check_format(opt, value)
         return cls(FreezeOmniEngine(model_path, llm_path, device=device, train_yaml=train_yaml,
                                     receive_weights=receive_weights, mlp_weights=mlp_weights,
                                     mlp_fp8_rows=mlp_fp8_rows, llm_kv=llm_kv,

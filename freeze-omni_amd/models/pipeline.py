@@ -18,6 +18,7 @@ import uuid
 
 import torch
 
+from fo.quant import check_format
 from models.audioLLM import AudioLLM
 
 _UPSTREAM_TO_STATUS = {"dialog_sl": "ipu_sl", "dialog_cl": "ipu_cl", "dialog_el": "ipu_el"}
@@ -28,16 +29,17 @@ class inferencePipeline:
         """weights_from: another inferencePipeline (any device) whose frozen weights this replica copies
         instead of reading / generating its own (fo.replica.copy_frozen: the in-process form of the
         start-up broadcast, bin/pool.py's `devices` replicas).
-        args["llm_mlp_weights"]: "bf16" (default), "fp8", "mxfp4" or "mxfp6", the engine's mlp_weights (every replica of a pool takes
-        the same value, so the copied layouts match); args["llm_mlp_fp8_rows"]: 16 (default), 64 or 128, its mlp_fp8_rows;
+        args["llm_mlp_weights"], args["llm_lm_head_weights"], args["llm_attn_weights"]: the engine's mlp_weights,
+        lm_head_weights and attn_weights (the Qwen2 MLP, output head and q, k, v, o projections: "bf16", the default,
+        or one of the option's formats in fo.quant.FORMATS; every replica of a pool takes the same values, so the
+        copied layouts match);
+        args["llm_mlp_fp8_rows"]: 16 (default), 64 or 128, its mlp_fp8_rows;
         args["llm_mlp_mxfp4_rows"]: 16 (default) or 64, its mlp_mxfp4_rows;
-        args["llm_kv"]: "fp32" (default) or "bf16", its llm_kv (the Qwen2 paged KV's element);
-        args["llm_lm_head_weights"]: "bf16" (default), "fp8", "mxfp4" or "mxfp6", its lm_head_weights (the Qwen2 output head; as
-        with llm_mlp_weights, every replica of a pool takes the same value);
-        args["llm_attn_weights"]: "bf16" (default), "fp8" or "mxfp4", its attn_weights (the Qwen2 q, k, v and o
-        projections; every replica of a pool takes the same value)."""
+        args["llm_kv"]: "fp32" (default) or "bf16", its llm_kv (the Qwen2 paged KV's element)."""
         if isinstance(args, argparse.Namespace):
             args = vars(args)
+        for opt in ("mlp_weights", "lm_head_weights", "attn_weights"):
+            check_format(opt, args.get("llm_" + opt) or "bf16")
         self.args = args
         self.device = args.get("device", "cuda:0")
         self.id = uuid.uuid4().hex[:22]

@@ -40,7 +40,7 @@ N = args.forwards or N
 dev = torch.device("cuda:0")
 cfg = configs.get("real")
 src = SynthSource(cfg["seed"], all_shapes(cfg), dev, cfg["overrides"])
-A = LLMEngine(src, cfg["llm"], dev, kv_tokens=KV[0], mlp_w8=True, mlp_w8_rows=BAND)
+A = LLMEngine(src, cfg["llm"], dev, kv_tokens=KV[0], mlp_weights="fp8", mlp_rows=BAND)
 B = LLMEngine(FakeQuantSource(src), cfg["llm"], dev, kv_tokens=KV[1])
 rng = np.random.default_rng(0)
 POLICY = {"gu": A.stack.layers[0].gu.rows_rb, "down": A.stack.layers[0].down.rows_rb}
@@ -51,7 +51,7 @@ def set_rows(eng, rows, forced):
         L.gu.stream_rows = L.down.stream_rows = rows
         L.gu.rows_rb = tuple(range(2, 9)) if forced else POLICY["gu"]
         L.down.rows_rb = tuple(range(2, 9)) if forced else POLICY["down"]
-    eng.stack.mlp_w8_rows = rows
+    eng.stack.mlp_rows = rows
 
 
 arms = {64: {"bf16": (B, None, False), "fp8 rows=16": (A, 16, False), "fp8 rows=64": (A, 64, False)},

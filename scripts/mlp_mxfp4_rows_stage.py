@@ -28,7 +28,7 @@ N = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 dev = torch.device("cuda:0")
 cfg = configs.get("real")
 src = SynthSource(cfg["seed"], all_shapes(cfg), dev, cfg["overrides"])
-A = LLMEngine(src, cfg["llm"], dev, kv_tokens=KV[0], mlp_w4=True, mlp_w4_rows=64)
+A = LLMEngine(src, cfg["llm"], dev, kv_tokens=KV[0], mlp_weights="mxfp4", mlp_rows=64)
 B = LLMEngine(FakeQuantSource(src, "mxfp4"), cfg["llm"], dev, kv_tokens=KV[1])
 rng = np.random.default_rng(0)
 POLICY = {"gu": A.stack.layers[0].gu.rows_rb, "down": A.stack.layers[0].down.rows_rb}
@@ -39,7 +39,7 @@ def set_rows(eng, rows, forced):
         L.gu.stream_rows = L.down.stream_rows = rows
         L.gu.rows_rb = (2, 3, 4) if forced else POLICY["gu"]
         L.down.rows_rb = (2, 3, 4) if forced else POLICY["down"]
-    eng.stack.mlp_w4_rows = rows
+    eng.stack.mlp_rows = rows
 
 
 # name -> (engine, mlp_mxfp4_rows, every pair forced onto the row stream)

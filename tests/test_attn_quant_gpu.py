@@ -188,7 +188,7 @@ def test_12_rows_packed_activation_bookkeeping(dev, fmt, mlp):
     cfg = configs.get("tiny")
     src = SynthSource(cfg["seed"], all_shapes(cfg), dev, cfg["overrides"])
     w4 = mlp == "mxfp4"
-    A = LLMEngine(src, cfg["llm"], dev, kv_tokens=1024, attn_weights=fmt, mlp_w4=w4)
+    A = LLMEngine(src, cfg["llm"], dev, kv_tokens=1024, attn_weights=fmt, mlp_weights="mxfp4" if w4 else "bf16")
     B = LLMEngine(FakeQuantSource(src, "mxfp4" if w4 else None, attn=fmt), cfg["llm"], dev, kv_tokens=1024)
     n = len(A.stack.layers)
     ids = list(range(30, 42))

@@ -122,7 +122,7 @@ class _DeviceWeights(dict):
 
 
 def test_real_geometry_llm_fp8_against_bf16_engine_and_oracle(dev):
-    """The fixture recipe of tests/test_real_qwen2_gpu.py with mlp_w8=True: a 24-row prefill (the bf16 image), then
+    """The fixture recipe of tests/test_real_qwen2_gpu.py with mlp_weights="fp8": a 24-row prefill (the bf16 image), then
     4 steps of 8 rows on fixed ids (gate/up on the X-stationary FP8 stream, down on the split-K form).  Against the
     bf16 engine on the same model: hidden rows and decision-row logits 1e-3 abs + 1e-3 rel; against the numpy oracle
     on the same model: the bounds of tests/test_full_depth_gpu.py."""
@@ -134,7 +134,7 @@ def test_real_geometry_llm_fp8_against_bf16_engine_and_oracle(dev):
     cfg = configs.get("real")
     cfg["llm"]["num_hidden_layers"] = 2
     src = SynthSource(cfg["seed"], all_shapes(cfg), dev, cfg["overrides"])
-    A = LLMEngine(src, cfg["llm"], dev, kv_tokens=4096, page_size=16, mlp_w8=True)
+    A = LLMEngine(src, cfg["llm"], dev, kv_tokens=4096, page_size=16, mlp_weights="fp8")
     model = FakeQuantSource(src)
     B = LLMEngine(model, cfg["llm"], dev, kv_tokens=4096, page_size=16)
     assert A.mlp_fp8_bytes == 2 * (3 * 18944 * 3584 + 4 * (2 * 18944 + 3584)) and B.mlp_fp8_bytes == 0

@@ -55,7 +55,7 @@ class _DeviceWeights(dict):
 
 def test_real_geometry_listen_shapes_against_bf16_engine_and_oracle(dev):
     """Eight sessions; steps of 8 x 9, 12 and 16 tokens (72, 96, 128 rows: a duplex tick that starts a turn, and the
-    grouped listen), then 8 x 4 (the 17..64-row kernels) and 8 x 1 (the <= 16-row ones).  C, with mlp_w8_rows=64, runs
+    grouped listen), then 8 x 4 (the 17..64-row kernels) and 8 x 1 (the <= 16-row ones).  C, with mlp_rows=64, runs
     the same steps without a 65..128-row FP8 launch: its 72-row step (no FP8 history yet) has the bf16 engine's bits."""
     from fo import ops
     from fo.llm import LLMEngine
@@ -65,12 +65,12 @@ def test_real_geometry_listen_shapes_against_bf16_engine_and_oracle(dev):
     cfg = configs.get("real")
     cfg["llm"]["num_hidden_layers"] = 2
     src = SynthSource(cfg["seed"], all_shapes(cfg), dev, cfg["overrides"])
-    A = LLMEngine(src, cfg["llm"], dev, kv_tokens=4096, page_size=16, mlp_w8=True, mlp_w8_rows=128)
+    A = LLMEngine(src, cfg["llm"], dev, kv_tokens=4096, page_size=16, mlp_weights="fp8", mlp_rows=128)
     model = FakeQuantSource(src)
     B = LLMEngine(model, cfg["llm"], dev, kv_tokens=4096, page_size=16)
-    C = LLMEngine(src, cfg["llm"], dev, kv_tokens=4096, page_size=16, mlp_w8=True, mlp_w8_rows=64)
+    C = LLMEngine(src, cfg["llm"], dev, kv_tokens=4096, page_size=16, mlp_weights="fp8", mlp_rows=64)
     _force_if_policy_is_empty(A.stack)
-    assert A.weight_bytes == B.weight_bytes and A.stack.mlp_w8_rows == 128
+    assert A.weight_bytes == B.weight_bytes and A.stack.mlp_rows == 128 and A.stack.mlp_weights == "fp8"
     S = 8
     per = [9, 12, 16, 4, 1]
     rng = np.random.default_rng(8)
@@ -105,7 +105,7 @@ def test_real_geometry_listen_shapes_against_bf16_engine_and_oracle(dev):
     for s, n in enumerate(per):
         _close(got["A"][0][s], got["B"][0][s], f"{S} x {n} rows: hidden rows, FP8 against the bf16 engine")
         _close(got["A"][1][s], got["B"][1][s], f"{S} x {n} rows: logits, FP8 against the bf16 engine")
-    assert torch.equal(got["C"][0][0], got["B"][0][0])   # 72 rows under mlp_w8_rows=64: the same kernels, same image
+    assert torch.equal(got["C"][0][0], got["B"][0][0])   # 72 rows under mlp_rows=64: the same kernels, same image
     # the oracle on the same model, session 0
     W = _DeviceWeights(model)
     q = nets.Qwen2(W, cfg)
@@ -160,7 +160,7 @@ def test_tiny_engine_grouped_listen_streams_128_and_112_rows(dev):
     from fo.engine import FreezeOmniEngine
     path = os.path.join(ROOT, "configs", "tiny")
     A = FreezeOmniEngine(path, device=dev, max_sessions=12, mlp_weights="fp8", mlp_fp8_rows=128)
-    assert A.mlp_fp8_rows == 128 and A.llm.stack.mlp_w8_rows == 128
+    assert A.mlp_fp8_rows == 128 and A.llm.stack.mlp_rows == 128 and A.llm.stack.mlp_weights == "fp8"
     B = FreezeOmniEngine(path, device=dev, max_sessions=12, source=A.src)
     assert B.mlp_fp8_rows == 16
     _force_if_policy_is_empty(A.llm.stack)

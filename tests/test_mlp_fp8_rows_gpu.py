@@ -65,11 +65,11 @@ def test_real_geometry_duplex_shapes_against_bf16_engine_and_oracle(dev):
     cfg = configs.get("real")
     cfg["llm"]["num_hidden_layers"] = 2
     src = SynthSource(cfg["seed"], all_shapes(cfg), dev, cfg["overrides"])
-    A = LLMEngine(src, cfg["llm"], dev, kv_tokens=4096, page_size=16, mlp_w8=True, mlp_w8_rows=64)
+    A = LLMEngine(src, cfg["llm"], dev, kv_tokens=4096, page_size=16, mlp_weights="fp8", mlp_rows=64)
     model = FakeQuantSource(src)
     B = LLMEngine(model, cfg["llm"], dev, kv_tokens=4096, page_size=16)
     _force_if_policy_is_empty(A.stack)
-    assert A.weight_bytes == B.weight_bytes and A.stack.mlp_w8_rows == 64
+    assert A.weight_bytes == B.weight_bytes and A.stack.mlp_rows == 64 and A.stack.mlp_weights == "fp8"
     S = 8
     per = [3, 4, 5, 6, 8, 1, 9]
     rng = np.random.default_rng(8)
@@ -157,7 +157,7 @@ def test_tiny_engine_streams_17_to_64_rows(dev):
     from fo.engine import FreezeOmniEngine
     path = os.path.join(ROOT, "configs", "tiny")
     A = FreezeOmniEngine(path, device=dev, max_sessions=12, mlp_weights="fp8", mlp_fp8_rows=64)
-    assert A.mlp_fp8_rows == 64 and A.llm.stack.mlp_w8_rows == 64
+    assert A.mlp_fp8_rows == 64 and A.llm.stack.mlp_rows == 64 and A.llm.stack.mlp_weights == "fp8"
     B = FreezeOmniEngine(path, device=dev, max_sessions=12, source=A.src)
     assert B.mlp_fp8_rows == 16
     _force_if_policy_is_empty(A.llm.stack)

@@ -142,7 +142,7 @@ def _limit(bound, control):
 
 
 def test_real_geometry_llm_mxfp4_against_bf16_engine_and_oracle(dev):
-    """The fixture recipe of tests/test_real_qwen2_gpu.py with mlp_w4=True: a 24-row prefill (the bf16 image), then
+    """The fixture recipe of tests/test_real_qwen2_gpu.py with mlp_weights="mxfp4": a 24-row prefill (the bf16 image), then
     4 steps of 8 rows on fixed ids (the GEMMs of ops.W4_POLICY on the MXFP4 stream: gate/up X-stationary, down split-K).
     Against the bf16 engine on the same model: hidden rows and decision-row logits 1e-3 abs + 1e-3 rel; against the
     numpy oracle on the same model: the bounds of tests/test_full_depth_gpu.py (last hidden row abs < 1e-2, rel L2 <
@@ -155,7 +155,7 @@ def test_real_geometry_llm_mxfp4_against_bf16_engine_and_oracle(dev):
     cfg = configs.get("real")
     cfg["llm"]["num_hidden_layers"] = 2
     src = SynthSource(cfg["seed"], all_shapes(cfg), dev, cfg["overrides"])
-    A = LLMEngine(src, cfg["llm"], dev, kv_tokens=4096, page_size=16, mlp_w4=True)
+    A = LLMEngine(src, cfg["llm"], dev, kv_tokens=4096, page_size=16, mlp_weights="mxfp4")
     model = FakeQuantSource(src, "mxfp4")
     B = LLMEngine(model, cfg["llm"], dev, kv_tokens=4096, page_size=16)
     assert A.mlp_fp4_bytes == 2 * (3 * 18944 * 3584 // 2 + 3 * 18944 * 3584 // 32)

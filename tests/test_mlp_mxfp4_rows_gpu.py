@@ -51,11 +51,11 @@ def test_real_geometry_duplex_shapes_against_bf16_engine_and_oracle(dev):
     cfg = configs.get("real")
     cfg["llm"]["num_hidden_layers"] = 2
     src = SynthSource(cfg["seed"], all_shapes(cfg), dev, cfg["overrides"])
-    A = LLMEngine(src, cfg["llm"], dev, kv_tokens=4096, page_size=16, mlp_w4=True, mlp_w4_rows=64)
+    A = LLMEngine(src, cfg["llm"], dev, kv_tokens=4096, page_size=16, mlp_weights="mxfp4", mlp_rows=64)
     model = FakeQuantSource(src, "mxfp4")
     B = LLMEngine(model, cfg["llm"], dev, kv_tokens=4096, page_size=16)
     _force_if_policy_is_empty(A.stack)
-    assert A.weight_bytes == B.weight_bytes and A.stack.mlp_w4_rows == 64
+    assert A.weight_bytes == B.weight_bytes and A.stack.mlp_rows == 64 and A.stack.mlp_weights == "mxfp4"
     gu, down = _policy()
     S = 8
     per = [3, 4, 5, 6, 8, 1, 9]
@@ -159,7 +159,8 @@ def test_tiny_engine_streams_17_to_64_rows(dev):
     from fo.engine import FreezeOmniEngine
     path = os.path.join(ROOT, "configs", "tiny")
     A = FreezeOmniEngine(path, device=dev, max_sessions=12, mlp_weights="mxfp4", mlp_mxfp4_rows=64)
-    assert A.mlp_mxfp4_rows == 64 and A.llm.stack.mlp_w4_rows == 64 and A.mlp_fp8_rows == 16
+    assert A.mlp_mxfp4_rows == 64 and A.llm.stack.mlp_rows == 64 and A.mlp_fp8_rows == 16
+    assert A.llm.stack.mlp_weights == "mxfp4"
     B = FreezeOmniEngine(path, device=dev, max_sessions=12, source=A.src)
     assert B.mlp_mxfp4_rows == 16
     _force_if_policy_is_empty(A.llm.stack)
@@ -183,7 +184,7 @@ def test_tiny_engine_streams_17_to_64_rows(dev):
     assert np.array_equal(pa, pa2) and torch.equal(ra, ra2)   # equal state in, equal bits out
     # mlp_weights="mxfp4" alone: no row-stream launch at 20 rows
     C = FreezeOmniEngine(path, device=dev, max_sessions=2, mlp_weights="mxfp4")
-    assert C.mlp_mxfp4_rows == 16 and C.llm.stack.mlp_w4_rows == 16
+    assert C.mlp_mxfp4_rows == 16 and C.llm.stack.mlp_rows == 16 and C.llm.stack.mlp_weights == "mxfp4"
     hc, nc = _prefill(C, ids)
     assert nc == 0 and torch.equal(hc, hb)
 

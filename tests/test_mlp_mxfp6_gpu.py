@@ -165,7 +165,7 @@ def _real(dev):
 
 
 def test_real_geometry_llm_mxfp6_against_bf16_engine_and_oracle(dev):
-    """The fixture recipe of tests/test_real_qwen2_gpu.py with mlp_w6=True: a 24-row prefill (the bf16 image), then
+    """The fixture recipe of tests/test_real_qwen2_gpu.py with mlp_weights="mxfp6": a 24-row prefill (the bf16 image), then
     4 steps of 8 rows on fixed ids (the GEMMs of ops.W6_POLICY on the MXFP6 stream: gate/up X-stationary, down split-K).
     Against the bf16 engine on the same model: hidden rows and decision-row logits 1e-3 abs + 1e-3 rel; against the
     numpy oracle on the same model: the bounds of tests/test_full_depth_gpu.py (last hidden row abs < 1e-2, rel L2 <
@@ -175,7 +175,7 @@ def test_real_geometry_llm_mxfp6_against_bf16_engine_and_oracle(dev):
     from fo.weights import FakeQuantSource
     from oracle import nets
     cfg, src = _real(dev)
-    A = LLMEngine(src, cfg["llm"], dev, kv_tokens=4096, page_size=16, mlp_w6=True)
+    A = LLMEngine(src, cfg["llm"], dev, kv_tokens=4096, page_size=16, mlp_weights="mxfp6")
     model = FakeQuantSource(src, "mxfp6")
     B = LLMEngine(model, cfg["llm"], dev, kv_tokens=4096, page_size=16)
     assert A.mlp_fp6_bytes == 2 * (3 * 18944 * 3584 * 3 // 4 + 3 * 18944 * 3584 // 32)      # 6.25 bits per weight
