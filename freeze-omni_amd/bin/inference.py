@@ -57,7 +57,8 @@ def get_args(argv=None):
     p.add_argument("--llm_mlp_mxfp4_rows", type=int, choices=[16, 64], default=16,
                    help="with --llm_mlp_weights mxfp4: the most rows of a Qwen2 step that stream the MXFP4 codes")
     p.add_argument("--llm_kv", choices=FORMATS["llm_kv"], default="fp32",
-                   help="Qwen2 paged KV cache element: fp32, or bf16 (half the memory and attention bytes)")
+                   help="Qwen2 paged KV cache element: fp32, bf16 (half the memory and attention bytes) or e4m3 (FP8 codes "
+                        "with a scale per token and kv head: 0.26 of the memory, lossy)")
     p.add_argument("--llm_lm_head_weights", choices=FORMATS["lm_head_weights"], default="bf16",
                    help="Qwen2 output head (lm_head) weights: bf16, weight-only FP8 (e4m3 codes x a power of two per "
                         "vocabulary row) or weight-only MXFP4 / MXFP6 (e2m1 / e2m3 codes x a power of two per 32 "

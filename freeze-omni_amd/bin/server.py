@@ -385,7 +385,8 @@ def get_parser():
     p.add_argument("--llm_mlp_mxfp4_rows", type=int, choices=[16, 64], default=None,
                    help="with MXFP4 weights: the most rows of a Qwen2 step that stream the codes (default 16)")
     p.add_argument("--llm_kv", choices=FORMATS["llm_kv"], default=None,
-                   help="Qwen2 paged KV cache element: fp32 (default), or bf16 (half the memory and attention bytes)")
+                   help="Qwen2 paged KV cache element: fp32 (default), bf16 (half the memory and attention bytes) or e4m3 (FP8 "
+                        "codes with a scale per token and kv head: 0.26 of the memory, lossy)")
     p.add_argument("--llm_lm_head_weights", choices=FORMATS["lm_head_weights"], default=None,
                    help="Qwen2 output head (lm_head) weights: bf16 (default), weight-only FP8, MXFP4 or MXFP6")
     p.add_argument("--llm_attn_weights", choices=FORMATS["attn_weights"], default=None,

@@ -17,6 +17,7 @@
 // 2. Encoder rel-pos attention over a per-user ring buffer (models/encoder/attention.py:407-459):
 //    scores = ((q+u).K^T + (q+v).P^T)/sqrt(dk), no mask, no rel_shift; P rows come from a
 //    table of linear_pos(sinusoid(position)) precomputed at load for every position.
+#include <atomic>
 #include <type_traits>
 
 #include "fo_common.h"
@@ -66,9 +67,46 @@ __global__ __launch_bounds__(256) void k_rope_kv_write(const float* qkv, int ldq
   }
 }
 
+// The FP8 KV append: one wave per (token, kv head, K or V).  The q|k|v launch has written the token's K
+// (after bias and RoPE) and V (after bias) as fp32 into a staging cache [kv head][stage row = token][hd]; the wave takes
+// the row's maximum magnitude, the row exponent e of the weight quantiser (e4m3_row_exp), rounds x * 2^-e (exact) to
+// e4m3fn by v_cvt_pk_fp8_f32 -- 4 elements a lane, one 4-byte store -- and stores the scale 2^e.  A non-finite element
+// takes no part in the maximum and becomes the NaN code (sign | 0x7f), never a finite one.  Rows past T and lanes past
+// hd / 4 load and store nothing.
+__global__ __launch_bounds__(256) void k_kv8_append(const float* ksg, const float* vsg, int T, int KVH, int hd,
+                                                    int srows, const int* slot, int PS, unsigned char* kc, float* ks,
+                                                    unsigned char* vc, float* vs) {
+  const int lane = threadIdx.x & 63;
+  const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);   // wave-uniform
+  if (idx >= T * KVH * 2) return;
+  const int isv = idx & 1, kvh = (idx >> 1) % KVH, t = (idx >> 1) / KVH;
+  const bool on = 4 * lane < hd;
+  float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (on) x = *reinterpret_cast<const float4*>((isv ? vsg : ksg) + ((size_t)kvh * srows + t) * hd + 4 * lane);
+  auto mag = [](float v) { return fabsf(v) <= 3.4028234664e38f ? fabsf(v) : 0.f; };   // finite elements only
+  const float amax = wave_max(fmaxf(fmaxf(mag(x.x), mag(x.y)), fmaxf(mag(x.z), mag(x.w))));
+  const int e = e4m3_row_exp(amax);
+  const float inv = pow2f(-e);
+  int c = 0;
+  c = __builtin_amdgcn_cvt_pk_fp8_f32(x.x * inv, x.y * inv, c, false);
+  c = __builtin_amdgcn_cvt_pk_fp8_f32(x.z * inv, x.w * inv, c, true);
+  unsigned u = (unsigned)c;
+  auto nan_code = [&](float v, int sh) {
+    if (!(fabsf(v) <= 3.4028234664e38f)) u = (u & ~(0xffu << sh)) | (((__float_as_uint(v) >> 24) & 0x80u) | 0x7fu) << sh;
+  };
+  nan_code(x.x, 0);
+  nan_code(x.y, 8);
+  nan_code(x.z, 16);
+  nan_code(x.w, 24);
+  const int sl = slot[t];
+  const size_t row = ((size_t)(sl / PS) * KVH + kvh) * PS + sl % PS;
+  if (on) *reinterpret_cast<unsigned*>((isv ? vc : kc) + row * hd + 4 * lane) = u;
+  if (lane == 0) (isv ? vs : ks)[row] = pow2f(e);
+}
+
 #include "fo_attn_rows.h"
 
-template <int HD, int NW = 4, int RT = 1, bool TR = false, bool KV16 = false>
+template <int HD, int NW = 4, int RT = 1, bool TR = false, int KVB = 4>
 __global__ __launch_bounds__(NW * 64) void k_attn_mfma(AttnArgs a) {
   if constexpr (TR) {
 #pragma nounroll
@@ -77,7 +115,7 @@ __global__ __launch_bounds__(NW * 64) void k_attn_mfma(AttnArgs a) {
       __syncthreads();
     }
   } else {
-    attn_rows_body<HD, NW, RT, TR, KV16>(a, blockIdx.x, blockIdx.y, blockIdx.z);
+    attn_rows_body<HD, NW, RT, TR, KVB>(a, blockIdx.x, blockIdx.y, blockIdx.z);
   }
 }
 
@@ -92,6 +130,13 @@ constexpr int DEC_NW = 8, DEC_NT = DEC_NW * 64;  // 8 waves: a key per thread up
 __device__ __forceinline__ float4 bf4_to_f4(uint2 u) {
   return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
                      __uint_as_float(u.y & 0xffff0000u));
+}
+// 4 e4m3fn codes of an FP8 cache times their key's scale (a power of two), widened
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+__device__ __forceinline__ float4 fp8x4_to_f4(unsigned w, float sc) {
+  const f32x2 lo = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w, sc, false);
+  const f32x2 hi = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w, sc, true);
+  return make_float4(lo[0], lo[1], hi[0], hi[1]);
 }
 // The decode body's two sums, spelled out: 4 elements of a key's score, and a lane's 4 outputs += p * v.  Contraction
 // is off, so the fmaf calls are the only fused operations and nothing is fused or regrouped around them -- every
@@ -118,7 +163,11 @@ __device__ __forceinline__ void dec_pv(float4& acc, float p, float4 v) {
 // with which adds depends on how each instantiation's loads vectorise, and the two forms then differ in the last bit.
 // (16-byte V loads would halve the lanes per key and with them the key-to-lane interleave and the order of the
 // cross-lane adds: not taken.)
-template <int HD, bool KV16 = false>
+// KVB 1: e4m3fn codes with one scale 2^e per (key, kv head) (a.ks / a.vs).  A key row is read as 16-byte
+// loads of 16 codes and a lane's 4 elements of a V row as one 4-byte load; the scaled conversion
+// (v_cvt_scalef32_pk_f32_fp8) widens them to the floats code * 2^e -- the widened elements of a bf16 cache holding those
+// values -- and the sums are again dec_dot4 / dec_pv on the same lanes in the same order: the same result bit for bit.
+template <int HD, int KVB = 4>
 __device__ bool attn_decode_row(const AttnArgs& a, const int it, const int h, float* o_s, bool to_lds_only) {
   static_assert(HD % 4 == 0 && HD <= 128, "decode attention: head_dim");
   __shared__ float s_s[DEC_MAXK];
@@ -159,28 +208,47 @@ __device__ bool attn_decode_row(const AttnArgs& a, const int it, const int h, fl
   // one, spills a VGPR)
   constexpr int NPF = HD == 128 ? 14 : (512 / VSTR < 16 ? 512 / VSTR : 16);
   const int sub = lane / LPK, l4 = lane % LPK;
-  using kv_t = std::conditional_t<KV16, bf16_t, float>;
-  using v4_t = std::conditional_t<KV16, uint2, float4>;   // 4 elements of a V row as loaded
+  static_assert(KVB == 4 || KVB == 2 || KVB == 1, "cache element width");
+  constexpr bool KV16 = KVB == 2, KV8 = KVB == 1;
+  using kv_t = std::conditional_t<KV8, unsigned char, std::conditional_t<KV16, bf16_t, float>>;
+  // 4 elements of a V row as loaded
+  using v4_t = std::conditional_t<KV8, unsigned, std::conditional_t<KV16, uint2, float4>>;
   const kv_t* const kcp = reinterpret_cast<const kv_t*>(a.kc);
   const kv_t* const vcp = reinterpret_cast<const kv_t*>(a.vc);
-  auto widen = [](v4_t v) {
-    if constexpr (KV16) return bf4_to_f4(v);
+  const size_t sc_page = (size_t)a.KVH * a.PS, sc_head = (size_t)kvh * a.PS;   // KV8: the scales' [page][kv head][slot]
+  auto widen = [](v4_t v, [[maybe_unused]] float sc) {
+    if constexpr (KV8) return fp8x4_to_f4(v, sc);
+    else if constexpr (KV16) return bf4_to_f4(v);
     else return v;
   };
   v4_t vpf[NPF];
+  float vsc[KV8 ? NPF : 1];   // KV8: the prefetched rows' scales
 #pragma unroll
   for (int i = 0; i < NPF; ++i) {
     const int j = wave * KPW + sub + i * VSTR;
-    if (j < L)
+    if (j < L) {
       vpf[i] = *reinterpret_cast<const v4_t*>(vcp + (size_t)pg_s[j / a.PS] * page_sz + head_off +
                                               (size_t)(j % a.PS) * HD + 4 * l4);
+      if constexpr (KV8) vsc[i] = a.vs[(size_t)pg_s[j / a.PS] * sc_page + sc_head + j % a.PS];
+    }
   }
   auto dot4 = [&](float& s, int d, float4 k4) { s = dec_dot4(s, q_s + d, k4); };
   float mx = -INFINITY;
   for (int j = tid; j < L; j += DEC_NT) {
     const kv_t* kr = kcp + (size_t)pg_s[j / a.PS] * page_sz + head_off + (size_t)(j % a.PS) * HD;
     float s = 0.f;
-    if constexpr (KV16) {
+    if constexpr (KV8) {
+      static_assert(HD % 16 == 0, "decode attention on an FP8 cache: head_dim");
+      const float sc = a.ks[(size_t)pg_s[j / a.PS] * sc_page + sc_head + j % a.PS];
+#pragma unroll
+      for (int d = 0; d < HD; d += 16) {
+        const uint4 k16 = *reinterpret_cast<const uint4*>(kr + d);
+        dot4(s, d, fp8x4_to_f4(k16.x, sc));
+        dot4(s, d + 4, fp8x4_to_f4(k16.y, sc));
+        dot4(s, d + 8, fp8x4_to_f4(k16.z, sc));
+        dot4(s, d + 12, fp8x4_to_f4(k16.w, sc));
+      }
+    } else if constexpr (KV16) {
       static_assert(HD % 8 == 0, "decode attention on a bf16 cache: head_dim");
 #pragma unroll
       for (int d = 0; d < HD; d += 8) {
@@ -213,13 +281,15 @@ __device__ bool attn_decode_row(const AttnArgs& a, const int it, const int h, fl
 #pragma unroll
   for (int i = 0; i < NPF; ++i) {
     const int j = wave * KPW + sub + i * VSTR;
-    if (j < L) pv_add(s_s[j], widen(vpf[i]));
+    if (j < L) pv_add(s_s[j], widen(vpf[i], vsc[KV8 ? i : 0]));
   }
 #pragma unroll 8
   for (int j = wave * KPW + sub + NPF * VSTR; j < L; j += VSTR) {
     const float p = s_s[j];
+    float sc = 0.f;
+    if constexpr (KV8) sc = a.vs[(size_t)pg_s[j / a.PS] * sc_page + sc_head + j % a.PS];
     pv_add(p, widen(*reinterpret_cast<const v4_t*>(vcp + (size_t)pg_s[j / a.PS] * page_sz + head_off +
-                                                   (size_t)(j % a.PS) * HD + 4 * l4)));
+                                                   (size_t)(j % a.PS) * HD + 4 * l4), sc));
   }
   // the wave's keys, lanes LPK apart (lane_xor: no LDS round trip)
   auto xadd = [&](auto off) {
@@ -249,10 +319,11 @@ __device__ bool attn_decode_row(const AttnArgs& a, const int it, const int h, fl
   return true;
 }
 
-template <int HD, bool KV16 = false>
+template <int HD, int KVB = 4>
 __global__ __launch_bounds__(DEC_NT) void k_attn_decode(AttnArgs a) {
+  static_assert(KVB != 1, "no FP8 form: only the AR speech decoder, whose cache stays fp32, takes this launch");
   __shared__ float o_s[HD];
-  attn_decode_row<HD, KV16>(a, blockIdx.x, blockIdx.y, o_s, false);
+  attn_decode_row<HD, KVB>(a, blockIdx.x, blockIdx.y, o_s, false);
 }
 
 // One-token GQA steps (the Qwen2 text step: 7 query heads per kv head, one token per session) on the grid of the
@@ -271,8 +342,9 @@ __global__ __launch_bounds__(DEC_NT) void k_attn_decode(AttnArgs a) {
 // single-row body grows by ~2.4 us per 100 keys (one CU pulls a head's whole K / V), the split body by ~0.4.
 constexpr int GQA_DEC_KEYS = 448;
 static_assert(GQA_DEC_KEYS <= DEC_NT, "the single-row body scores one key per thread");
-// KV16 (a bf16 cache): both bodies' bf16 forms, 44 + 22 KB of LDS; the crossover is kept.
-template <int HD, bool KV16 = false>
+// KVB 2 (a bf16 cache): both bodies' bf16 forms, 44 + 22 KB of LDS; the crossover is kept.
+// KVB 1 (an FP8 cache): both bodies' FP8 forms, the same LDS; the crossover is kept.
+template <int HD, int KVB = 4>
 __global__ __launch_bounds__(DEC_NT) void k_attn_gqa_decode(AttnArgs a) {
   static_assert(DEC_NW == 8, "shares the 8-wave multi-row body's block");
   __shared__ float o_s[HD];
@@ -285,11 +357,11 @@ __global__ __launch_bounds__(DEC_NT) void k_attn_gqa_decode(AttnArgs a) {
       // computed inside the iteration; hoisted out of the loop it costs 54 spilled VGPRs)
       AttnArgs b = a;
       asm volatile("" : "+s"(b.PS));
-      attn_decode_row<HD, KV16>(b, it, kvh * G + g, o_s, false);
+      attn_decode_row<HD, KVB>(b, it, kvh * G + g, o_s, false);
     }
     return;
   }
-  attn_rows_body<HD, DEC_NW, 1, false, KV16>(a, it, kvh, sp);
+  attn_rows_body<HD, DEC_NW, 1, false, KVB>(a, it, kvh, sp);
 }
 
 // The AR speech decoder's attention fused with its o projection, residual add and the next RMSNorm's statistics
@@ -820,6 +892,9 @@ thread_local uint16_t* g_oph = nullptr;
 thread_local uint16_t* g_opl = nullptr;
 thread_local int g_op_cols = 0, g_op_rb = 0;
 
+// the launch counters of the FP8 KV cache (fo_kv8_counts): fo_kv8_append, fo_attention_kv8
+std::atomic<long long> g_kv8_launches[2];
+
 inline int grid_for(long long n) {
   long long g = (n + 255) / 256;
   return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
@@ -924,48 +999,54 @@ int fo_attention(const float* q, int T, const int* items, int n_items, int max_r
                          nsplit, part_ml, part_o, out, tickets, keys_per_split, 4, s);
 }
 
-// fo_attention over a cache of kv_bytes-wide elements (4: fp32, 2: bf16 -- the KV16 instantiations)
-int fo_attention_kv(const float* q, int T, const int* items, int n_items, int max_rows, const int* tok_nvis,
-                    const int* block_table, int maxb, int PS, const void* kc, const void* vc, int H, int KVH, int hd,
-                    float scale, int nsplit, float* part_ml, float* part_o, float* out, int* tickets,
-                    int keys_per_split, int kv_bytes, hipStream_t s) {
+// The attention launch over a cache of kv_bytes-wide elements, for the entry `fn` (its name opens every refusal):
+// 4: fp32, 2: bf16; kv8 (fo_attention_kv8 only): e4m3fn codes with the scales ks / vs
+static int attention_any(const char* fn, const float* q, int T, const int* items, int n_items, int max_rows,
+                         const int* tok_nvis, const int* block_table, int maxb, int PS, const void* kc, const void* vc,
+                         const float* ks, const float* vs, int H, int KVH, int hd, float scale, int nsplit,
+                         float* part_ml, float* part_o, float* out, int* tickets, int keys_per_split, int kv_bytes,
+                         bool kv8, hipStream_t s) {
   uint16_t *oph = g_oph, *opl = g_opl;   // the armed packed output is consumed by this launch whatever happens
   const int op_cols = g_op_cols, op_rb = g_op_rb;
   g_oph = g_opl = nullptr;
   g_op_cols = g_op_rb = 0;
-  FO_REQUIRE(T > 0 && n_items > 0 && KVH > 0 && H % KVH == 0, "fo_attention: bad shape");
+  FO_REQUIRE(T > 0 && n_items > 0 && KVH > 0 && H % KVH == 0, "%s: bad shape", fn);
   FO_REQUIRE(!oph || (op_cols == H * hd && op_rb * 16 >= T),
-             "fo_attention: packed output of %d columns x %d row blocks armed for %d x %d tokens", op_cols, op_rb,
+             "%s: packed output of %d columns x %d row blocks armed for %d x %d tokens", fn, op_cols, op_rb,
              H * hd, T);
-  FO_REQUIRE(items || T % n_items == 0, "fo_attention: items NULL needs T / n_items tokens per item");
-  FO_REQUIRE(hd == 32 || hd == 64 || hd == 128, "fo_attention: head_dim %d unsupported", hd);
-  FO_REQUIRE(kv_bytes == 4 || kv_bytes == 2, "fo_attention: kv_bytes %d (4 = fp32, 2 = bf16)", kv_bytes);
-  const bool kv16 = kv_bytes == 2;
+  FO_REQUIRE(items || T % n_items == 0, "%s: items NULL needs T / n_items tokens per item", fn);
+  FO_REQUIRE(hd == 32 || hd == 64 || hd == 128, "%s: head_dim %d unsupported", fn, hd);
+  FO_REQUIRE(kv8 || kv_bytes == 4 || kv_bytes == 2, "%s: kv_bytes %d (4 = fp32, 2 = bf16)", fn, kv_bytes);
+  FO_REQUIRE(!kv8 || (kc && vc && ks && vs), "%s: NULL codes or scales", fn);
+  FO_REQUIRE(PS > 0, "%s: page size %d", fn, PS);
+  const bool kv16 = kv_bytes != 4;   // (narrow: the forms below exist for an fp32 cache only)
   // forms without a bf16 instantiation are refused by name, never run on the wrong element size
-  FO_REQUIRE(!kv16 || !g_attn_trc, "fo_attention: the traced launches (fo_attention_set_trace) read an fp32 cache only");
+  FO_REQUIRE(!kv16 || !g_attn_trc, "%s: the traced launches (fo_attention_set_trace) read an fp32 cache only", fn);
   FO_REQUIRE(!kv16 || hd != 128 || attn_waves() == 8,
-             "fo_attention: FO_ATTN_NW=4 at head_dim 128 (k_attn_mfma<128, 4>) reads an fp32 cache only");
+             "%s: FO_ATTN_NW=4 at head_dim 128 (k_attn_mfma<128, 4>) reads an fp32 cache only", fn);
   // up to 32 query rows per item on the 8-wave head-dim-128 kernel (two row tiles share every K / V load: a duplex
   // tick's 4 tokens x 7 query heads per kv head read the session's keys once, not twice), 16 elsewhere
   const int rows_max = attn_max_rows(hd);
-  FO_REQUIRE(max_rows >= 1 && max_rows <= rows_max, "fo_attention: %d query rows per item (max %d)", max_rows,
+  FO_REQUIRE(max_rows >= 1 && max_rows <= rows_max, "%s: %d query rows per item (max %d)", fn, max_rows,
              rows_max);
-  FO_REQUIRE(nsplit >= 1 && (nsplit == 1 || (part_ml && part_o)), "fo_attention: bad split buffers");
-  FO_REQUIRE(!tickets || keys_per_split >= 32, "fo_attention: keys_per_split %d < 32", keys_per_split);
+  FO_REQUIRE(nsplit >= 1 && (nsplit == 1 || (part_ml && part_o)), "%s: bad split buffers", fn);
+  FO_REQUIRE(!tickets || keys_per_split >= 32, "%s: keys_per_split %d < 32", fn, keys_per_split);
   // the in-launch merge reads the partials back through 32-bit buffer offsets (ld_sc1)
   FO_REQUIRE(!tickets || nsplit == 1 || (long long)T * H * nsplit * hd * 4 < (1ll << 31),
-             "fo_attention: %d tokens x %d heads x %d splits of partials exceed the merge's 2 GiB window", T, H, nsplit);
+             "%s: %d tokens x %d heads x %d splits of partials exceed the merge's 2 GiB window", fn, T, H, nsplit);
   AttnArgs a{q, items, tok_nvis, block_table, kc, vc, part_ml, part_o, out, H, KVH, PS, maxb, nsplit, scale,
              tickets, keys_per_split, items ? 1 : T / n_items, oph, opl, (T + 15) / 16, g_attn_trc,
-             g_attn_trc && getenv("FO_ATTN_TRACE_REPS") ? atoi(getenv("FO_ATTN_TRACE_REPS")) : 1};
+             g_attn_trc && getenv("FO_ATTN_TRACE_REPS") ? atoi(getenv("FO_ATTN_TRACE_REPS")) : 1, ks, vs};
   const bool dec = max_rows == 1 && (long long)maxb * PS <= DEC_MAXK;
   FO_REQUIRE(!a.oph || (T <= 64 && (dec || nsplit == 1 || tickets)),
-             "fo_attention: packed output needs <= 64 tokens and no combine launch");
+             "%s: packed output needs <= 64 tokens and no combine launch", fn);
+  FO_REQUIRE(!kv8 || !dec, "%s: one query row per item takes the single-row decode form (k_attn_decode), which has no "
+                           "FP8 form (the AR speech decoder's cache stays fp32)", fn);
   if (dec) {  // one query row per (session, head): decode kernel
     dim3 g1(n_items, H);
-    if (kv16 && hd == 128) hipLaunchKernelGGL((k_attn_decode<128, true>), g1, dim3(DEC_NT), 0, s, a);
-    else if (kv16 && hd == 64) hipLaunchKernelGGL((k_attn_decode<64, true>), g1, dim3(DEC_NT), 0, s, a);
-    else if (kv16) hipLaunchKernelGGL((k_attn_decode<32, true>), g1, dim3(DEC_NT), 0, s, a);
+    if (kv16 && hd == 128) hipLaunchKernelGGL((k_attn_decode<128, 2>), g1, dim3(DEC_NT), 0, s, a);
+    else if (kv16 && hd == 64) hipLaunchKernelGGL((k_attn_decode<64, 2>), g1, dim3(DEC_NT), 0, s, a);
+    else if (kv16) hipLaunchKernelGGL((k_attn_decode<32, 2>), g1, dim3(DEC_NT), 0, s, a);
     else if (hd == 128) hipLaunchKernelGGL((k_attn_decode<128>), g1, dim3(DEC_NT), 0, s, a);
     else if (hd == 64) hipLaunchKernelGGL((k_attn_decode<64>), g1, dim3(DEC_NT), 0, s, a);
     else hipLaunchKernelGGL((k_attn_decode<32>), g1, dim3(DEC_NT), 0, s, a);
@@ -981,22 +1062,30 @@ int fo_attention_kv(const float* q, int T, const int* items, int n_items, int ma
   const bool gqa_dec = hd == 128 && KVH < H && G <= 8 && max_rows == G && (items || T == n_items) &&
                        (tickets || nsplit == 1) && attn_waves() == 8 && !a.trc;
   if (gqa_dec) {
-    if (kv16) hipLaunchKernelGGL((k_attn_gqa_decode<128, true>), grid, dim3(DEC_NT), 0, s, a);
+    if (kv8) hipLaunchKernelGGL((k_attn_gqa_decode<128, 1>), grid, dim3(DEC_NT), 0, s, a);
+    else if (kv16) hipLaunchKernelGGL((k_attn_gqa_decode<128, 2>), grid, dim3(DEC_NT), 0, s, a);
     else hipLaunchKernelGGL((k_attn_gqa_decode<128>), grid, dim3(DEC_NT), 0, s, a);
     fo::count_launch(FO_L_ATTN_GQA_DECODE);
+    if (kv8) g_kv8_launches[1].fetch_add(1, std::memory_order_relaxed);
     if (a.oph) fo::count_launch(FO_L_ATTN_OPACK);
     return fo::check_launch("fo_attention/gqa_decode");
   }
   // splits under 64 keys (the text step's short contexts spread over more CUs: a split's K / V arrive at one CU's
   // memory parallelism) take the 2-wave form with 32-key tiles
   const bool small = hd == 128 && tickets && keys_per_split < 64 && max_rows <= 16 && !a.trc;
-  FO_REQUIRE(!kv16 || !small, "fo_attention: keys_per_split %d takes the 2-wave form (k_attn_mfma<128, 2>), which reads "
-                              "an fp32 cache only; a bf16 cache needs >= 64", keys_per_split);
-  if (kv16) {
-    if (hd == 128 && max_rows > 16) hipLaunchKernelGGL((k_attn_mfma<128, 8, 2, false, true>), grid, dim3(512), 0, s, a);
-    else if (hd == 128) hipLaunchKernelGGL((k_attn_mfma<128, 8, 1, false, true>), grid, dim3(512), 0, s, a);
-    else if (hd == 64) hipLaunchKernelGGL((k_attn_mfma<64, 4, 1, false, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_attn_mfma<32, 4, 1, false, true>), grid, dim3(256), 0, s, a);
+  FO_REQUIRE(!kv16 || !small, "%s: keys_per_split %d takes the 2-wave form (k_attn_mfma<128, 2>), which reads "
+                              "an fp32 cache only; a bf16 or FP8 cache needs >= 64", fn, keys_per_split);
+  if (kv8) {
+    if (hd == 128 && max_rows > 16) hipLaunchKernelGGL((k_attn_mfma<128, 8, 2, false, 1>), grid, dim3(512), 0, s, a);
+    else if (hd == 128) hipLaunchKernelGGL((k_attn_mfma<128, 8, 1, false, 1>), grid, dim3(512), 0, s, a);
+    else if (hd == 64) hipLaunchKernelGGL((k_attn_mfma<64, 4, 1, false, 1>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_attn_mfma<32, 4, 1, false, 1>), grid, dim3(256), 0, s, a);
+    g_kv8_launches[1].fetch_add(1, std::memory_order_relaxed);
+  } else if (kv16) {
+    if (hd == 128 && max_rows > 16) hipLaunchKernelGGL((k_attn_mfma<128, 8, 2, false, 2>), grid, dim3(512), 0, s, a);
+    else if (hd == 128) hipLaunchKernelGGL((k_attn_mfma<128, 8, 1, false, 2>), grid, dim3(512), 0, s, a);
+    else if (hd == 64) hipLaunchKernelGGL((k_attn_mfma<64, 4, 1, false, 2>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_attn_mfma<32, 4, 1, false, 2>), grid, dim3(256), 0, s, a);
   } else if (small) hipLaunchKernelGGL((k_attn_mfma<128, 2>), grid, dim3(128), 0, s, a);
   else if (hd == 128 && attn_waves() == 8 && max_rows > 16) hipLaunchKernelGGL((k_attn_mfma<128, 8, 2>), grid, dim3(512), 0, s, a);
   else if (hd == 128 && attn_waves() == 8 && a.trc) hipLaunchKernelGGL((k_attn_mfma<128, 8, 1, true>), grid, dim3(512), 0, s, a);
@@ -1010,6 +1099,51 @@ int fo_attention_kv(const float* q, int T, const int* items, int n_items, int ma
   if (rc || nsplit == 1 || tickets) return rc;
   hipLaunchKernelGGL(k_attn_combine, dim3(T, H), dim3(hd < 64 ? 64 : hd), 0, s, a, hd);
   return fo::check_launch("fo_attention/combine");
+}
+
+int fo_attention_kv(const float* q, int T, const int* items, int n_items, int max_rows, const int* tok_nvis,
+                    const int* block_table, int maxb, int PS, const void* kc, const void* vc, int H, int KVH, int hd,
+                    float scale, int nsplit, float* part_ml, float* part_o, float* out, int* tickets,
+                    int keys_per_split, int kv_bytes, hipStream_t s) {
+  return attention_any("fo_attention", q, T, items, n_items, max_rows, tok_nvis, block_table, maxb, PS, kc, vc, nullptr,
+                       nullptr, H, KVH, hd, scale, nsplit, part_ml, part_o, out, tickets, keys_per_split, kv_bytes, false,
+                       s);
+}
+
+// fo_attention over an FP8 cache: e4m3fn codes kc / vc with the scales ks / vs
+int fo_attention_kv8(const float* q, int T, const int* items, int n_items, int max_rows, const int* tok_nvis,
+                     const int* block_table, int maxb, int PS, const void* kc, const void* vc, int H, int KVH, int hd,
+                     float scale, int nsplit, float* part_ml, float* part_o, float* out, int* tickets,
+                     int keys_per_split, const float* ks, const float* vs, hipStream_t s) {
+  return attention_any("fo_attention_kv8", q, T, items, n_items, max_rows, tok_nvis, block_table, maxb, PS, kc, vc, ks,
+                       vs, H, KVH, hd, scale, nsplit, part_ml, part_o, out, tickets, keys_per_split, 1, true, s);
+}
+
+// The FP8 cache's append (k_kv8_append): the T staged fp32 rows of K and V ([KVH][stage_rows][hd], row t = token t)
+// quantised into the codes kc / vc and scales ks / vs at slot[t] (pages of PS slots).
+int fo_kv8_append(const float* k_stage, const float* v_stage, int T, int KVH, int hd, int stage_rows, const int* slot,
+                  int PS, void* kc, float* ks, void* vc, float* vs, hipStream_t s) {
+  FO_REQUIRE(kc && vc && ks && vs, "fo_kv8_append: NULL codes or scales");
+  FO_REQUIRE(k_stage && v_stage && slot, "fo_kv8_append: NULL staged rows or slot table");
+  FO_REQUIRE(hd == 32 || hd == 64 || hd == 128, "fo_kv8_append: head_dim %d unsupported (32, 64, 128)", hd);
+  FO_REQUIRE(PS > 0 && KVH > 0, "fo_kv8_append: page size %d, %d kv heads", PS, KVH);
+  FO_REQUIRE(T >= 1 && T <= stage_rows, "fo_kv8_append: T=%d outside 1..%d stage rows", T, stage_rows);
+  FO_REQUIRE((long long)T * KVH * 2 < (1ll << 31), "fo_kv8_append: T=%d x %d kv heads", T, KVH);
+  hipLaunchKernelGGL(k_kv8_append, dim3((T * KVH * 2 + 3) / 4), dim3(256), 0, s, k_stage, v_stage, T, KVH, hd,
+                     stage_rows, slot, PS, reinterpret_cast<unsigned char*>(kc), ks,
+                     reinterpret_cast<unsigned char*>(vc), vs);
+  g_kv8_launches[0].fetch_add(1, std::memory_order_relaxed);
+  return fo::check_launch("fo_kv8_append");
+}
+
+int fo_kv8_counts(long long* out, int n) {
+  for (int i = 0; out && i < n && i < 2; ++i) out[i] = g_kv8_launches[i].load(std::memory_order_relaxed);
+  return 2;
+}
+
+int fo_kv8_counts_reset(void) {
+  for (int i = 0; i < 2; ++i) g_kv8_launches[i].store(0, std::memory_order_relaxed);
+  return 0;
 }
 
 int fo_enc_kv_write(const float* k, const float* v, int ldkv, int B, int T, int d, const int* start, const int* len,

@@ -8,7 +8,7 @@ struct AttnArgs {
   const int* items;        // [n_items][3]: sequence, first token, token count (a sequence's tokens are contiguous)
   const int* tok_nvis;     // keys visible to each query token (causal: own cache index + 1; full: all)
   const int* block_table;  // [S][maxb]
-  const void* kc;         // paged K / V, [page][kv head][slot][hd]: fp32, or bf16 (the KV16 instantiations)
+  const void* kc;         // paged K / V, [page][kv head][slot][hd]: fp32, bf16 (KVB 2) or e4m3fn codes (KVB 1)
   const void* vc;
   float* part_ml;  // [T*H][nsplit][2]   (nsplit > 1)
   float* part_o;   // [T*H][nsplit][hd]  (nsplit > 1)
@@ -29,7 +29,33 @@ struct AttnArgs {
                              // ran, loads landed}
   int reps;                  // probe build only: the body runs reps times in a row (FO_ATTN_TRACE_REPS; the stamps
                              // are the last pass's: the same code again, its instructions already fetched)
+  const float* ks;           // KVB 1 only: the codes' scales 2^e, [page][kv head][slot]
+  const float* vs;
 };
+
+// e4m3fn codes -> the bf16 values code * scale (scale a power of two: exact), by gfx950's scaled FP8 conversion
+// (v_cvt_scalef32_pk_bf16_fp8: two codes of a dword's low or high half per instruction)
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+__device__ __forceinline__ void fp8x4_to_bf16(unsigned w, float sc, __bf16* o) {
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, sc, false);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, sc, true);
+  o[0] = a[0]; o[1] = a[1]; o[2] = b[0]; o[3] = b[1];
+}
+__device__ __forceinline__ bf16x8 fp8x8_to_bf16(uint2 w, float sc) {
+  bf16x8 r;
+  __bf16 t[8];
+  fp8x4_to_bf16(w.x, sc, t);
+  fp8x4_to_bf16(w.y, sc, t + 4);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) r[i] = t[i];
+  return r;
+}
+// ... packed as the two dwords of 4 bf16 (the LDS staging of V)
+__device__ __forceinline__ uint2 fp8x4_to_bf16_u2(unsigned w, float sc) {
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, sc, false);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, sc, true);
+  return make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));
+}
 
 constexpr int KT = 64;      // keys per LDS tile (one key per lane in the score phase)
 constexpr int MAXPG = 256;  // pages of one split staged in LDS (fo_attn_nsplit keeps splits <= 4096 keys)
@@ -196,13 +222,21 @@ __device__ void attn_arrive_and_merge(const AttnArgs& a, int it, int kvh, int ns
 // softmax per row with the running max exchanged across the 4 waves through LDS.
 // RT: 16-row query tiles per item (2: up to 32 rows share the K / V loads); TR: the probe build with per-workgroup
 // clocks (a.trc) -- a compile-time switch: the runtime-null hook cost the product launches ~6 % (r05zz vs r05m)
-// KV16: the cache holds bf16 elements.  A lane's K slice of a d chunk is then one 16-byte load that is the
+// KVB: bytes per cache element, 4 (fp32), 2 or 1.
+// KVB 2 (KV16 below): the cache holds bf16 elements.  A lane's K slice of a d chunk is then one 16-byte load that is the
 // MFMA B fragment as it stands, V is staged to LDS as bf16 (half the tile) and read back as 16-bit elements, and each
 // product is two MFMAs, q_hi k + q_lo k and p_hi v + p_lo v: the fp32 form's three with the one against the (zero) low
 // half of k / v dropped, in the same order -- on a cache of bf16-representable values the two forms give the same
 // result bit for bit.  Everything else (tiles, ping-pong, softmax, splits, merge) is shared.
-template <int HD, int NW, int RT = 1, bool TR = false, bool KV16 = false>
+// KVB 1 (KV8): e4m3fn codes with one scale 2^e per (key, kv head) (a.ks / a.vs): the bf16 form with other
+// loads.  A lane's K slice of a d chunk is 8 bytes, decoded with the key's scale straight into the B fragment; V pieces
+// (16 codes; 8 at head_dim 32 on 4 waves, where a tile has only 128 16-byte pieces for 256 threads) are decoded with
+// their key's scale as they are staged into the same bf16 v_s.  code * 2^e is a bf16 value, so from the operands on
+// the launch is the bf16 one: the same result bit for bit as a bf16 cache holding those values.
+template <int HD, int NW, int RT = 1, bool TR = false, int KVB = 4>
 __device__ __forceinline__ void attn_rows_body(const AttnArgs& a, const int it, const int kvh, const int sp) {
+  static_assert(KVB == 4 || KVB == 2 || KVB == 1, "cache element width");
+  constexpr bool KV8 = KVB == 1, KV16 = KVB != 4;   // KV16: bf16 operands (a bf16 cache, or codes decoded to bf16)
   static_assert(!(KV16 && TR), "the probe build reads an fp32 cache");
   constexpr int KT = 16 * NW;           // keys per tile: one 16-key column block per wave
   constexpr int NTH = NW * 64;
@@ -214,12 +248,17 @@ __device__ __forceinline__ void attn_rows_body(const AttnArgs& a, const int it, 
   // columns): the 16 columns of a group share 8 dwords, and the groups, 8 rows = 4 HD + 16 dwords apart, sit 16 banks
   // apart (HD a multiple of 8) -- conflict-free
   constexpr int VP = KV16 ? HD + 4 : HD + 2;
-  constexpr int VL = KT * HD / (KV16 ? 8 : 4) / NTH;  // 16-B pieces of V per thread per tile
-  constexpr int KN = KV16 ? DC : 2 * DC;              // 16-B pieces of a key's row per lane
+  constexpr int VE = KV8 ? (KT * HD / 16 >= NTH ? 16 : 8) : KV16 ? 8 : 4;   // V elements per piece (16 B; KV8: or 8 B)
+  constexpr int VL = KT * HD / VE / NTH;              // pieces of V per thread per tile
+  static_assert(VL >= 1 && VL * VE * NTH == KT * HD, "every thread stages whole pieces of the V tile");
+  constexpr int KN = KV16 ? DC : 2 * DC;              // pieces of a key's row per lane (16 B; KV8: 8 B)
   constexpr bool SC = NW == 8;           // one workgroup per CU: the fence-free split hand-off (attn_arrive_and_merge)
-  using kv_t = std::conditional_t<KV16, bf16_t, float>;
-  using kv16B = std::conditional_t<KV16, uint4, float4>;   // 16 bytes of the cache: 8 bf16 or 4 floats
-  __shared__ kv_t v_s[KT][VP];
+  using kv_t = std::conditional_t<KV8, unsigned char, std::conditional_t<KV16, bf16_t, float>>;   // a cache element
+  using vs_t = std::conditional_t<KV16, bf16_t, float>;    // ... and V's element in LDS
+  using kv16B = std::conditional_t<KV16, uint4, float4>;   // 16 bytes of the cache: 16 codes, 8 bf16 or 4 floats
+  using kp_t = std::conditional_t<KV8, uint2, kv16B>;      // a lane's piece of its key's row
+  using vp_t = std::conditional_t<KV8 && VE == 8, uint2, kv16B>;   // a thread's piece of the V tile
+  __shared__ vs_t v_s[KT][VP];
   // (at least 64 + 4 wide: attn_arrive_and_merge reuses it as its [16][64 + 4] weight table)
   __shared__ float p_s[16 * RT][(KT > 64 ? KT : 64) + 4];
   __shared__ float mx_s[NW][16 * RT];
@@ -350,17 +389,21 @@ __device__ __forceinline__ void attn_rows_body(const AttnArgs& a, const int it, 
   const size_t page_sz = (size_t)a.KVH * a.PS * HD;
   const kv_t* const kcp = reinterpret_cast<const kv_t*>(a.kc);
   const kv_t* const vcp = reinterpret_cast<const kv_t*>(a.vc);
-  constexpr int VE = KV16 ? 8 : 4;                 // V elements per 16-B piece
-  kv16B kA[KN], vA[VL], kB[KN], vB[VL];            // two tiles' K / V in flight (ping-pong)
+  kp_t kA[KN], kB[KN];                             // two tiles' K / V in flight (ping-pong)
+  vp_t vA[VL], vB[VL];
+  // KV8: this lane's key's scale and each V piece's key's scale ride with them
+  float ksA = 0.f, ksB = 0.f, vsA[KV8 ? VL : 1], vsB[KV8 ? VL : 1];
+  const size_t sc_head = (size_t)kvh * a.PS, sc_page = (size_t)a.KVH * a.PS;
   // K: this lane's key (16 per wave) x its 8-wide d slices; V: cooperative 16-B rows for LDS
-#define FO_ATTN_LOAD(kreg, vreg, K0)                                                                      \
+#define FO_ATTN_LOAD(kreg, vreg, kscl, vscl, K0)                                                          \
   {                                                                                                       \
     const int pk = min((K0) + 16 * wave + col, c1 - 1);                                                   \
     const kv_t* kr = kcp + (size_t)pg_s[pk / a.PS - pb] * page_sz + head_off + (size_t)(pk % a.PS) * HD   \
                      + 8 * grp;                                                                           \
+    if constexpr (KV8) kscl = a.ks[(size_t)pg_s[pk / a.PS - pb] * sc_page + sc_head + pk % a.PS];         \
     _Pragma("unroll") for (int c = 0; c < DC; ++c) {                                                      \
       if constexpr (KV16) {                                                                               \
-        kreg[c] = *reinterpret_cast<const kv16B*>(kr + 32 * c);                                           \
+        kreg[c] = *reinterpret_cast<const kp_t*>(kr + 32 * c);                                            \
       } else {                                                                                            \
         kreg[2 * c] = *reinterpret_cast<const kv16B*>(kr + 32 * c);                                       \
         kreg[2 * c + 1] = *reinterpret_cast<const kv16B*>(kr + 32 * c + 4);                               \
@@ -369,8 +412,9 @@ __device__ __forceinline__ void attn_rows_body(const AttnArgs& a, const int it, 
     _Pragma("unroll") for (int i = 0; i < VL; ++i) {                                                      \
       const int e = tid + NTH * i, j = e / (HD / VE), dv = e % (HD / VE);                                 \
       const int pv = min((K0) + j, c1 - 1);                                                               \
-      vreg[i] = *reinterpret_cast<const kv16B*>(vcp + (size_t)pg_s[pv / a.PS - pb] * page_sz + head_off   \
-                                                + (size_t)(pv % a.PS) * HD + dv * VE);                    \
+      vreg[i] = *reinterpret_cast<const vp_t*>(vcp + (size_t)pg_s[pv / a.PS - pb] * page_sz + head_off    \
+                                               + (size_t)(pv % a.PS) * HD + dv * VE);                     \
+      if constexpr (KV8) vscl[i] = a.vs[(size_t)pg_s[pv / a.PS - pb] * sc_page + sc_head + pv % a.PS];    \
     }                                                                                                     \
   }
 
@@ -386,18 +430,25 @@ __device__ __forceinline__ void attn_rows_body(const AttnArgs& a, const int it, 
 
   // tile t's loads are issued while tile t - 1 computes and two tiles are in flight from the start, so a
   // 256-key split waits for one round of memory, not two
-  FO_ATTN_LOAD(kA, vA, c0)
-  if (c0 + KT < c1) FO_ATTN_LOAD(kB, vB, c0 + KT)
+  FO_ATTN_LOAD(kA, vA, ksA, vsA, c0)
+  if (c0 + KT < c1) FO_ATTN_LOAD(kB, vB, ksB, vsB, c0 + KT)
   if constexpr (TR) {   // probe: when this wave's first tiles have landed
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (tr && tid == 0) tr[6] = wall_clock64();
   }
-  auto tile = [&](kv16B (&kreg)[KN], kv16B (&vreg)[VL], const int k0) {
+  auto tile = [&](kp_t (&kreg)[KN], vp_t (&vreg)[VL], float& kscl, float (&vscl)[KV8 ? VL : 1], const int k0) {
     __syncthreads();  // the previous tile's p_s / v_s readers are done
 #pragma unroll
     for (int i = 0; i < VL; ++i) {
       const int e = tid + NTH * i, j = e / (HD / VE), dv = e % (HD / VE);
-      if constexpr (KV16) {
+      if constexpr (KV8) {
+        *reinterpret_cast<uint2*>(&v_s[j][dv * VE]) = fp8x4_to_bf16_u2(vreg[i].x, vscl[i]);
+        *reinterpret_cast<uint2*>(&v_s[j][dv * VE + 4]) = fp8x4_to_bf16_u2(vreg[i].y, vscl[i]);
+        if constexpr (VE == 16) {
+          *reinterpret_cast<uint2*>(&v_s[j][dv * VE + 8]) = fp8x4_to_bf16_u2(vreg[i].z, vscl[i]);
+          *reinterpret_cast<uint2*>(&v_s[j][dv * VE + 12]) = fp8x4_to_bf16_u2(vreg[i].w, vscl[i]);
+        }
+      } else if constexpr (KV16) {
         *reinterpret_cast<uint2*>(&v_s[j][dv * 8]) = make_uint2(vreg[i].x, vreg[i].y);
         *reinterpret_cast<uint2*>(&v_s[j][dv * 8 + 4]) = make_uint2(vreg[i].z, vreg[i].w);
       } else {
@@ -408,7 +459,9 @@ __device__ __forceinline__ void attn_rows_body(const AttnArgs& a, const int it, 
     bf16x8 kh[DC], kl[KV16 ? 1 : DC];   // (bf16: the loaded 16 bytes are the fragment; no low half)
 #pragma unroll
     for (int c = 0; c < DC; ++c) {
-      if constexpr (KV16) {
+      if constexpr (KV8) {
+        kh[c] = fp8x8_to_bf16(kreg[c], kscl);
+      } else if constexpr (KV16) {
         kh[c] = __builtin_bit_cast(bf16x8, kreg[c]);
       } else {
         const float f[8] = {kreg[2 * c].x, kreg[2 * c].y, kreg[2 * c].z, kreg[2 * c].w,
@@ -417,7 +470,7 @@ __device__ __forceinline__ void attn_rows_body(const AttnArgs& a, const int it, 
       }
     }
     if (tr && tid == 0 && k0 == c0) tr[7] = wall_clock64();
-    if (k0 + 2 * KT < c1) FO_ATTN_LOAD(kreg, vreg, k0 + 2 * KT)
+    if (k0 + 2 * KT < c1) FO_ATTN_LOAD(kreg, vreg, kscl, vscl, k0 + 2 * KT)
     // S[r = 16 rt + 4 grp + i][key = k0 + 16 wave + col]
     f32x4 s[RT];
 #pragma unroll
@@ -513,8 +566,8 @@ __device__ __forceinline__ void attn_rows_body(const AttnArgs& a, const int it, 
     if (tr && tid == 0 && k0 == c0) tr[10] = wall_clock64();
   };
   for (int k0 = c0; k0 < c1; k0 += 2 * KT) {
-    tile(kA, vA, k0);
-    if (k0 + KT < c1) tile(kB, vB, k0 + KT);
+    tile(kA, vA, ksA, vsA, k0);
+    if (k0 + KT < c1) tile(kB, vB, ksB, vsB, k0 + KT);
   }
 #undef FO_ATTN_LOAD
   if (tr && tid == 0) tr[2] = wall_clock64();

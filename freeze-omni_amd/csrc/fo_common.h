@@ -93,6 +93,16 @@ __device__ __forceinline__ bf16_t f2bf(float f) {
   u += 0x7fffu + ((u >> 16) & 1u);
   return (bf16_t)(u >> 16);
 }
+// The e4m3 row exponent (fo/quant.py row_exponents): the smallest integer e with amax * 2^-e <= 448 = 1.75 * 2^8, read
+// from the float's exponent and mantissa, at least -126 (2^e and 2^-e stay normal floats); 0 for amax == 0.  Shared by
+// the weight quantiser (k_quant_w8) and the FP8 KV append (k_kv8_append).
+__device__ __forceinline__ int e4m3_row_exp(float amax) {
+  if (!(amax > 0.f)) return 0;
+  const unsigned b = __float_as_uint(amax);
+  const int e = (int)(b >> 23) - 127 - 8 + ((b & 0x7fffffu) > 0x600000u ? 1 : 0);
+  return max(e, -126);
+}
+__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }   // -126 <= e <= 127
 __host__ __device__ __forceinline__ float round_f16(float f) {
   return (float)(_Float16)f;
 }

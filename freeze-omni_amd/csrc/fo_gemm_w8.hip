@@ -624,13 +624,8 @@ __global__ __launch_bounds__(256) void k_quant_w8(const void* W, int src_bf16, i
   if (lane == 0) red[threadIdx.x >> 6] = amax;
   __syncthreads();
   amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  int e = 0;
-  if (amax > 0.f) {
-    const unsigned b = __float_as_uint(amax);
-    e = (int)(b >> 23) - 127 - 8 + ((b & 0x7fffffu) > 0x600000u ? 1 : 0);
-    e = max(e, -126);   // 2^e and 2^-e stay normal floats
-  }
-  const float s = __uint_as_float((unsigned)(e + 127) << 23), inv = __uint_as_float((unsigned)(127 - e) << 23);
+  const int e = e4m3_row_exp(amax);
+  const float s = pow2f(e), inv = pow2f(-e);
   const size_t dt = (size_t)tile_base + (size_t)(n >> 4) * tile_stride;
   if (threadIdx.x == 0) scale[dt * 16 + (n & 15)] = s;
   for (int g = threadIdx.x; g < KK * 8; g += 256) {   // group g: columns 8 g .. + 8

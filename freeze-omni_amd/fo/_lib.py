@@ -156,6 +156,11 @@ _SIGS = {
                                     c_int, c_int, c_vp]),
     "fo_attention_kv": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int,
                                 c_int, c_float, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
+    "fo_attention_kv8": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int,
+                                 c_int, c_float, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "fo_kv8_append": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "fo_kv8_counts": (c_int, [ctypes.POINTER(c_ll), c_int]),
+    "fo_kv8_counts_reset": (c_int, []),
     "fo_attention_o_kv": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int, c_float, c_vp,
                                   c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp]),
     "fo_attention": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int,

@@ -82,10 +82,13 @@ class FreezeOmniEngine:
         mlp_weights, mlp_*_rows and llm_kv.  Calls of <= 16 rows (the captured TextGraph, the eager text_step, LLMEngine.logits)
         stream the codes where ops.HEAD_POLICY says so; more rows run the exact bf16 image.  `src` serves the
         dequantised head (FakeQuantSource(..., lm_head=...)).
-        llm_kv: "fp32" (default) or "bf16": the element of the Qwen2 stack's paged KV.  "bf16" is the
+        llm_kv: "fp32" (default), "bf16" or "e4m3": the element of the Qwen2 stack's paged KV.  "bf16" is the
         cache the reference keeps: K after bias and RoPE and V after bias are rounded once to bf16 as they are
         appended, stored as 2-byte elements and read as such by the attention; llm_kv_tokens keeps meaning tokens,
-        so the pool is half the bytes.  The speech decoder's pool, the encoder rings and the adapter caches stay fp32.
+        so the pool is half the bytes.  "e4m3" (DESIGN §5.11): e4m3fn codes with one power-of-two scale per (token,
+        kv head), 0.26 of the fp32 bytes; lossy (about 2.7 % per element), quantised by one small launch per layer
+        after the q|k|v projection and decoded in registers by the attention.  It combines freely with the weight
+        options.  The speech decoder's pool, the encoder rings and the adapter caches stay fp32.
         mlp_weights: "bf16" (default) or "fp8": the Qwen2 gate/up/down weights under weight-only FP8 (e4m3fn codes
         times a power of two per output row, DESIGN: `mlp_weights`); Qwen2 steps of <= 16 rows then stream the codes.
         `src` serves the dequantised weights (fo.weights.FakeQuantSource), so an oracle or a second engine can be

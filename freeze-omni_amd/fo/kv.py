@@ -4,7 +4,8 @@ The reference keeps one transformers DynamicCache per session and grows it with 
 chunk (models/audioLLM.py:416-419, models/decoder/decoder.py:321); sessions deep-copy the system
 prompt cache (bin/dialog_state_pred.py:110,218).  Here every layer's K/V live in one device pool of
 fixed-size pages ([layer][page][kv_head][slot][hd]; fp32, or bf16 for the Qwen2 stack's opt-in
-`llm_kv="bf16"`: the same layout in 2-byte elements).  A sequence is a block list; `fork()`
+`llm_kv="bf16"`: the same layout in 2-byte elements; or e4m3fn codes for `llm_kv="e4m3"`: one byte per
+element plus one fp32 scale per (token, kv head)).  A sequence is a block list; `fork()`
 shares full pages copy-on-write (refcounts), so N sessions forked from one system prompt store it
 once, and appending never moves existing keys.
 """
@@ -19,15 +20,21 @@ from . import ops
 
 class KVPool:
     def __init__(self, n_layers, n_kv, hd, n_pages, page_size, device, dtype=torch.float32):
-        """dtype: torch.float32 (default) or torch.bfloat16 -- the element the append kernels store and the attention
-        kernels read (they take the layout from these tensors, ops.kv_bytes)."""
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError(f"KVPool dtype must be torch.float32 or torch.bfloat16, got {dtype}")
+        """dtype: torch.float32 (default), torch.bfloat16 or torch.float8_e4m3fn -- the element the append kernels store
+        and the attention kernels read (they take the layout from these tensors, ops.kv_bytes).  An fp8 pool also holds
+        ks / vs, the fp32 scales 2^e of its codes, [layer][page][kv_head][slot] (None on the other pools)."""
+        if dtype not in (torch.float32, torch.bfloat16, torch.float8_e4m3fn):
+            raise ValueError(f"KVPool dtype must be torch.float32, torch.bfloat16 or torch.float8_e4m3fn, got {dtype}")
         self.n_layers, self.n_kv, self.hd, self.PS = n_layers, n_kv, hd, page_size
         self.n_pages = n_pages
         self.dtype = dtype
         self.k = torch.empty(n_layers, n_pages, n_kv, page_size, hd, dtype=dtype, device=device)
         self.v = torch.empty_like(self.k)
+        self.fp8 = dtype == torch.float8_e4m3fn
+        self.ks = self.vs = None
+        if self.fp8:
+            self.ks = torch.empty(n_layers, n_pages, n_kv, page_size, dtype=torch.float32, device=device)
+            self.vs = torch.empty_like(self.ks)
         self.ref = np.zeros(n_pages, dtype=np.int32)
         self.free = list(range(n_pages - 1, -1, -1))
         self.device = torch.device(device)
@@ -37,7 +44,8 @@ class KVPool:
 
     @property
     def bytes_per_token(self):
-        return self.n_layers * self.n_kv * self.hd * self.k.element_size() * 2
+        per_row = self.hd * self.k.element_size() + (self.ks.element_size() if self.fp8 else 0)   # (+ the row's scale)
+        return self.n_layers * self.n_kv * per_row * 2
 
     def alloc(self):
         with self.lock:
@@ -82,6 +90,9 @@ class KVPool:
     def copy_page(self, src, dst):
         self.k[:, dst].copy_(self.k[:, src])
         self.v[:, dst].copy_(self.v[:, src])
+        if self.fp8:
+            self.ks[:, dst].copy_(self.ks[:, src])
+            self.vs[:, dst].copy_(self.vs[:, src])
 
     def pages_in_use(self):
         return self.n_pages - len(self.free)

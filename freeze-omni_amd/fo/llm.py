@@ -28,10 +28,12 @@ class LLMEngine:
         MXFP6) says so, every other call runs the exact bf16 image.  embed_tokens is never quantised.  Over a
         ReceiveSource the head's storages are allocated and nothing is quantised (a replica whose weights arrive by
         broadcast fills codes, scales and image).
-        kv_dtype: "fp32" (default) or "bf16" -- the paged KV's element: K / V rounded once to bf16
-        as they are appended and read as bf16 by the attention; kv_tokens keeps meaning tokens (half the bytes)."""
-        if kv_dtype not in ("fp32", "bf16"):
-            raise ValueError(f'kv_dtype must be "fp32" or "bf16", got {kv_dtype!r}')
+        kv_dtype: "fp32" (default), "bf16" or "e4m3" -- the paged KV's element.  "bf16" (DESIGN §5.6): K / V rounded
+        once to bf16 as they are appended and read as bf16 by the attention; kv_tokens keeps meaning tokens (half the
+        bytes).  "e4m3" (DESIGN §5.11): e4m3fn codes with one power-of-two scale per (token, kv head), quantised by a
+        launch of its own after the q|k|v projection and decoded in registers by the attention (0.26 of the bytes)."""
+        if kv_dtype not in ("fp32", "bf16", "e4m3"):
+            raise ValueError(f'kv_dtype must be "fp32", "bf16" or "e4m3", got {kv_dtype!r}')
         self.mlp_weights = check_format("mlp_weights", mlp_weights)
         self.lm_head_weights = check_format("lm_head_weights", lm_head_weights)
         self.attn_weights = check_format("attn_weights", attn_weights)
@@ -48,7 +50,7 @@ class LLMEngine:
         self.rope = (cos.to(self.device), sin.to(self.device))
         n_pages = (kv_tokens + page_size - 1) // page_size
         self.pool = KVPool(c["num_hidden_layers"], self.KVH, self.hd, n_pages, page_size, self.device,
-                           dtype=torch.bfloat16 if kv_dtype == "bf16" else torch.float32)
+                           dtype={"fp32": torch.float32, "bf16": torch.bfloat16, "e4m3": torch.float8_e4m3fn}[kv_dtype])
         self.stack = DecoderStack(src, "model.layers.", c["num_hidden_layers"], self.D, self.H, self.KVH, self.eps,
                                   True, self.rope, self.pool, first_fp16=True, mlp_weights=mlp_weights,
                                   mlp_rows=mlp_rows, attn_weights=attn_weights)

@@ -1037,10 +1037,46 @@ def attn_nsplit(max_keys, n_items, KVH):
 
 def kv_bytes(kc, vc):
     """Element width of one layer's paged K / V (the *_kv entries' kv_bytes): 4 for an fp32 pool, 2 for a bf16 one
-    (KVPool(dtype=torch.bfloat16)).  The launch takes its layout from the tensors it is given."""
+    (KVPool(dtype=torch.bfloat16)).  The launch takes its layout from the tensors it is given.  (An FP8
+    pool's codes never reach a *_kv entry: kv8_append and attention(kscale=, vscale=) take them with their scales.)"""
     if kc.dtype != vc.dtype or kc.dtype not in (F32, BF16):
         raise ValueError(f"paged K / V must both be fp32 or both bf16, got {kc.dtype} / {vc.dtype}")
     return 4 if kc.dtype == F32 else 2
+
+
+FP8 = torch.float8_e4m3fn
+KV8_LAUNCH_KINDS = ("kv8_append", "kv8_attention")
+
+
+def kv8_launch_counts():
+    """{entry: fo_kv8_append / fo_attention_kv8 launches issued since the last reset} (the FP8 KV cache, DESIGN §5.11;
+    the attention launches also count under their kernel family in launch_counts())."""
+    return _launch_counts("fo_kv8_counts", KV8_LAUNCH_KINDS)
+
+
+def kv8_launch_counts_reset():
+    _lib.call("fo_kv8_counts_reset")
+
+
+def _check_kv8(what, kc, kscale, vc, vscale):
+    if kc.dtype != FP8 or vc.dtype != FP8 or kscale.dtype != F32 or vscale.dtype != F32:
+        raise ValueError(f"{what}: an FP8 cache is e4m3fn codes with fp32 scales, got {kc.dtype} / {vc.dtype} codes and "
+                         f"{kscale.dtype} / {vscale.dtype} scales")
+    if kscale.shape != kc.shape[:-1] or vscale.shape != vc.shape[:-1]:
+        raise ValueError(f"{what}: scales {tuple(kscale.shape)} / {tuple(vscale.shape)} for codes {tuple(kc.shape)} / "
+                         f"{tuple(vc.shape)} (one per row)")
+
+
+def kv8_append(k_stage, v_stage, T, slot, kc, kscale, vc, vscale, PS):
+    """The FP8 cache's append (fo_kv8_append): rows 0 .. T - 1 of the fp32 staging caches k_stage / v_stage
+    [1][KVH][rows][hd] (what a q|k|v launch writes at PS = rows with the slot table arange(rows)) quantised into one
+    layer's codes kc / vc [page][KVH][PS][hd] and scales kscale / vscale [page][KVH][PS] at slot[t]."""
+    _check_kv8("kv8_append", kc, kscale, vc, vscale)
+    _, KVH, rows, hd = k_stage.shape
+    if k_stage.dtype != F32 or v_stage.dtype != F32 or v_stage.shape != k_stage.shape or k_stage.shape[0] != 1:
+        raise ValueError("kv8_append: the staging caches are fp32 [1][KVH][rows][hd]")
+    _lib.call("fo_kv8_append", k_stage.data_ptr(), v_stage.data_ptr(), T, KVH, hd, rows, slot.data_ptr(), PS,
+              kc.data_ptr(), kscale.data_ptr(), vc.data_ptr(), vscale.data_ptr(), stream(k_stage.device))
 
 
 def rope_kv_write(qkv, T, H, KVH, hd, pos, slot, cos_t, sin_t, q_out, kc, vc, PS):
@@ -1079,23 +1115,30 @@ ATTN_MAX_SPLIT_KEYS = 4096
 
 
 def attention(q, T, items, n_items, max_rows, tok_nvis, block_table, PS, kc, vc, H, KVH, hd, scale, nsplit,
-              part_ml, part_o, out, tickets=None, keys_per_split=128, opack=None):
+              part_ml, part_o, out, tickets=None, keys_per_split=128, opack=None, kscale=None, vscale=None):
     """tickets: zeroed int32 [>= n_items * KVH] -> splits sized from each item's key count (at most
     nsplit) merged inside the launch; None -> nsplit static splits + a combine launch.
     items None: a uniform batch, T / n_items tokens per sequence in sequence order (item b = sequence b); a
-    decode batch is the one-token case."""
+    decode batch is the one-token case.
+    kscale / vscale: the scales of an FP8 cache (kc / vc its e4m3fn codes): fo_attention_kv8, DESIGN §5.11."""
     if items is None and T % n_items:
         raise ValueError("attention: items=None needs T / n_items tokens per sequence")
     if tickets is not None and tickets.numel() < n_items * KVH:
         raise ValueError("attention tickets buffer smaller than n_items * KVH")
-    kvb = kv_bytes(kc, vc)
+    if (kscale is None) != (vscale is None):
+        raise ValueError("attention: kscale and vscale come together")
+    if kscale is not None:
+        _check_kv8("attention", kc, kscale, vc, vscale)
+        entry, tail = "fo_attention_kv8", (kscale.data_ptr(), vscale.data_ptr())
+    else:
+        entry, tail = "fo_attention_kv", (kv_bytes(kc, vc),)
     if opack is not None:
         _lib.call("fo_attention_set_opack", opack.hi.data_ptr(), opack.lo.data_ptr(), opack.K, opack.rb)
     try:
-        _lib.call("fo_attention_kv", q.data_ptr(), T, ptr(items), n_items, max_rows, tok_nvis.data_ptr(),
+        _lib.call(entry, q.data_ptr(), T, ptr(items), n_items, max_rows, tok_nvis.data_ptr(),
                   block_table.data_ptr(), block_table.shape[1], PS, kc.data_ptr(), vc.data_ptr(), H, KVH, hd,
                   float(scale), nsplit, ptr(part_ml), ptr(part_o), out.data_ptr(), ptr(tickets), int(keys_per_split),
-                  kvb, stream(q.device))
+                  *tail, stream(q.device))
     except Exception:
         if opack is not None:   # the launch did not consume it: never leave it for the next one
             _lib.call("fo_attention_set_opack", None, None, 0, 0)

@@ -22,7 +22,7 @@ ATTN_WEIGHT_FORMATS = ("fp8", "mxfp4")          # ... those the fused q|k|v + Ro
 FORMATS = {"mlp_weights": ("bf16",) + WEIGHT_FORMATS,
            "lm_head_weights": ("bf16",) + WEIGHT_FORMATS,
            "attn_weights": ("bf16",) + ATTN_WEIGHT_FORMATS,
-           "llm_kv": ("fp32", "bf16"),
+           "llm_kv": ("fp32", "bf16", "e4m3"),
            "FakeQuantSource format": WEIGHT_FORMATS,
            "FakeQuantSource lm_head": (None,) + WEIGHT_FORMATS,
            "FakeQuantSource attn": (None,) + ATTN_WEIGHT_FORMATS}
@@ -59,6 +59,22 @@ def quantize_rows_e4m3(w):
     q = scaled.to(torch.float8_e4m3fn)
     w_dq = torch.ldexp(q.float(), e[:, None]).to(torch.bfloat16)
     return q.view(torch.uint8), e, w_dq
+
+
+def quantize_kv_rows(x):
+    """The CPU model of the FP8 KV cache (llm_kv="e4m3"; fo_kv8_append): x [..., hd] fp32, each hd-wide
+    row one token's K (after bias and RoPE) or V (after bias) of one kv head -> (codes uint8 [..., hd], e int32 [...],
+    image bf16 [..., hd] = code * 2^e), the row quantiser above with the row's largest finite magnitude as amax.  A
+    non-finite element takes no part in the row's exponent and becomes the e4m3fn NaN code (sign | 0x7f; NaN in the
+    image), never a finite one."""
+    x32 = x.detach().float()
+    rows = x32.reshape(-1, x32.shape[-1])
+    bad = ~torch.isfinite(rows)
+    q, e, img = quantize_rows_e4m3(torch.where(bad, torch.zeros_like(rows), rows))
+    sign = ((rows.contiguous().view(torch.int32) >> 24) & 0x80).to(torch.uint8)
+    q = torch.where(bad, sign | 0x7F, q)
+    img = torch.where(bad, torch.full_like(img, float("nan")), img)
+    return q.reshape(x32.shape), e.reshape(x32.shape[:-1]), img.reshape(x32.shape)
 
 
 def pack_codes(q, tile_base=0, tile_stride=1, out=None):

@@ -93,6 +93,10 @@ class DecoderStack:
         # heads of 64, o 896 x 896 -- fuse the attention with the o projection (fo_attention_o: each (session, head)
         # workgroup multiplies its attention row by its head's o slice; the last head sums the partials)
         self.attn_o = ATTN_O and H == KVH and self.hd == 64 and D <= 1024 and n_layers > 0
+        # an FP8 pool (KVPool(dtype=torch.float8_e4m3fn)): staged append + fo_attention_kv8, never fuse_o
+        self.kv8 = bool(getattr(pool, "fp8", False))
+        if self.kv8:
+            self.attn_o = False
 
     def _packs(self, T):
         """Whether a T-row forward writes / reads packed activations (9..64 rows; <= 8 rows too for wide stacks under
@@ -133,6 +137,12 @@ class DecoderStack:
         if self.attn_o:
             ws["o_part"] = torch.empty(T * H * self.D, dtype=F32, device=device)
             ws["o_tickets"] = torch.zeros(max(T, 1), dtype=torch.int32, device=device)
+        if self.kv8:
+            # an FP8 pool: the q|k|v launch appends its fp32 K / V to this one-page staging cache (row t
+            # = token t: PS = T, slot table arange(T)) and ops.kv8_append quantises the rows into the pool
+            ws["k8"] = torch.zeros(1, KVH, T, hd, dtype=F32, device=device)
+            ws["v8"] = torch.zeros(1, KVH, T, hd, dtype=F32, device=device)
+            ws["slot8"] = torch.arange(T, dtype=torch.int32, device=device)
         if nsplit > 1:
             ws["part_ml"] = torch.empty(T * H * nsplit * 2, dtype=F32, device=device)
             ws["part_o"] = torch.empty(T * H * nsplit * hd, dtype=F32, device=device)
@@ -195,23 +205,31 @@ class DecoderStack:
         kps = self.attn_kps or (ops.attn_keys_per_split(meta.max_keys, meta.n_items, KVH, hd, x.device) if eager else 128)
         for i, L in enumerate(self.layers):
             li = self.kv_layer0 + i
-            rope = (meta.tok_pos, meta.tok_slot, self.cos, self.sin, q, self.pool.k[li], self.pool.v[li], H, KVH,
-                    self.pool.PS)
+            kc, vc = self.pool.k[li], self.pool.v[li]
+            if self.kv8:   # the GEMM writes the staging cache; kv8_append below moves the rows into the pool
+                rope = (meta.tok_pos, ws["slot8"], self.cos, self.sin, q, ws["k8"], ws["v8"], H, KVH,
+                        ws["k8"].shape[2])
+            else:
+                rope = (meta.tok_pos, meta.tok_slot, self.cos, self.sin, q, kc, vc, H, KVH, self.pool.PS)
             # (the first layer's rows come from a gather: no producer statistics yet; later layers apply the input
             # RMSNorm from the previous down projection's x*gamma and row sums)
             xin, norm = (h, None) if i == 0 else (xg, (sA, self.eps))
             if i == 0 and not pre_normed:
                 ops.rmsnorm(x, L.ln1, self.eps, out=h, round_fp16=self.first_fp16, M=T)
             L.qkv.qkv_rope(xin, T, *rope, norm=norm, xpack=xgp_qkv if i > 0 else None)
+            scales = {}
+            if self.kv8:
+                scales = {"kscale": self.pool.ks[li], "vscale": self.pool.vs[li]}
+                ops.kv8_append(ws["k8"], ws["v8"], T, meta.tok_slot, kc, scales["kscale"], vc, scales["vscale"],
+                               self.pool.PS)
             if fuse_o:
                 ops.attention_o(q, T, None if dense else meta.items, meta.tok_nvis, meta.block_table, self.pool.PS,
-                                self.pool.k[li], self.pool.v[li], H, hd, scale, L.o, ws["o_part"], ws["o_tickets"], x,
-                                L.ln2, xg, sB)
+                                kc, vc, H, hd, scale, L.o, ws["o_part"], ws["o_tickets"], x, L.ln2, xg, sB)
             else:
                 ops.attention(q, T, None if dense else meta.items, meta.n_items, meta.max_rows, meta.tok_nvis,
-                              meta.block_table, self.pool.PS, self.pool.k[li], self.pool.v[li], H, KVH, hd, scale,
+                              meta.block_table, self.pool.PS, kc, vc, H, KVH, hd, scale,
                               nsplit, part_ml, part_o, att, tickets=ws["tickets"], keys_per_split=kps,
-                              opack=attp)
+                              opack=attp, **scales)
                 L.o(att, out=x, residual=True, M=T, stats_out=sB.set(L.ln2, xg), xpack=attp, ypack=xgp_gu)
             L.gu(xg, out=m, M=T, norm=(sB, self.eps), xpack=xgp_gu)
             if i == last and final_norm is None:

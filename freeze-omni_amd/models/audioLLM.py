@@ -100,7 +100,7 @@ class AudioLLM:
         under one of the option's weight-only formats (fo.quant.FORMATS);
         mlp_fp8_rows: 16, 64 or 128 (with fp8, 64 lets 17..64-row Qwen2 steps stream the codes too, 128 65..128-row
         ones as well); mlp_mxfp4_rows: 16 or 64 (with mxfp4, 64 lets 17..64-row Qwen2 steps stream the codes too);
-        llm_kv: "fp32" or "bf16", the Qwen2 paged KV's element."""
+        llm_kv: "fp32", "bf16" or "e4m3", the Qwen2 paged KV's element."""
         for opt, value in (("mlp_weights", mlp_weights), ("lm_head_weights", lm_head_weights),
                            ("attn_weights", attn_weights)):
             check_format(opt, value)

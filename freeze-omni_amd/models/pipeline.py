@@ -35,7 +35,7 @@ class inferencePipeline:
         copied layouts match);
         args["llm_mlp_fp8_rows"]: 16 (default), 64 or 128, its mlp_fp8_rows;
         args["llm_mlp_mxfp4_rows"]: 16 (default) or 64, its mlp_mxfp4_rows;
-        args["llm_kv"]: "fp32" (default) or "bf16", its llm_kv (the Qwen2 paged KV's element)."""
+        args["llm_kv"]: "fp32" (default), "bf16" or "e4m3", its llm_kv (the Qwen2 paged KV's element)."""
         if isinstance(args, argparse.Namespace):
             args = vars(args)
         for opt in ("mlp_weights", "lm_head_weights", "attn_weights"):

@@ -471,6 +471,34 @@ int fo_attention_kv(const float* q, int T, const int* items, int n_items, int ma
                     const int* block_table, int maxb, int PS, const void* kc, const void* vc, int H, int KVH, int hd,
                     float scale, int nsplit, float* part_ml, float* part_o, float* out, int* tickets,
                     int keys_per_split, int kv_bytes, hipStream_t s);
+/* The FP8 (e4m3) paged KV cache of the Qwen2 stack (llm_kv="e4m3").  The cache holds OCP e4m3fn codes
+ * kc / vc, [page][kv head][slot][hd] bytes, and one scale 2^e per (token, kv head), ks / vs fp32 [page][kv head][slot]:
+ * e is fo_quant_w8's row exponent of the token's hd-wide K (after bias and RoPE) or V (after bias) row, the codes are
+ * x * 2^-e rounded to nearest even; a non-finite element becomes the NaN code.  code * 2^e is a bf16 value.
+ *
+ * fo_kv8_append: the q|k|v launch (any fo_gemm_qkv_rope_kv / fo_gemm_w8_qkv_rope / fo_gemm_w4_qkv_rope form) writes
+ * the T tokens' fp32 K / V into a staging cache k_stage / v_stage [KVH][stage_rows][hd] (one page of PS = stage_rows,
+ * slot table 0 .. stage_rows - 1); this launch quantises rows 0 .. T - 1 into the cache at slot[t] (pages of PS).
+ * Refused (-2, nothing launched): NULL codes, scales, staged rows or slot; hd not 32 / 64 / 128; PS <= 0; T outside
+ * 1 .. stage_rows.
+ *
+ * fo_attention_kv8: fo_attention_kv on such a cache, ks / vs in place of kv_bytes.  The kernels decode the codes to the
+ * bf16 values code * 2^e before any arithmetic and are the bf16 kernels from there: the result equals fo_attention_kv's
+ * on a bf16 cache holding those values bit for bit.  Counted under FO_L_ATTN_MFMA / FO_L_ATTN_GQA_DECODE.  Refused
+ * (-2, nothing launched): NULL codes or scales, hd not 32 / 64 / 128, PS <= 0, and the forms without an FP8 kernel --
+ * the 2-wave form (tickets with keys_per_split < 64 at hd 128), the traced launches, FO_ATTN_NW=4 at hd 128, and one
+ * query row per item (the single-row k_attn_decode form of the AR speech decoder, whose cache stays fp32).
+ *
+ * fo_kv8_counts: the launches issued since the last reset (fo_kv8_append, fo_attention_kv8) into out[0 .. min(n, 2));
+ * returns 2.  A captured graph counts at capture, a refused call not at all. */
+int fo_kv8_append(const float* k_stage, const float* v_stage, int T, int KVH, int hd, int stage_rows, const int* slot,
+                  int PS, void* kc, float* ks, void* vc, float* vs, hipStream_t s);
+int fo_attention_kv8(const float* q, int T, const int* items, int n_items, int max_rows, const int* tok_nvis,
+                     const int* block_table, int maxb, int PS, const void* kc, const void* vc, int H, int KVH, int hd,
+                     float scale, int nsplit, float* part_ml, float* part_o, float* out, int* tickets,
+                     int keys_per_split, const float* ks, const float* vs, hipStream_t s);
+int fo_kv8_counts(long long* out, int n);
+int fo_kv8_counts_reset(void);
 /* Conv2dSubsampling4.infer up to its output Linear (models/encoder/subsampling.py:67-73) with GlobalCMVN
  * (models/encoder/cmvn.py:24-35): feats [B][R][F] fp32 -> z [B * H2][C * W2] (the Linear's input rows, the reference's
  * x.transpose(1, 2).view(b, t, c * f)), H1 = (R - 3) / 2 + 1, W1 = (F - 3) / 2 + 1, H2 / W2 likewise from H1 / W1.
