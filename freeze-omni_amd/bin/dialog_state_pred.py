@@ -52,7 +52,8 @@ class DialogStateParams(DuplexSession):
                 "top_k": ic.get("top_k", 1), "top_p": ic.get("top_p", 0.0), "temperature": ic.get("temperature", 1.0),
                 "llm_mlp_weights": c.get("llm_mlp_weights", "bf16"),
                 "llm_mlp_fp8_rows": c.get("llm_mlp_fp8_rows", 16),
-                "llm_mlp_mxfp4_rows": c.get("llm_mlp_mxfp4_rows", 16), "llm_kv": c.get("llm_kv", "fp32"),
+                "llm_mlp_mxfp4_rows": c.get("llm_mlp_mxfp4_rows", 16),
+                "llm_mlp_mxfp6_rows": c.get("llm_mlp_mxfp6_rows", 16), "llm_kv": c.get("llm_kv", "fp32"),
                 "llm_lm_head_weights": c.get("llm_lm_head_weights", "bf16"),
                 "llm_attn_weights": c.get("llm_attn_weights", "bf16")})
         return cls.PIPELINE_POOL

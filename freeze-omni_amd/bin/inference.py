@@ -56,6 +56,8 @@ def get_args(argv=None):
                    help="with --llm_mlp_weights fp8: the most rows of a Qwen2 step that stream the FP8 codes")
     p.add_argument("--llm_mlp_mxfp4_rows", type=int, choices=[16, 64], default=16,
                    help="with --llm_mlp_weights mxfp4: the most rows of a Qwen2 step that stream the MXFP4 codes")
+    p.add_argument("--llm_mlp_mxfp6_rows", type=int, choices=[16, 64], default=16,
+                   help="with --llm_mlp_weights mxfp6: the most rows of a Qwen2 step that stream the MXFP6 codes")
     p.add_argument("--llm_kv", choices=FORMATS["llm_kv"], default="fp32",
                    help="Qwen2 paged KV cache element: fp32, bf16 (half the memory and attention bytes) or e4m3 (FP8 codes "
                         "with a scale per token and kv head: 0.26 of the memory, lossy)")

@@ -339,6 +339,7 @@ def dialog_session_factory(args):
     cfg["llm_mlp_weights"] = getattr(args, "llm_mlp_weights", None) or cfg.get("llm_mlp_weights", "bf16")
     cfg["llm_mlp_fp8_rows"] = getattr(args, "llm_mlp_fp8_rows", None) or cfg.get("llm_mlp_fp8_rows", 16)
     cfg["llm_mlp_mxfp4_rows"] = getattr(args, "llm_mlp_mxfp4_rows", None) or cfg.get("llm_mlp_mxfp4_rows", 16)
+    cfg["llm_mlp_mxfp6_rows"] = getattr(args, "llm_mlp_mxfp6_rows", None) or cfg.get("llm_mlp_mxfp6_rows", 16)
     cfg["llm_kv"] = getattr(args, "llm_kv", None) or cfg.get("llm_kv", "fp32")
     cfg["llm_lm_head_weights"] = getattr(args, "llm_lm_head_weights", None) or cfg.get("llm_lm_head_weights", "bf16")
     cfg["llm_attn_weights"] = getattr(args, "llm_attn_weights", None) or cfg.get("llm_attn_weights", "bf16")
@@ -384,6 +385,8 @@ def get_parser():
                    help="with FP8 weights: the most rows of a Qwen2 step that stream the codes (default 16)")
     p.add_argument("--llm_mlp_mxfp4_rows", type=int, choices=[16, 64], default=None,
                    help="with MXFP4 weights: the most rows of a Qwen2 step that stream the codes (default 16)")
+    p.add_argument("--llm_mlp_mxfp6_rows", type=int, choices=[16, 64], default=None,
+                   help="with MXFP6 weights: the most rows of a Qwen2 step that stream the codes (default 16)")
     p.add_argument("--llm_kv", choices=FORMATS["llm_kv"], default=None,
                    help="Qwen2 paged KV cache element: fp32 (default), bf16 (half the memory and attention bytes) or e4m3 (FP8 "
                         "codes with a scale per token and kv head: 0.26 of the memory, lossy)")

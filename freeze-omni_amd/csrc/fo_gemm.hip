@@ -1895,6 +1895,7 @@ int plan_grid(const GemmCall& c, const WeightDesc& w, GridPlan& p) {
   int S_auto = 0;
   if (p.mid) {
     NT = big_w ? (ntiles % 4 == 0 ? 4 : 2) : (swiglu ? 2 : 1);
+    if (ntiles % NT) NT = 1;   // (an odd plain tile count: pairs would leave the last tile uncomputed)
   } else if (p.RB == 1) {
     // measured policy (gemm_sweep.py, gemm_graph_sweep.py): wide layers (>= 1024 tiles: Qwen2 gate/up, lm_head) take 4
     // tiles per workgroup; long-K layers (Qwen2 down) 7 or 8 tiles and an 8-way K split; mid-size grids

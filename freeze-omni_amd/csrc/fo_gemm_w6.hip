@@ -1,5 +1,6 @@
 // Weight-only MXFP6 (OCP e2m3 codes, one power-of-two scale per 32 elements) GEMMs for the Qwen2 MLP at <= 16 rows
-// (fo_gemm_w6; fo_gemm_w6_head for the lm_head: k_w6_xs's plain form), and their quantiser.
+// (fo_gemm_w6; fo_gemm_w6_head for the lm_head: k_w6_xs's plain form) and at 17..64 rows (fo_gemm_w6_rows: k_w6_rows,
+// then k_w8_rows_merge of fo_gemm_wq.h where K is split), and their quantiser.
 //
 //   W'[n, k] = q[n, k] * 2^e[n, k / 32]   q an e2m3 code (1 sign, 2 exponent bits of bias 1, 3 mantissa bits: 0,
 //                                         0.125 .. 0.875, 1 .. 1.875, 2 .. 3.75, 4 .. 7.5), e one integer per (output
@@ -61,9 +62,14 @@ __device__ __forceinline__ W6Q w6_codes(const W6Srd& d, int lane, int step) {   
   q.p1 = __builtin_bit_cast(u32x3, __builtin_amdgcn_raw_buffer_load_b96(d.q, 768 + lane * 12, step * W6_STEP, 2));
   return q;
 }
-// the lane's scale byte: byte lane >> 4 of row lane & 15's dword
+// the lane's scale byte: byte lane >> 4 of row lane & 15's dword (w6_scale_dword: that dword as loaded, for a kernel
+// that keeps the load in flight and takes the byte where it decodes)
+__device__ __forceinline__ unsigned w6_scale_dword(const W6Srd& d, int lane, int step) {
+  return __builtin_amdgcn_raw_buffer_load_b32(d.s, (lane & 15) * 4, step * 64, 0);
+}
+__device__ __forceinline__ unsigned w6_scale_byte(unsigned dword, int lane) { return (dword >> (8 * (lane >> 4))) & 0xffu; }
 __device__ __forceinline__ unsigned w6_scale(const W6Srd& d, int lane, int step) {
-  return (__builtin_amdgcn_raw_buffer_load_b32(d.s, (lane & 15) * 4, step * 64, 0) >> (8 * (lane >> 4))) & 0xffu;
+  return w6_scale_byte(w6_scale_dword(d, lane, step), lane);
 }
 
 // A 4 x 4 transpose across the four lane groups of a wave (lanes r, r + 16, r + 32, r + 48), one dword per (register,
@@ -348,6 +354,153 @@ __global__ __launch_bounds__(NW * 64) void k_w6_xs(W8Args a, int units) {
   }
 }
 
+// ---- 17..64 rows (RB = 2..4 row blocks of 16; fo_gemm_w6_rows): k_w4_rows's design (fo_gemm_w4.hip) on this file's
+// code layout.  Workgroup (g, sp): the sp-th of S slices of the code steps for units [ub, ue) of column group g; a unit
+// is a packed tile pair (the (gate, up) pair, or two adjacent plain tiles: the second of an odd count's last pair lies
+// past both descriptors and loads zero codes under a zero scale byte).  Wave w owns KPW code steps of the slice.  Their
+// X fragments of all RB row blocks follow the layout's assignment -- lane (r, g), sub-step t of code step s:
+// X[row][128 s + 32 g + 8 t .. + 7], k_w6_xs's direct load -- and are split once (hi in VGPRs, lo in the wave's LDS
+// region).  A lane whose 32-column block lies at or past K (K % 128 = 32, 64 or 96, the last code step: a condition
+// per lane group, not per wave) reads no X -- X may end at the last row's column K -- and holds zero fragments.  Per
+// (tile, code step) two 12-byte plane loads and the scale dword; one dec6 gives the 4 B fragments that feed
+// RB x (hi, lo) MFMAs each.  The next two units' codes and scales are in flight meanwhile.  Per unit the NW partial
+// tiles are summed through LDS in wave order (both tiles in one round where the LDS allows).  S == 1: the epilogue
+// follows.  S > 1: the sums are stored as split sp's slab of `ws` ([S][RB * 16][ntiles * 16] floats) and
+// k_w8_rows_merge (fo_gemm_wq.h, unscaled), the next launch, sums the slabs in split order and runs the epilogue.
+template <int NW, int KPW, int RB, bool SW>
+__global__ __launch_bounds__(NW * 64) void k_w6_rows(W8Args a, int S, int per, float* ws) {
+  constexpr int ROWS = RB * 16, NTH = NW * 64, NE = ROWS * 16, EPT = (NE + NTH - 1) / NTH;
+  constexpr int PT = (NW * RB * 4 * KPW * 1024 + NW * 2 * ROWS * 17 * 4 + 512 <= 160 * 1024) ? 2 : 1;
+  __shared__ bf16x8 xlo[NW][RB][4 * KPW][64];
+  __shared__ float part[NW][PT][ROWS][17];
+  __shared__ float rstd_s[ROWS];
+  // (the wave index through readfirstlane: the code steps' offsets are then scalars the buffer loads take as they are)
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int G = gridDim.x, g = blockIdx.x, sp = blockIdx.y;
+  const int units = (a.ntiles + 1) >> 1, tiles = (a.N + 15) / 16;   // (tiles: output tiles, the statistics' groups)
+  const int ub = (int)((long)units * g / G), ue = (int)((long)units * (g + 1) / G);
+  const W6Srd d = w6_srd(a);   // (exactly the codes and the scale bytes)
+  // this wave's code steps: [k0, k0 + nj) inside the slice [sp * per, (sp + 1) * per) and inside KK (wave-uniform)
+  const int k0 = sp * per + wave * KPW;
+  const int nj = max(0, min(KPW, min(a.KK, (sp + 1) * per) - k0));
+  W6Q q[2][2][KPW];
+  unsigned sc[2][2][KPW];   // (the scale dwords as loaded: the lane's byte is taken where they are decoded)
+  auto issue = [&](W6Q (&qq)[2][KPW], unsigned (&ss)[2][KPW], int u) {   // u >= ue: no load issued
+    if (u < ue) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int j = 0; j < KPW; ++j)
+          if (j < nj) {
+            qq[t][j] = w6_codes(d, lane, (2 * u + t) * a.KK + k0 + j);
+            ss[t][j] = w6_scale_dword(d, lane, (2 * u + t) * a.KK + k0 + j);
+          }
+    }
+  };
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int j = 0; j < KPW; ++j) {   // code steps past the slice: zero codes under a zero scale byte
+        q[b][t][j].p0 = q[b][t][j].p1 = u32x3{0u, 0u, 0u};
+        sc[b][t][j] = 0u;
+      }
+  issue(q[0], sc[0], ub);
+  issue(q[1], sc[1], ub + 1);
+  bf16x8 zero;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) zero[i] = (__bf16)0.f;
+  bf16x8 xh[RB][4 * KPW];
+#pragma unroll
+  for (int r = 0; r < RB; ++r) {
+    const int row = min(r * 16 + (lane & 15), a.M - 1);   // rows >= M: computed, never stored or summed
+    const float* xp = a.X + (size_t)row * a.ldx + 32 * (lane >> 4);
+#pragma unroll
+    for (int j = 0; j < 4 * KPW; ++j) {
+      bf16x8 hi = zero, lo = zero;
+      const int blk = (k0 + (j >> 2)) * 128 + 32 * (lane >> 4);   // the lane's block of this code step: in K or past it
+      if ((j >> 2) < nj && blk < a.K) {
+        const float4* p = reinterpret_cast<const float4*>(xp + (size_t)(k0 + (j >> 2)) * 128 + (j & 3) * 8);
+        split8(p[0], p[1], hi, lo);
+      }
+      xh[r][j] = hi;
+      xlo[wave][r][j][lane] = lo;
+    }
+  }
+  if (S == 1) {   // the consumer's rstd of every row (rows >= M from the clamped row)
+    if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane, 0, ROWS);
+    __syncthreads();
+  }
+  const int Ncols = a.ntiles * 16;
+  float* slab = ws + (size_t)sp * ROWS * Ncols;
+  auto unit = [&](W6Q (&qq)[2][KPW], unsigned (&ss)[2][KPW], int u) {
+    float v[2][EPT];
+    // (the lo fragments are re-read from LDS per unit, as in k_w6_xs: an opaque lane index keeps the compiler from
+    // hoisting the loop-invariant reads into RB * 4 KPW more live registers, which spilled at 2 row blocks)
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+#pragma unroll
+    for (int t0 = 0; t0 < 2; t0 += PT) {
+      f32x4 acc[PT][RB];
+#pragma unroll
+      for (int p = 0; p < PT; ++p) {
+#pragma unroll
+        for (int r = 0; r < RB; ++r) acc[p][r] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < KPW; ++j) {
+          const W6Frag w = dec6(qq[t0 + p][j], w6_scale_byte(ss[t0 + p][j], lane));
+#pragma unroll
+          for (int h = 0; h < 4; ++h)
+#pragma unroll
+            for (int r = 0; r < RB; ++r) {
+              acc[p][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[r][4 * j + h], w.f[h], acc[p][r], 0, 0, 0);
+              acc[p][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xlo[wave][r][4 * j + h][ln], w.f[h], acc[p][r], 0, 0, 0);
+            }
+        }
+      }
+      if (t0 + PT == 2) issue(qq, ss, u + 2);   // (the unit's codes are decoded: its buffer takes the unit after next)
+      __syncthreads();  // the previous reduction has read part[]
+#pragma unroll
+      for (int p = 0; p < PT; ++p)
+#pragma unroll
+        for (int r = 0; r < RB; ++r) w8_store_tile(part[wave][p], acc[p][r], lane, r * 16);
+      __syncthreads();
+#pragma unroll
+      for (int p = 0; p < PT; ++p)
+#pragma unroll
+        for (int i = 0; i < EPT; ++i) {
+          const int e = threadIdx.x + i * NTH;
+          float s = 0.f;
+          if (e < NE) {
+#pragma unroll
+            for (int w = 0; w < NW; ++w) s += part[w][p][e >> 4][e & 15];
+            if (S > 1 && 2 * u + t0 + p < a.ntiles)
+              slab[(size_t)(e >> 4) * Ncols + (2 * u + t0 + p) * 16 + (e & 15)] = s;
+          }
+          v[t0 + p][i] = s;
+        }
+    }
+    if (S == 1) {
+#pragma unroll
+      for (int i = 0; i < EPT; ++i) {
+        const int e = threadIdx.x + i * NTH;   // (NTH % 16 == 0: a row's 16 columns are one 16-lane row of a wave)
+        const int rr = e < NE ? e >> 4 : ROWS, c = e & 15;
+        if constexpr (SW) {
+          w8_epilogue<true, false>(a, u, tiles, rr, c, v[0][i], v[1][i], rstd_s);
+        } else {
+          w8_epilogue<false, false>(a, 2 * u, tiles, rr, c, v[0][i], 0.f, rstd_s);
+          if (2 * u + 1 < a.ntiles) w8_epilogue<false, false>(a, 2 * u + 1, tiles, rr, c, v[1][i], 0.f, rstd_s);
+        }
+      }
+    }
+  };
+  for (int u = ub; u < ue; u += 2) {   // (workgroup-uniform: every wave reaches unit's barriers)
+    unit(q[0], sc[0], u);
+    if (u + 1 < ue) unit(q[1], sc[1], u + 1);
+  }
+}
+
 // ---- quantiser.  One workgroup per source row n, one 32-column block per thread and pass: the block's amax, e from
 // its exponent and mantissa (the smallest integer with amax * 2^-e <= 7.5 = 1.875 * 2^2, at least -123 so that every
 // non-zero q * 2^e is a normal bf16; 0 for an all-zero block), W * 2^-e (exact, or an underflow that rounds to 0 anyway)
@@ -425,16 +578,20 @@ int w6_cus() {
   return g_cus;
 }
 
-// the launch counters (fo_gemm_w6_counts): fo_gemm_w6's general, xs and sk forms, and fo_gemm_w6_head
+// the launch counters (fo_gemm_w6_counts): fo_gemm_w6's general, xs and sk forms, and fo_gemm_w6_head; and the calls of
+// fo_gemm_w6_rows (fo_gemm_w6_rows_count)
 std::atomic<long long> g_w6_launches[4];
+std::atomic<long long> g_w6_rows_calls;
 
-// What the two GEMM entries share: every check (all before the entry's first HIP call), then W8Args (with KK) and the
-// output tile count.  `fn` is the entry's name.
-int w6_args(const char* fn, const float* X, int ldx, int M, int K, const void* Q, const void* scale, int ntiles, int N,
-            int swiglu, float* Y, int ldy, int residual, const float* rstats, int rgroups, float eps, float* sout,
-            const float* gnext, float* yg, W8Args& a, int& units) {
+// What the GEMM entries share: the checks of everything but the workspace (all before the entry's first HIP call),
+// then W8Args (with KK) and the output tile count.  `fn` is the entry's name, [m_lo, m_hi] its row band and `serves`
+// what its refusal says of the band.
+constexpr const char* W6_SERVES_16 = "the MXFP6 stream serves M <= 16 (more rows run the bf16 image)";
+int w6_args(const char* fn, int m_lo, int m_hi, const char* serves, const float* X, int ldx, int M, int K, const void* Q,
+            const void* scale, int ntiles, int N, int swiglu, float* Y, int ldy, int residual, const float* rstats,
+            int rgroups, float eps, float* sout, const float* gnext, float* yg, W8Args& a, int& units) {
   FO_REQUIRE(M > 0 && N > 0 && K > 0, "%s: bad shape M=%d N=%d K=%d", fn, M, N, K);
-  FO_REQUIRE(M <= 16, "%s: M=%d rows, the MXFP6 stream serves M <= 16 (more rows run the bf16 image)", fn, M);
+  FO_REQUIRE(M >= m_lo && M <= m_hi, "%s: M=%d rows, %s", fn, M, serves);
   FO_REQUIRE((K & 31) == 0, "%s: K=%d must be a multiple of 32", fn, K);
   FO_REQUIRE(X && Q && Y, "%s: NULL X, Q or Y", fn);
   FO_REQUIRE(scale, "%s: NULL scale (the E8M0 block bytes of fo_quant_w6)", fn);
@@ -484,8 +641,10 @@ int fo_gemm_w6_counts(long long* out, int n) {
 }
 int fo_gemm_w6_counts_reset(void) {
   for (int i = 0; i < 4; ++i) g_w6_launches[i].store(0, std::memory_order_relaxed);
+  g_w6_rows_calls.store(0, std::memory_order_relaxed);
   return 0;
 }
+long long fo_gemm_w6_rows_count(void) { return g_w6_rows_calls.load(std::memory_order_relaxed); }
 
 int fo_gemm_w6(const float* X, int ldx, int M, int K, const void* Q, const void* scale, int ntiles, int N, int swiglu,
                float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters, const float* rstats,
@@ -493,8 +652,8 @@ int fo_gemm_w6(const float* X, int ldx, int M, int K, const void* Q, const void*
   // every check before the first HIP call
   W8Args a;
   int units;
-  if (const int rc = w6_args("fo_gemm_w6", X, ldx, M, K, Q, scale, ntiles, N, swiglu, Y, ldy, residual, rstats, rgroups,
-                             eps, sout, gnext, yg, a, units))
+  if (const int rc = w6_args("fo_gemm_w6", 1, 16, W6_SERVES_16, X, ldx, M, K, Q, scale, ntiles, N, swiglu, Y, ldy,
+                             residual, rstats, rgroups, eps, sout, gnext, yg, a, units))
     return rc;
   const int KK = a.KK;
   if (sgroups) *sgroups = units;
@@ -538,8 +697,8 @@ int fo_gemm_w6_head(const float* X, int ldx, int M, int K, const void* Q, const 
   // every check before the first HIP call
   W8Args a;
   int tiles;
-  if (const int rc = w6_args("fo_gemm_w6_head", X, ldx, M, K, Q, scale, ntiles, N, 0, Y, ldy, 0, nullptr, 0, 0.f,
-                             nullptr, nullptr, nullptr, a, tiles))
+  if (const int rc = w6_args("fo_gemm_w6_head", 1, 16, W6_SERVES_16, X, ldx, M, K, Q, scale, ntiles, N, 0, Y, ldy, 0,
+                             nullptr, 0, 0.f, nullptr, nullptr, nullptr, a, tiles))
     return rc;
   FO_REQUIRE(K == 3584, "fo_gemm_w6_head: K=%d, the X-stationary plain form is compiled for K = 3584 (fo_gemm_w6 serves "
              "any other K)", K);
@@ -549,6 +708,63 @@ int fo_gemm_w6_head(const float* X, int ldx, int M, int K, const void* Q, const 
   hipLaunchKernelGGL((k_w6_xs<14, 2, false>), dim3(G), dim3(896), 0, stream, a, units);
   g_w6_launches[3].fetch_add(1, std::memory_order_relaxed);
   return fo::check_launch("fo_gemm_w6_head");
+}
+
+int fo_gemm_w6_rows(const float* X, int ldx, int M, int K, const void* Q, const void* scale, int ntiles, int N,
+                    int swiglu, float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters,
+                    const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
+                    int* sgroups, hipStream_t stream) {
+  // every check before the first HIP call
+  W8Args a;
+  int units;
+  if (const int rc = w6_args("fo_gemm_w6_rows", 17, 64,
+                             "this MXFP6 stream serves 17 <= M <= 64 (fo_gemm_w6 serves M <= 16, more than 64 rows run "
+                             "the bf16 image)",
+                             X, ldx, M, K, Q, scale, ntiles, N, swiglu, Y, ldy, residual, rstats, rgroups, eps, sout,
+                             gnext, yg, a, units))
+    return rc;
+  const int KK = a.KK;
+  // NW waves x KPW code steps of X per K slice (hi in VGPRs, lo in LDS): fo_gemm_w4_rows's shapes at 3 and 4 row
+  // blocks (7 x 1 for SwiGLU, 8 x 1 / 6 x 1 for plain).  At 2 row blocks its 7 x 2 does not fit here: the two-deep code
+  // buffer is 2 x 2 x KPW x 7 dwords a lane against MXFP4's x 5, and both 7 x 2 instantiations spilled (256 VGPRs, 8 and
+  // 16 bytes of scratch a lane), so 2 row blocks run 7 x 1 (DESIGN 5.10 has every instantiation's figures).  S slices
+  // of `per` code steps, units of two packed tiles, about one workgroup per CU.  S > 1: the slabs are merged by a
+  // second launch (k_w8_rows_merge), one small workgroup per (tile, row block)
+  const int RB = (M + 15) / 16;
+  const int NW = RB == 3 ? (swiglu ? 7 : 8) : (RB == 4 && !swiglu ? 6 : 7), KPW = 1;
+  const int S = (KK + NW * KPW - 1) / (NW * KPW), per = (KK + S - 1) / S;
+  if (S > 1) {
+    const long long need = (long long)S * RB * 16 * ntiles * 16;
+    FO_REQUIRE(ws && need <= ws_floats,
+               "fo_gemm_w6_rows: K=%d splits over %d workgroups: split-K workspace too small (%lld floats needed, "
+               "%lld given)", K, S, need, ws ? ws_floats : 0ll);
+  }
+  const int pairs = (ntiles + 1) / 2;
+  const int per_split = w6_cus() / S < 1 ? 1 : w6_cus() / S;
+  const int G = pairs < per_split ? pairs : per_split;
+  (void)counters;
+  if (sgroups) *sgroups = units;
+  const dim3 grid(G, S), block(NW * 64);
+#define FO_W6_ROWS(NW_, KPW_, RB_, SW_) \
+  hipLaunchKernelGGL((k_w6_rows<NW_, KPW_, RB_, SW_>), grid, block, 0, stream, a, S, per, ws)
+  if (RB == 2) {
+    if (swiglu) FO_W6_ROWS(7, 1, 2, true);
+    else FO_W6_ROWS(7, 1, 2, false);
+  } else if (RB == 3) {
+    if (swiglu) FO_W6_ROWS(7, 1, 3, true);
+    else FO_W6_ROWS(8, 1, 3, false);
+  } else {
+    if (swiglu) FO_W6_ROWS(7, 1, 4, true);
+    else FO_W6_ROWS(6, 1, 4, false);
+  }
+#undef FO_W6_ROWS
+  if (S > 1) {
+    const int rc = fo::check_launch("fo_gemm_w6_rows");
+    if (rc) return rc;
+    launch_merge<false>(a, swiglu, units, RB, S, ws, stream);
+  }
+  g_w6_rows_calls.fetch_add(1, std::memory_order_relaxed);
+  return fo::check_launch("fo_gemm_w6_rows");
 }
 
 }  // extern "C"

@@ -113,7 +113,10 @@ _SIGS = {
     "fo_gemm_w6": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_ll,
                            c_vp, c_vp, c_int, c_float, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), c_vp]),
     "fo_gemm_w6_head": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_int, c_vp]),
+    "fo_gemm_w6_rows": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp,
+                                c_ll, c_vp, c_vp, c_int, c_float, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), c_vp]),
     "fo_gemm_w6_counts": (c_int, [ctypes.POINTER(c_ll), c_int]),
+    "fo_gemm_w6_rows_count": (c_ll, []),
     "fo_gemm_w6_counts_reset": (c_int, []),
     "fo_gemm_w8_qkv_rope": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_float,
                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),

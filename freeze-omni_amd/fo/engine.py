@@ -71,7 +71,7 @@ class FreezeOmniEngine:
     def __init__(self, model_path, llm_path=None, device="cuda:0", max_sessions=64, llm_kv_tokens=None,
                  tts_kv_tokens=None, source=None, receive_weights=False, train_yaml=None, mlp_weights="bf16",
                  mlp_fp8_rows=16, llm_kv="fp32", mlp_mxfp4_rows=16, lm_head_weights="bf16",
-                 attn_weights="bf16"):
+                 attn_weights="bf16", mlp_mxfp6_rows=16):
         """attn_weights: "bf16" (default), "fp8" or "mxfp4": self_attn.{q,k,v,o}_proj.weight of every Qwen2 layer under
         weight-only FP8 per output row or MXFP4, independent of mlp_weights, mlp_*_rows, lm_head_weights
         and llm_kv; the biases and the AR speech decoder's stack are untouched.  Steps of <= 16 rows stream the codes
@@ -98,6 +98,9 @@ class FreezeOmniEngine:
         under weight-only MXFP6 (e2m3 codes under the same block scales, DESIGN §5.10: FP8's accuracy at 0.78 of its
         bytes): Qwen2 steps of <= 16 rows stream the codes for the GEMMs of ops.W6_POLICY, every other launch runs the
         exact bf16 image; mlp_fp8_rows and mlp_mxfp4_rows stay 16.
+        mlp_mxfp6_rows: 16 (default) or 64, with mlp_weights="mxfp6" only: 64 lets Qwen2 steps of 17..64 rows stream the
+        MXFP6 codes too (fo_gemm_w6_rows), for the GEMMs and row counts of ops.W6_ROWS_POLICY; the model
+        is the same, every other step is unchanged.
         mlp_fp8_rows: 16 (default), 64 or 128, with mlp_weights="fp8" only: 64 lets Qwen2 steps of 17..64 rows (duplex
         ticks, prefixed first chunks, one-chunk listens of more than 8 sessions) stream the codes too, 128 steps of
         65..128 rows as well (the grouped offline listen, duplex ticks whose sessions start a turn), for the GEMMs
@@ -115,6 +118,7 @@ class FreezeOmniEngine:
         self.mlp_weights = check_format("mlp_weights", mlp_weights)
         self.mlp_fp8_rows = check_format("mlp_fp8_rows", mlp_fp8_rows, ops.QUANT_FORMATS["fp8"].stream_rows)
         self.mlp_mxfp4_rows = check_format("mlp_mxfp4_rows", mlp_mxfp4_rows, ops.QUANT_FORMATS["mxfp4"].stream_rows)
+        self.mlp_mxfp6_rows = check_format("mlp_mxfp6_rows", mlp_mxfp6_rows, ops.QUANT_FORMATS["mxfp6"].stream_rows)
         self.llm_kv = check_format("llm_kv", llm_kv)
         self.lm_head_weights = check_format("lm_head_weights", lm_head_weights)
         self.attn_weights = check_format("attn_weights", attn_weights)
@@ -158,9 +162,9 @@ class FreezeOmniEngine:
         self._chat_template(ty["model_conf"].get("chat_template"))
 
     def _llm_options(self):
-        """This engine's Qwen2 options as LLMEngine's keywords: mlp_fp8_rows / mlp_mxfp4_rows, each of which needs its
-        own format, become the one mlp_rows."""
-        rows = {"fp8": self.mlp_fp8_rows, "mxfp4": self.mlp_mxfp4_rows}
+        """This engine's Qwen2 options as LLMEngine's keywords: mlp_fp8_rows / mlp_mxfp4_rows / mlp_mxfp6_rows, each of
+        which needs its own format, become the one mlp_rows."""
+        rows = {"fp8": self.mlp_fp8_rows, "mxfp4": self.mlp_mxfp4_rows, "mxfp6": self.mlp_mxfp6_rows}
         for fmt, r in rows.items():
             if r != 16 and self.mlp_weights != fmt:
                 raise ValueError(f"mlp_{fmt}_rows={r} needs mlp_weights={fmt!r}")

@@ -390,21 +390,40 @@ W4_ROWS_POLICY = {"gate_up": (2, 3, 4), "down": (2, 3)}
 W6_POLICY = {"gate_up": True, "down": True, "head": True}
 
 
+# Which 17..64-row launches of a PackedLinearW6(stream_rows=64) stream the codes (fo_gemm_w6_rows): per GEMM, the
+# row-block counts (ceil(rows / 16)) out of 2, 3, 4 at which the MXFP6 row stream beat the bf16 image of the same W' by
+# more than that arm's repeat-to-repeat spread -- for the down, by more than that spread plus the packed input it costs
+# the next q|k|v (DESIGN 5.5's rule; scripts/gemm_w4_rows_ab.py --fmt mxfp6, profiles/mlp_mxfp6_rows_gemm_ab.txt,
+# DESIGN 5.10).
+# Builder-run, not driver-timed (medians, us, bf16 image / mxfp6 at 32 / 48 / 64 rows; the bf16 spread in brackets):
+#   gate/up: 59.1 / 44.7 (1.6), 70.2 / 56.5 (1.4), 81.5 / 74.3 (1.8): every pair entered;
+#   down:    35.1 / 29.5 (2.5), 40.2 / 35.1 (1.5), 47.0 / 46.5 (0.7), and the next q|k|v loses 2.8 us on fp32 rows: the
+#   down entered at 2 and 3 row blocks (gains 5.6 and 5.2 us against margins of 5.4 and 4.3) and not at 4 (0.5 us).
+# The one place the policy lives.
+W6_ROWS_POLICY = {"gate_up": (2, 3, 4), "down": (2, 3)}
+
+
 # (format -> (the <= 16-row policy of its MLP GEMMs, its row-stream policy); an FP8 MLP GEMM always streams)
 _MLP_POLICY = {"fp8": ({"gate_up": True, "down": True}, W8_ROWS_POLICY), "mxfp4": (W4_POLICY, W4_ROWS_POLICY),
-               "mxfp6": (W6_POLICY, {})}
+               "mxfp6": (W6_POLICY, W6_ROWS_POLICY)}
 _HEAD_POLICY = {**HEAD_POLICY, "mxfp6": W6_POLICY["head"]}
+# The formats whose row policy reaches only a layer built with a band above 16: a default PackedLinearW6 answers
+# rows_rb == () (FP8 and MXFP4 layers carry their policy at any stream_rows, and streams() keeps it behind stream_rows).
+_ROWS_WITH_THE_BAND = ("mxfp6",)
 
 
-def _policy(fmt, gemm, K):
+def _policy(fmt, gemm, K, stream_rows=16):
     """What the tables above say about one GEMM of a format -> (stream, rows_rb): whether its <= 16-row calls stream
     the codes, and the row-block counts at which its larger calls do.  gemm: "gate_up", "down", "head", "attn_o" or
-    "qkv"; K matters to the head alone, whose policy is about the entry compiled for HEAD_K."""
+    "qkv"; K matters to the head alone, whose policy is about the entry compiled for HEAD_K; stream_rows to the formats
+    of _ROWS_WITH_THE_BAND alone."""
     if gemm == "head":
         return bool(_HEAD_POLICY[fmt]) if K == HEAD_K else True, ()
     if gemm in ("attn_o", "qkv"):
         return bool(ATTN_POLICY[fmt][gemm.replace("attn_", "")]), ()
     streams, rows = _MLP_POLICY[fmt]
+    if fmt in _ROWS_WITH_THE_BAND and stream_rows == 16:
+        return bool(streams[gemm]), ()
     return bool(streams[gemm]), rows.get(gemm, ())
 
 
@@ -431,8 +450,8 @@ QUANT_FORMATS = {
                        "fp8_nbytes"),
     "mxfp4": QuantFormat(128, 1024, True, (16, 64), ("head", "attn_o"), "fo_quant_w4", "fo_gemm_w4", "fo_gemm_w4_head",
                          {64: "fo_gemm_w4_rows"}, "fo_gemm_w4_qkv_rope", "fp4_nbytes"),
-    "mxfp6": QuantFormat(128, 1536, True, (16,), ("head",), "fo_quant_w6", "fo_gemm_w6", "fo_gemm_w6_head", {}, None,
-                         "fp6_nbytes"),
+    "mxfp6": QuantFormat(128, 1536, True, (16, 64), ("head",), "fo_quant_w6", "fo_gemm_w6", "fo_gemm_w6_head",
+                         {64: "fo_gemm_w6_rows"}, None, "fp6_nbytes"),
 }
 
 
@@ -523,7 +542,8 @@ class PackedLinearQuant(_QuantCodes):
     w: [N, K] device weight (bf16 or fp32; K % 32 == 0 under the MX formats), quantised on the device; swiglu_up as
     PackedLinear.
     receive=True: storages allocated, nothing quantised (a replica whose weights arrive by broadcast).
-    stream_rows: 16 (default), or a larger band the format has row-stream entries for (FP8 64 and 128, MXFP4 64): calls
+    stream_rows: 16 (default), or a larger band the format has row-stream entries for (FP8 64 and 128, MXFP4 and MXFP6
+    64): calls
     of 17 rows up to it stream the codes too, for the row-block counts in `rows_rb`.
     kind: None for an MLP GEMM (gate/up with swiglu_up, else down); "head": the Qwen2 output head, at K = HEAD_K on
     the format's head entry (plain: a call with a residual, norm or stats_out runs the image), at any other K on the
@@ -548,7 +568,7 @@ class PackedLinearQuant(_QuantCodes):
             raise ValueError(f"{type(self).__name__} needs K % 32 == 0 (the scale block), got K={self.K}")
         self.Kp = (self.K + 31) // 32 * 32
         self.swiglu = swiglu_up is not None
-        self.stream, self.rows_rb = _policy(fmt, kind or ("gate_up" if self.swiglu else "down"), self.K)
+        self.stream, self.rows_rb = _policy(fmt, kind or ("gate_up" if self.swiglu else "down"), self.K, stream_rows)
         self.device = w.device
         self.ntiles = (self.N + 15) // 16 * (2 if self.swiglu else 1)
         # the entries, resolved here: __call__ runs once per GEMM of an eager step
@@ -625,8 +645,9 @@ class PackedLinearW4(PackedLinearQuant):
 
 class PackedLinearW6(PackedLinearQuant):
     """PackedLinearQuant under MXFP6: W'[n, k] = q[n, k] * 2^e[n, k // 32] with q an e2m3 code under MXFP4's block
-    scales (fo_quant_w6).  <= 16-row calls run fo_gemm_w6 where W6_POLICY lists the GEMM; the format has no row
-    streams (stream_rows is 16) and no attention output."""
+    scales (fo_quant_w6).  <= 16-row calls run fo_gemm_w6 where W6_POLICY lists the GEMM; stream_rows 64 adds
+    fo_gemm_w6_rows for 17..64 rows at W6_ROWS_POLICY's row-block counts (a layer built with the default 16 has
+    rows_rb == ()).  The format has no attention output."""
 
     def __init__(self, w, swiglu_up=None, receive=False, kind=None, stream_rows=16):
         super().__init__(w, "mxfp6", swiglu_up, receive, stream_rows, kind)
@@ -752,6 +773,11 @@ def head_launch_counts():
 
 def head_launch_counts_reset():
     _lib.call("fo_gemm_head_counts_reset")
+
+
+def w6_rows_launch_count():
+    """fo_gemm_w6_rows calls since the last w6_launch_counts_reset (one per call, its merge included)."""
+    return int(_lib.load().fo_gemm_w6_rows_count())
 
 
 def w4_rows_launch_count():

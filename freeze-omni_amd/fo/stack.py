@@ -42,8 +42,8 @@ class DecoderStack:
         mlp_weights: "bf16", "fp8", "mxfp4" or "mxfp6": gate/up and down under that weight-only format
         (ops.PackedLinearW8 / W4 / W6: the model's MLP weights become q * 2^e; forwards of <= 16 rows stream the codes
         for the GEMMs the format's policy lists, everything else runs the exact bf16 image of the same weights).
-        mlp_rows: the layers' stream_rows: 16, or 64 (FP8, MXFP4: 17..64-row forwards stream the codes too, for the
-        pairs of ops.W8_ROWS_POLICY / W4_ROWS_POLICY) or 128 (FP8: 65..128-row ones as well)."""
+        mlp_rows: the layers' stream_rows: 16, or 64 (17..64-row forwards stream the codes too, for the pairs of
+        ops.W8_ROWS_POLICY / W4_ROWS_POLICY / W6_ROWS_POLICY) or 128 (FP8: 65..128-row ones as well)."""
         self.mlp_weights = check_format("mlp_weights", mlp_weights)
         self.attn_weights = check_format("attn_weights", attn_weights)
         self.mlp_rows = mlp_rows

@@ -35,6 +35,7 @@ class inferencePipeline:
         copied layouts match);
         args["llm_mlp_fp8_rows"]: 16 (default), 64 or 128, its mlp_fp8_rows;
         args["llm_mlp_mxfp4_rows"]: 16 (default) or 64, its mlp_mxfp4_rows;
+        args["llm_mlp_mxfp6_rows"]: 16 (default) or 64, its mlp_mxfp6_rows;
         args["llm_kv"]: "fp32" (default), "bf16" or "e4m3", its llm_kv (the Qwen2 paged KV's element)."""
         if isinstance(args, argparse.Namespace):
             args = vars(args)
@@ -53,6 +54,7 @@ class inferencePipeline:
                                              mlp_weights=args.get("llm_mlp_weights") or "bf16",
                                              mlp_fp8_rows=args.get("llm_mlp_fp8_rows") or 16,
                                              mlp_mxfp4_rows=args.get("llm_mlp_mxfp4_rows") or 16,
+                                             mlp_mxfp6_rows=args.get("llm_mlp_mxfp6_rows") or 16,
                                              llm_kv=args.get("llm_kv") or "fp32",
                                              lm_head_weights=args.get("llm_lm_head_weights") or "bf16",
                                              attn_weights=args.get("llm_attn_weights") or "bf16")

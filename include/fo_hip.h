@@ -308,7 +308,7 @@ int fo_gemm_w4_head(const float* X, int ldx, int M, int K, const void* q, const 
 int fo_gemm_head_counts(long long* out, int n);
 int fo_gemm_head_counts_reset(void);
 /* Weight-only MXFP6 (OCP e2m3 codes, one power-of-two scale per 32 elements) for <= 16-row launches of the Qwen2 MLP
- * (fo_gemm_w6) and output head (fo_gemm_w6_head):
+ * (fo_gemm_w6) and output head (fo_gemm_w6_head), and 17..64-row launches of the MLP (fo_gemm_w6_rows):
  *   W'[n][k] = q[n][k] * 2^e[n][k / 32], q an e2m3 code (bit 5 the sign, 2 exponent bits of bias 1, 3 mantissa bits:
  *   magnitudes 0, 0.125 .. 0.875, 1 .. 1.875, 2 .. 3.75, 4 .. 7.5), e the smallest integer with
  *   max|W[n][block]| * 2^-e <= 7.5, taken from the float's exponent and mantissa (mantissa > 0x700000 adds one), at
@@ -332,8 +332,24 @@ int fo_gemm_head_counts_reset(void);
  *   merge inside the launch in split order where ws and counters are given (k_w6_sk; the tickets are left zeroed).  A
  *   lane whose block lies at or past K reads no X and feeds zero A fragments.  Deterministic, capture-safe.
  * fo_gemm_w6_head: fo_gemm_w4_head's arguments and refusals (K must be 3584): the plain form of k_w6_xs.
- * fo_gemm_w6_counts: the launches issued per form since the last reset (general, xs, sk, head) into
- *   out[0 .. min(n, 4)); returns 4.  A refused call is not counted.  These kernels have no FoLaunchKind. */
+ * fo_gemm_w6_rows: fo_gemm_w6's arguments and epilogue semantics (plain, + Y, swiglu, the RMSNorm consumer, the
+ *   producer's yg with row sums) for 17 <= M <= 64: fo_gemm_w4_rows's design on the layout above (k_w6_rows).  X is
+ *   stationary per K slice, a lane's A fragments being X[row][128 s + 32 g + 8 t .. + 7] for every row block (a lane
+ *   whose 32-column block lies at or past K reads no X and holds zeros: K % 128 may be 32, 64 or 96, and X may end at
+ *   the last row's column K); per (tile, code step) the two 12-byte plane loads and the scale byte are decoded once for
+ *   every row block; a unit is the (gate, up) pair or two adjacent plain tiles (the second tile of an odd count's last
+ *   pair lies past both descriptors, loads zero codes under a zero scale byte and is never stored).  K is split over
+ *   workgroups whenever it exceeds one workgroup's slice (S = ceil(ceil(K/128) / c) slices, c = 7 at 2 row blocks, 7
+ *   (swiglu) or 8 at 3, 7 (swiglu) or 6 at 4) and merged by a second launch in slice order, which needs `ws` of at
+ *   least S * 16 ceil(M/16) * ntiles * 16 floats; `counters` is not used.  Rows >= M are computed from a clamped row,
+ *   never stored and never summed into the row statistics.  Refused on the host before any HIP call, with the entry's
+ *   name: M outside the band ("17 <= M <= 64"), K % 32 != 0, a NULL X, q, Y or scale, ldx < K or ldx % 4 != 0 or X not
+ *   16-byte aligned, ldy < N, an ntiles that is not the packed tile count, a producer (sout) on a SwiGLU launch, codes
+ *   of 2 GiB or more, and S > 1 with `ws` missing or too small ("floats needed").  Deterministic, capture-safe.
+ *   Which launches take it is the caller's policy (fo/ops.py W6_ROWS_POLICY).
+ * fo_gemm_w6_counts: the launches issued per <= 16-row form since the last reset (general, xs, sk, head) into
+ *   out[0 .. min(n, 4)); returns 4.  fo_gemm_w6_rows_count: the calls of fo_gemm_w6_rows since the last reset
+ *   (fo_gemm_w6_counts_reset zeroes it too).  A refused call is not counted.  These kernels have no FoLaunchKind. */
 long long fo_quant_w6_bytes(int N, int K);
 long long fo_quant_w6_scale_bytes(int N, int K);
 int fo_quant_w6(const void* W, int src_bf16, int N, int K, int ldw, void* q, void* scale, void* wdq, int tile_base,
@@ -343,7 +359,12 @@ int fo_gemm_w6(const float* X, int ldx, int M, int K, const void* q, const void*
                int rgroups, float eps, float* sout, const float* gnext, float* yg, int* sgroups, hipStream_t stream);
 int fo_gemm_w6_head(const float* X, int ldx, int M, int K, const void* q, const void* scale, int ntiles, int N,
                     float* Y, int ldy, hipStream_t stream);
+int fo_gemm_w6_rows(const float* X, int ldx, int M, int K, const void* q, const void* scale, int ntiles, int N,
+                    int swiglu, float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters,
+                    const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
+                    int* sgroups, hipStream_t stream);
 int fo_gemm_w6_counts(long long* out, int n);
+long long fo_gemm_w6_rows_count(void);
 int fo_gemm_w6_counts_reset(void);
 /* The fused q|k|v projection of a Qwen2 layer under the same two formats, for calls of <= 16 rows:
  * fo_gemm_qkv_rope_kv's arguments with codes and scales in place of Wp, and no workspace, tickets or split.
