@@ -12,11 +12,17 @@
 
 static thread_local char g_err[1024] = {0};
 static std::atomic<long long> g_launches[FO_LAUNCH_KINDS];
+// the launches of the two lm_head streams (fo_gemm_head_counts: fo_gemm_w8_head, fo_gemm_w4_head) and of the two
+// quantised q|k|v streams (fo_gemm_qkv_quant_counts: fo_gemm_w8_qkv_rope, fo_gemm_w4_qkv_rope)
+static std::atomic<long long> g_head_launches[2];
+static std::atomic<long long> g_qkv_launches[2];
 
 namespace fo {
 void count_launch(int kind) {
   if (kind >= 0 && kind < FO_LAUNCH_KINDS) g_launches[kind].fetch_add(1, std::memory_order_relaxed);
 }
+void count_head(int slot) { g_head_launches[slot].fetch_add(1, std::memory_order_relaxed); }
+void count_qkv_quant(int slot) { g_qkv_launches[slot].fetch_add(1, std::memory_order_relaxed); }
 void set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -43,6 +49,23 @@ int fo_launch_counts(long long* out, int n) {
 }
 int fo_launch_counts_reset(void) {
   for (int i = 0; i < FO_LAUNCH_KINDS; ++i) g_launches[i].store(0, std::memory_order_relaxed);
+  return 0;
+}
+
+int fo_gemm_head_counts(long long* out, int n) {
+  for (int i = 0; out && i < n && i < 2; ++i) out[i] = g_head_launches[i].load(std::memory_order_relaxed);
+  return 2;
+}
+int fo_gemm_head_counts_reset(void) {
+  for (int i = 0; i < 2; ++i) g_head_launches[i].store(0, std::memory_order_relaxed);
+  return 0;
+}
+int fo_gemm_qkv_quant_counts(long long* out, int n) {
+  for (int i = 0; out && i < n && i < 2; ++i) out[i] = g_qkv_launches[i].load(std::memory_order_relaxed);
+  return 2;
+}
+int fo_gemm_qkv_quant_counts_reset(void) {
+  for (int i = 0; i < 2; ++i) g_qkv_launches[i].store(0, std::memory_order_relaxed);
   return 0;
 }
 

@@ -16,12 +16,11 @@
 //
 // Code layout (include/fo_hip.h): [tile][K128][64 lanes][16 bytes], a lane's dword j being its 8-element MFMA
 // B fragment of k-step 4 s + j (two codes per byte, the lower column in the low nibble), K padded to a multiple of
-// 128 with zero codes; scale bytes [tile][K128][16 rows][4].  fo_gemm_w4: k_w4 (general), k_w4_xs (the SwiGLU pair at
-// K = 3584) or k_w4_sk (long-K plain), the forms of fo_gemm_w8.hip; fo_gemm_w4_qkv_rope: k_w4_qkv, k_w4's pair form
-// with the fused q|k|v epilogue (bias, RoPE, paged-KV append: fo_gemm_wq.h); fo_gemm_w4_rows: k_w4_rows, then k_w8_rows_merge
-// (fo_gemm_wq.h) where K is split.
-#include <stdlib.h>
-
+// 128 with zero codes; scale bytes [tile][K128][16 rows][4].  This file holds what is MXFP4's own -- the decode, the
+// streaming inner loop, the format description Mxfp4 and the quantiser; the kernels and the host path are
+// fo_gemm_wq.h's, instantiated on Mxfp4.  fo_gemm_w4: k_wq (general), k_wq_xs (the SwiGLU pair at K = 3584) or k_wq_sk
+// (long-K plain); fo_gemm_w4_head: k_wq_xs's plain form; fo_gemm_w4_qkv_rope: k_wq_qkv; fo_gemm_w4_rows: k_wq_rows, then
+// k_wq_rows_merge where K is split.
 #include <atomic>
 
 #include "fo_gemm_wq.h"
@@ -41,42 +40,77 @@ __device__ __forceinline__ bf16x8 dec4(unsigned d, unsigned sb) {
   return __builtin_bit_cast(bf16x8, r);
 }
 
-// The two descriptors cover exactly the codes (ntiles * KK KiB) and the scale bytes (ntiles * KK * 64): a tile at or
-// past ntiles is out of range and loads zero codes under a zero scale byte (2^-127 times 0)
-struct W4Srd {
-  __amdgpu_buffer_rsrc_t q, s;
+// One lane's image of a code step: its four fragment dwords and its row's four scale bytes (byte j: k-step j)
+struct W4Code {
+  u32x4 c;
+  unsigned s;
 };
-__device__ __forceinline__ W4Srd w4_srd(const W8Args& a) {
-  return W4Srd{rsrc_of(a.Q, a.ntiles * a.KK * 1024), rsrc_of(a.scale, a.ntiles * a.KK * 64)};
+__device__ __forceinline__ W4Code w4_load(const WqMxSrd& d, int lane, int step) {   // step = tile * KK + code step
+  return W4Code{__builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(d.q, lane * 16, step * 1024, 2)),
+                wq_mx_scale(d, lane, step)};
 }
-__device__ __forceinline__ u32x4 w4_codes(const W4Srd& d, int lane, int step) {   // step = tile * KK + code step
-  return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(d.q, lane * 16, step * 1024, 2));
-}
-__device__ __forceinline__ unsigned w4_scales(const W4Srd& d, int lane, int step) {
-  return __builtin_amdgcn_raw_buffer_load_b32(d.s, (lane & 15) * 4, step * 64, 0);
-}
+
+// The format description (fo_gemm_wq.h): 128-column code steps of four fragments, 1 KiB a tile, no column scale
+struct Mxfp4 {
+  static constexpr int COLS = 128, FR = 4, STEP = 1024;
+  static constexpr bool SCALED = false;
+  typedef W4Code Code;
+  typedef WqMxSrd Srd;
+  static __device__ __forceinline__ Code zero() { return W4Code{u32x4{0u, 0u, 0u, 0u}, 0u}; }
+  static __device__ __forceinline__ Srd srd(const WqArgs& a) { return wq_mx_srd<STEP>(a); }
+  static __device__ __forceinline__ Code load(const Srd& d, int lane, int step) { return w4_load(d, lane, step); }
+  static __device__ __forceinline__ void decode(const Code& q, int, bf16x8 (&w)[FR]) {
+#pragma unroll
+    for (int h = 0; h < FR; ++h) w[h] = dec4(q.c[h], (q.s >> (8 * h)) & 0xffu);
+  }
+  // fragment j = k-step j of the wave's code steps, lane group g its columns 8 g .. + 7
+  static __device__ __forceinline__ int xcol(int g, int j) { return 8 * g + 32 * j; }
+  static __device__ __forceinline__ int xblock(int, int j) { return 32 * j; }
+  template <int NT, int U>
+  static __device__ __forceinline__ void accumulate(const WqArgs& a, const Srd& d, const float* xp, int lane, int tile0,
+                                                    int kb, int ke, f32x4 (&acc)[NT]);
+  // code steps in flight (32 X floats per code step: Fp8's register budget at half the steps); the split-K form one
+  // (two measured 18.6 / 19.5 / 21.8 us at 1 / 8 / 16 rows against 18.0 / 19.5 / 20.9 for one)
+  static constexpr int U_PAIR = 1, U_PLAIN = 2, U_SK = 1;
+  // xs: 14 waves x 2 code steps (21.0 / 23.5 us at 8 / 16 rows against 21.6 / 24.3 for 7 x 4, which FO_W4_XS=7 runs:
+  // A/B only)
+  static constexpr WqShape XS = {14, 2}, XS_ALT = {7, 4};
+  static constexpr const char* XS_ENV = "FO_W4_XS";
+  static constexpr int XS_ALT_ARG = 7;
+  // (the lo fragments stay hoisted in registers, as they always were here; re-reading them per tile fits as well -- 94
+  // against 106 VGPRs -- and timed level: profiles/gemm_wq_fold_ab.txt)
+  static constexpr bool XS_REREAD_LO = false;
+  // rows: starting from Fp8's columns per wave (7 x 2 at 2 row blocks, 7 x 1 at 3, 6 x 1 at 4) and keeping what measured
+  // best per GEMM against one alternative each (builder-run, profiles/mlp_mxfp4_rows_gemm_ab.txt; gate/up / down in
+  // us): 2 row blocks 7 x 2 (41.6 / 26.4 against 42.2 / 27.8 for 7 x 1); 3 row blocks 7 x 1 for SwiGLU (54.2 against
+  // 55.1 for 8 x 1) and 8 x 1 for plain (32.5 against 35.6 for 7 x 1); 4 row blocks 7 x 1 for SwiGLU, which reduces a
+  // tile at a time (70.9 against 73.3 for 6 x 1), and 6 x 1 for plain (45.1 against 46.3)
+  static constexpr WqShape ROWS[3][2] = {{{7, 2}, {7, 2}}, {{8, 1}, {7, 1}}, {{6, 1}, {7, 1}}};
+  static constexpr const char* GEMM = "fo_gemm_w4";
+  static constexpr const char* QUANT = "the E8M0 block bytes of fo_quant_w4";
+  static constexpr bool PAIR_CHECK = true;
+  static void count(WqForm f);
+};
 
 // acc[t] = X[rows 0..16, code steps [kb, ke)] . (packed tile tile0 + t)^T for t < NT: U code steps in flight, each X
 // fragment loaded and split once for the NT tiles.  A k-step at or past K (K % 128 != 0: zero codes) reads no X and
 // runs no MFMA.
 template <int NT, int U>
-__device__ __forceinline__ void w4_accumulate(const W8Args& a, const W4Srd& d, const float* xp, int lane, int tile0,
-                                              int kb, int ke, f32x4 (&acc)[NT]) {
+__device__ __forceinline__ void Mxfp4::accumulate(const WqArgs& a, const Srd& d, const float* xp, int lane,
+                                                    int tile0, int kb, int ke, f32x4 (&acc)[NT]) {
 #pragma unroll
   for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int k0 = kb; k0 < ke; k0 += U) {
-    u32x4 q[U][NT];
-    unsigned sc[U][NT];
+    W4Code q[U][NT];
     float4 x[U][8];
 #pragma unroll
     for (int i = 0; i < U; ++i) {
       const int kk = k0 + i;
       if (kk < ke) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          q[i][t] = w4_codes(d, lane, (tile0 + t) * a.KK + kk);
-          sc[i][t] = w4_scales(d, lane, (tile0 + t) * a.KK + kk);
-        }
+        for (int t = 0; t < NT; ++t)
+          q[i][t] = w4_load(d, lane, (tile0 + t) * a.KK + kk);
+
         const float* p = xp + (size_t)kk * 128;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -97,377 +131,13 @@ __device__ __forceinline__ void w4_accumulate(const W8Args& a, const W4Srd& d, c
             split8(x[i][2 * j], x[i][2 * j + 1], hi, lo);
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
-              const bf16x8 w = dec4(q[i][t][j], (sc[i][t] >> (8 * j)) & 0xffu);
+              const bf16x8 w = dec4(q[i][t].c[j], (q[i][t].s >> (8 * j)) & 0xffu);
               acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hi, w, acc[t], 0, 0, 0);
               acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lo, w, acc[t], 0, 0, 0);
             }
           }
       }
     }
-  }
-}
-
-// ---- general form: workgroup u = output tile u (SW: the (gate, up) pair 2u, 2u + 1); wave w takes the code steps
-// [KK w / NW, KK (w + 1) / NW), U of them (per tile) in flight
-template <int NW, bool SW>
-__global__ __launch_bounds__(NW * 64) void k_w4(W8Args a) {
-  constexpr int T = SW ? 2 : 1, U = SW ? 1 : 2;   // (32 X floats per code step: k_w8's register budget)
-  __shared__ float part[NW][T][16][17];
-  __shared__ float rstd_s[16];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int u = blockIdx.x;
-  const W4Srd d = w4_srd(a);
-  const int kb = (int)((long)a.KK * wave / NW), ke = (int)((long)a.KK * (wave + 1) / NW);
-  const int row = min(lane & 15, a.M - 1);
-  const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
-  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
-  f32x4 acc[T];
-  w4_accumulate<T, U>(a, d, xp, lane, T * u, kb, ke, acc);
-#pragma unroll
-  for (int t = 0; t < T; ++t) w8_store_tile(part[wave][t], acc[t], lane);
-  __syncthreads();
-  const int e = threadIdx.x;
-  if (e < 256) {
-    const int rr = e >> 4, c = e & 15;
-    float x1 = 0.f, x2 = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      x1 += part[w][0][rr][c];
-      if constexpr (SW) x2 += part[w][1][rr][c];
-    }
-    w8_epilogue<SW, false>(a, u, gridDim.x, rr, c, x1, x2, rstd_s);
-  }
-}
-
-// ---- the fused q|k|v projection (fo_gemm_w4_qkv_rope), as k_w8_qkv: k_w4's pair form with the RoPE + paged-KV
-// epilogue in place of SwiGLU.  Workgroup P = rope tile pair P (packed tiles 2P, 2P + 1: columns (i, i + hd/2) of one
-// head); the waves split the code steps as in k_w4 and the cross-wave sum runs in wave order.
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void k_w4_qkv(W8Args a, QkvRopeArgs r) {
-  constexpr int U = 1;
-  __shared__ float part[NW][2][16][17];
-  __shared__ float rstd_s[16];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int P = blockIdx.x;
-  const W4Srd d = w4_srd(a);
-  const int kb = (int)((long)a.KK * wave / NW), ke = (int)((long)a.KK * (wave + 1) / NW);
-  const int row = min(lane & 15, a.M - 1);
-  const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
-  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
-  f32x4 acc[2];
-  w4_accumulate<2, U>(a, d, xp, lane, 2 * P, kb, ke, acc);
-  w8_store_tile(part[wave][0], acc[0], lane);
-  w8_store_tile(part[wave][1], acc[1], lane);
-  __syncthreads();
-  const int e = threadIdx.x;
-  if (e < 256) {
-    const int rr = e >> 4, c = e & 15;
-    float x1 = 0.f, x2 = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      x1 += part[w][0][rr][c];
-      x2 += part[w][1][rr][c];
-    }
-    wq_rope_epilogue<false>(a, r, P, rr, c, x1, x2, rstd_s);
-  }
-}
-
-// ---- long-K plain form, as k_w8_sk: workgroup (tg, sp) = tiles NT tg .. + NT over the sp-th of S slices of the code
-// steps, the slice split over the waves as in k_w4.  ws: S slabs of [16][groups * NT * 16] partial sums; counters: one
-// zeroed ticket per tile group, left zeroed.  The hand-off is fo_common.h's (st_wt / ld_sc1): no fences, no waiting;
-// the last split to arrive sums every split's partial in split order.
-template <int NW, int NT>
-__global__ __launch_bounds__(NW * 64) void k_w4_sk(W8Args a, int S, float* ws, int* counters) {
-  // (two code steps in flight measured 18.6 / 19.5 / 21.8 us at 1 / 8 / 16 rows against 18.0 / 19.5 / 20.9 for one)
-  constexpr int U = 1;
-  __shared__ float part[NW][NT][16][17];
-  __shared__ float red[NT][16][17];
-  __shared__ float rstd_s[16];
-  __shared__ int last_s;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int tg = blockIdx.x, sp = blockIdx.y;
-  const W4Srd d = w4_srd(a);
-  const int k_lo = (int)((long)a.KK * sp / S), k_n = (int)((long)a.KK * (sp + 1) / S) - k_lo;
-  const int kb = k_lo + (int)((long)k_n * wave / NW), ke = k_lo + (int)((long)k_n * (wave + 1) / NW);
-  const int row = min(lane & 15, a.M - 1);
-  const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
-  if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
-  f32x4 acc[NT];
-  w4_accumulate<NT, U>(a, d, xp, lane, NT * tg, kb, ke, acc);
-#pragma unroll
-  for (int t = 0; t < NT; ++t) w8_store_tile(part[wave][t], acc[t], lane);
-  __syncthreads();
-  constexpr int NE = NT * 256, NTH = NW * 64;
-  for (int e = threadIdx.x; e < NE; e += NTH) {
-    const int t = e >> 8, rr = (e >> 4) & 15, c = e & 15;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) v += part[w][t][rr][c];
-    red[t][rr][c] = v;
-  }
-  if (S > 1) {
-    const int Ncols = gridDim.x * NT * 16;
-    const size_t sl = (size_t)16 * Ncols;
-    float* slab = ws + (size_t)sp * sl;
-    for (int e = threadIdx.x; e < NE; e += NTH) {   // (each thread stores the elements it just summed)
-      const int t = e >> 8, rr = (e >> 4) & 15, c = e & 15;
-      st_wt(slab + (size_t)rr * Ncols + (tg * NT + t) * 16 + c, red[t][rr][c]);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int* tk = counters + tg;
-      const int old = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      last_s = old == S - 1;
-      if (old == S - 1) __hip_atomic_store(tk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (!last_s) return;
-    const __amdgpu_buffer_rsrc_t rws = rsrc_of(ws);
-    for (int e = threadIdx.x; e < NE; e += NTH) {
-      const int t = e >> 8, rr = (e >> 4) & 15, c = e & 15;
-      const size_t o = (size_t)rr * Ncols + (tg * NT + t) * 16 + c;
-      const float own = red[t][rr][c];
-      float v = 0.f;
-      for (int q0 = 0; q0 < S; ++q0) v += q0 != sp ? ld_sc1(rws, q0 * sl + o) : own;
-      red[t][rr][c] = v;
-    }
-  }
-  __syncthreads();
-  const int units = (a.N + 15) / 16;
-  if (threadIdx.x < 256) {
-    const int rr = threadIdx.x >> 4, c = threadIdx.x & 15;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-      if (tg * NT + t < units) w8_epilogue<false, false>(a, tg * NT + t, units, rr, c, red[t][rr][c], 0.f, rstd_s);
-  }
-}
-
-// ---- X-stationary persistent form, as k_w8_xs: the SwiGLU pair, K = NW * KPW * 128 (3584 = 28 code steps).  X hi in
-// registers, lo in LDS, units dealt evenly to at most one workgroup per CU, the next unit's codes and scales issued
-// before the current one is reduced, a fixed-order cross-wave reduction.
-// SW = false (fo_gemm_w4_head): the plain form, as k_w8_xs's.  A unit is two adjacent plain tiles 2u, 2u + 1 (the
-// second of an odd count's last unit lies past both descriptors: zero codes under a zero scale byte, never stored),
-// each with the plain epilogue: the store, no residual, no statistics (NW * 64 >= 512: a tile per 256 threads).
-template <int NW, int KPW, bool SW = true>
-__global__ __launch_bounds__(NW * 64) void k_w4_xs(W8Args a, int units) {
-  static_assert(SW || NW >= 8, "k_w4_xs: the plain epilogue takes 512 threads");
-  __shared__ bf16x8 xlo[NW][4 * KPW][64];
-  __shared__ float part[NW][2][16][17];
-  __shared__ float rstd_s[16];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  constexpr int KK = NW * KPW;
-  const int ub = (int)((long)units * blockIdx.x / gridDim.x);
-  const int ue = (int)((long)units * (blockIdx.x + 1) / gridDim.x);
-  const W4Srd d = w4_srd(a);
-  u32x4 q0[KPW], q1[KPW];
-  unsigned s0[KPW], s1[KPW];
-  auto issue = [&](u32x4 (&q)[KPW], unsigned (&s)[KPW], int tile) {
-#pragma unroll
-    for (int j = 0; j < KPW; ++j) {
-      q[j] = w4_codes(d, lane, tile * KK + wave * KPW + j);
-      s[j] = w4_scales(d, lane, tile * KK + wave * KPW + j);
-    }
-  };
-  issue(q0, s0, ub < ue ? 2 * ub : a.ntiles);
-  issue(q1, s1, ub < ue ? 2 * ub + 1 : a.ntiles);
-  // X slice (hi in registers, lo in LDS); rows >= M clamp to the last row (computed, never stored)
-  bf16x8 xh[4 * KPW];
-  {
-    const int row = min(lane & 15, a.M - 1);
-    const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4) + (size_t)wave * KPW * 128;
-#pragma unroll
-    for (int j = 0; j < 4 * KPW; ++j) {
-      bf16x8 lo;
-      split8(reinterpret_cast<const float4*>(xp + j * 32)[0], reinterpret_cast<const float4*>(xp + j * 32)[1], xh[j],
-             lo);
-      xlo[wave][j][lane] = lo;
-    }
-  }
-  if constexpr (SW) {
-    if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane);
-  }
-  auto compute = [&](u32x4 (&q)[KPW], unsigned (&s)[KPW]) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < KPW; ++j)
-#pragma unroll
-      for (int h = 0; h < 4; ++h) {
-        const bf16x8 w = dec4(q[j][h], (s[j] >> (8 * h)) & 0xffu);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[4 * j + h], w, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xlo[wave][4 * j + h][lane], w, acc, 0, 0, 0);
-      }
-    return acc;
-  };
-  for (int u = ub; u < ue; ++u) {
-    // the next unit's codes are issued unconditionally; past the last unit they address tile `ntiles`, beyond the
-    // descriptors' range, which the hardware drops without touching memory
-    const int nxt = u + 1 < ue ? 2 * (u + 1) : a.ntiles;
-    const f32x4 c0 = compute(q0, s0);
-    issue(q0, s0, nxt);
-    const f32x4 c1 = compute(q1, s1);
-    issue(q1, s1, nxt + (u + 1 < ue ? 1 : 0));
-    __syncthreads();  // the previous unit's epilogue has read part[]
-    w8_store_tile(part[wave][0], c0, lane);
-    w8_store_tile(part[wave][1], c1, lane);
-    __syncthreads();
-    const int e = threadIdx.x;
-    if constexpr (SW) {
-      if (e < 256) {
-        const int rr = e >> 4, c = e & 15;
-        float x1 = 0.f, x2 = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-          x1 += part[w][0][rr][c];
-          x2 += part[w][1][rr][c];
-        }
-        w8_epilogue<true, false>(a, u, 0, rr, c, x1, x2, rstd_s);
-      }
-    } else if (e < 512) {
-      const int t = e >> 8, rr = (e >> 4) & 15, c = e & 15;
-      float x1 = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) x1 += part[w][t][rr][c];
-      if (2 * u + t < a.ntiles) w8_epilogue<false, false>(a, 2 * u + t, 0, rr, c, x1, 0.f, rstd_s);
-    }
-  }
-}
-
-// ---- 17..64 rows (RB = 2..4 row blocks of 16; fo_gemm_w4_rows): k_w8_rows's design (fo_gemm_w8.hip) on 128-column
-// code steps.  Workgroup (g, sp): the sp-th of S slices of the code steps for units [ub, ue) of column group g; a unit
-// is a packed tile pair (the (gate, up) pair, or two adjacent plain tiles: the second of an odd count's last pair lies
-// past both descriptors and loads zero codes under a zero scale byte).  Wave w owns KPW code steps = 4 KPW k-steps of
-// the slice: their X fragments of all RB row blocks are split once (hi in VGPRs, lo in its LDS region; k-steps at or
-// past K -- K % 128 may be 32, 64 or 96 -- hold zeros and read no X), each 16-byte code load comes with its 4-byte
-// scale load and is decoded once per unit (dec4, with the block's 2^e) to feed RB x (hi, lo) MFMAs per k-step, the
-// next unit's codes and scales in flight meanwhile.  Per unit the NW partial tiles are summed through LDS in wave
-// order (both tiles in one round where the LDS allows).  S == 1: the epilogue follows.  S > 1: the sums are stored as
-// split sp's slab of `ws` ([S][RB * 16][ntiles * 16] floats) and k_w8_rows_merge (fo_gemm_wq.h, unscaled), the next
-// launch, sums the slabs in split order and runs the epilogue.
-template <int NW, int KPW, int RB, bool SW>
-__global__ __launch_bounds__(NW * 64) void k_w4_rows(W8Args a, int S, int per, float* ws) {
-  constexpr int ROWS = RB * 16, NTH = NW * 64, NE = ROWS * 16, EPT = (NE + NTH - 1) / NTH;
-  constexpr int PT = (NW * RB * 4 * KPW * 1024 + NW * 2 * ROWS * 17 * 4 + 512 <= 160 * 1024) ? 2 : 1;
-  __shared__ bf16x8 xlo[NW][RB][4 * KPW][64];
-  __shared__ float part[NW][PT][ROWS][17];
-  __shared__ float rstd_s[ROWS];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int G = gridDim.x, g = blockIdx.x, sp = blockIdx.y;
-  const int units = (a.ntiles + 1) >> 1, tiles = (a.N + 15) / 16;   // (tiles: output tiles, the statistics' groups)
-  const int ub = (int)((long)units * g / G), ue = (int)((long)units * (g + 1) / G);
-  const W4Srd d = w4_srd(a);   // (exactly the codes and the scale bytes)
-  // this wave's code steps: [k0, k0 + nj) inside the slice [sp * per, (sp + 1) * per) and inside KK (wave-uniform)
-  const int k0 = sp * per + wave * KPW;
-  const int nj = max(0, min(KPW, min(a.KK, (sp + 1) * per) - k0));
-  u32x4 q[2][2][KPW];
-  unsigned sc[2][2][KPW];
-  auto issue = [&](u32x4 (&qq)[2][KPW], unsigned (&ss)[2][KPW], int u) {   // u >= ue: no load issued
-    if (u < ue) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int j = 0; j < KPW; ++j)
-          if (j < nj) {
-            qq[t][j] = w4_codes(d, lane, (2 * u + t) * a.KK + k0 + j);
-            ss[t][j] = w4_scales(d, lane, (2 * u + t) * a.KK + k0 + j);
-          }
-    }
-  };
-#pragma unroll
-  for (int b = 0; b < 2; ++b)
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int j = 0; j < KPW; ++j) {   // code steps past the slice: zero codes under a zero scale byte
-        q[b][t][j] = u32x4{0u, 0u, 0u, 0u};
-        sc[b][t][j] = 0u;
-      }
-  issue(q[0], sc[0], ub);
-  issue(q[1], sc[1], ub + 1);
-  bf16x8 zero;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) zero[i] = (__bf16)0.f;
-  bf16x8 xh[RB][4 * KPW];
-#pragma unroll
-  for (int r = 0; r < RB; ++r) {
-    const int row = min(r * 16 + (lane & 15), a.M - 1);   // rows >= M: computed, never stored or summed
-    const float* xp = a.X + (size_t)row * a.ldx + 8 * (lane >> 4);
-#pragma unroll
-    for (int j = 0; j < 4 * KPW; ++j) {
-      bf16x8 hi = zero, lo = zero;
-      const int col = (4 * k0 + j) * 32;   // (K % 128 != 0: the last code step's k-steps at or past K)
-      if ((j >> 2) < nj && col < a.K)
-        split8(reinterpret_cast<const float4*>(xp + col)[0], reinterpret_cast<const float4*>(xp + col)[1], hi, lo);
-      xh[r][j] = hi;
-      xlo[wave][r][j][lane] = lo;
-    }
-  }
-  if (S == 1) {   // the consumer's rstd of every row (rows >= M from the clamped row)
-    if (a.rstats) w8_rstd<NW>(a, rstd_s, wave, lane, 0, ROWS);
-    __syncthreads();
-  }
-  const int Ncols = a.ntiles * 16;
-  float* slab = ws + (size_t)sp * ROWS * Ncols;
-  auto unit = [&](u32x4 (&qq)[2][KPW], unsigned (&ss)[2][KPW], int u) {
-    float v[2][EPT];
-#pragma unroll
-    for (int t0 = 0; t0 < 2; t0 += PT) {
-      f32x4 acc[PT][RB];
-#pragma unroll
-      for (int p = 0; p < PT; ++p) {
-#pragma unroll
-        for (int r = 0; r < RB; ++r) acc[p][r] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < KPW; ++j)
-#pragma unroll
-          for (int h = 0; h < 4; ++h) {
-            const bf16x8 w = dec4(qq[t0 + p][j][h], (ss[t0 + p][j] >> (8 * h)) & 0xffu);
-#pragma unroll
-            for (int r = 0; r < RB; ++r) {
-              acc[p][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[r][4 * j + h], w, acc[p][r], 0, 0, 0);
-              acc[p][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xlo[wave][r][4 * j + h][lane], w, acc[p][r], 0, 0, 0);
-            }
-          }
-      }
-      if (t0 + PT == 2) issue(qq, ss, u + 2);   // (the unit's codes are decoded: its buffer takes the unit after next)
-      __syncthreads();  // the previous reduction has read part[]
-#pragma unroll
-      for (int p = 0; p < PT; ++p)
-#pragma unroll
-        for (int r = 0; r < RB; ++r) w8_store_tile(part[wave][p], acc[p][r], lane, r * 16);
-      __syncthreads();
-#pragma unroll
-      for (int p = 0; p < PT; ++p)
-#pragma unroll
-        for (int i = 0; i < EPT; ++i) {
-          const int e = threadIdx.x + i * NTH;
-          float s = 0.f;
-          if (e < NE) {
-#pragma unroll
-            for (int w = 0; w < NW; ++w) s += part[w][p][e >> 4][e & 15];
-            if (S > 1 && 2 * u + t0 + p < a.ntiles)
-              slab[(size_t)(e >> 4) * Ncols + (2 * u + t0 + p) * 16 + (e & 15)] = s;
-          }
-          v[t0 + p][i] = s;
-        }
-    }
-    if (S == 1) {
-#pragma unroll
-      for (int i = 0; i < EPT; ++i) {
-        const int e = threadIdx.x + i * NTH;   // (NTH % 16 == 0: a row's 16 columns are one 16-lane row of a wave)
-        const int rr = e < NE ? e >> 4 : ROWS, c = e & 15;
-        if constexpr (SW) {
-          w8_epilogue<true, false>(a, u, tiles, rr, c, v[0][i], v[1][i], rstd_s);
-        } else {
-          w8_epilogue<false, false>(a, 2 * u, tiles, rr, c, v[0][i], 0.f, rstd_s);
-          if (2 * u + 1 < a.ntiles) w8_epilogue<false, false>(a, 2 * u + 1, tiles, rr, c, v[1][i], 0.f, rstd_s);
-        }
-      }
-    }
-  };
-  for (int u = ub; u < ue; u += 2) {   // (workgroup-uniform: every wave reaches unit's barriers)
-    unit(q[0], sc[0], u);
-    if (u + 1 < ue) unit(q[1], sc[1], u + 1);
   }
 }
 
@@ -528,61 +198,28 @@ __global__ __launch_bounds__(256) void k_quant_w4(const void* W, int src_bf16, i
   }
 }
 
-int g_cus = 0;
-int w4_cus() {
-  if (!g_cus) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    g_cus = n;
-  }
-  return g_cus;
-}
-
 // the launch counters of the three <= 16-row forms (fo_gemm_w4_counts): general, xs, sk; and the calls of
 // fo_gemm_w4_rows (fo_gemm_w4_rows_count)
 std::atomic<long long> g_w4_launches[3];
 std::atomic<long long> g_w4_rows_calls;
-// the launches of the two lm_head streams (fo_gemm_head_counts): fo_gemm_w8_head, fo_gemm_w4_head
-std::atomic<long long> g_head_launches[2];
-// the launches of the two quantised q|k|v streams (fo_gemm_qkv_quant_counts): fo_gemm_w8_qkv_rope, fo_gemm_w4_qkv_rope
-std::atomic<long long> g_qkv_launches[2];
-
-// What the two GEMM entries share: the checks of everything but the workspace (all before the entry's first HIP call),
-// then W8Args (with KK) and the output tile count.  `fn` is the entry's name, [m_lo, m_hi] its row band and `serves`
-// what its refusal says of the band.
-int w4_args(const char* fn, int m_lo, int m_hi, const char* serves, const float* X, int ldx, int M, int K, const void* Q,
-            const void* scale, int ntiles, int N, int swiglu, float* Y, int ldy, int residual, const float* rstats,
-            int rgroups, float eps, float* sout, const float* gnext, float* yg, W8Args& a, int& units) {
-  FO_REQUIRE(M > 0 && N > 0 && K > 0, "%s: bad shape M=%d N=%d K=%d", fn, M, N, K);
-  FO_REQUIRE(M >= m_lo && M <= m_hi, "%s: M=%d rows, %s", fn, M, serves);
-  FO_REQUIRE((K & 31) == 0, "%s: K=%d must be a multiple of 32", fn, K);
-  FO_REQUIRE(X && Q && Y, "%s: NULL X, Q or Y", fn);
-  FO_REQUIRE(scale, "%s: NULL scale (the E8M0 block bytes of fo_quant_w4)", fn);
-  FO_REQUIRE(ldx >= K && (ldx & 3) == 0 && ((unsigned long long)X & 15) == 0,
-             "%s: X needs ldx=%d >= K=%d, ldx %% 4 == 0 and 16-byte alignment", fn, ldx, K);
-  FO_REQUIRE(ldy >= N, "%s: ldy=%d < N=%d", fn, ldy, N);
-  units = (N + 15) / 16;
-  FO_REQUIRE(!swiglu || (ntiles & 1) == 0, "%s: swiglu with an odd ntiles=%d (gate/up tiles come in pairs)", fn, ntiles);
-  // ntiles is the extent of Q and scale (the descriptors' range): (gate, up) pairs for SwiGLU
-  FO_REQUIRE(ntiles == (swiglu ? 2 : 1) * units, "%s: ntiles=%d packed tiles for N=%d%s", fn, ntiles, N,
-             swiglu ? " SwiGLU columns" : " columns");
-  FO_REQUIRE(!rstats || rgroups > 0, "%s: rstats without rgroups", fn);
-  FO_REQUIRE(!sout || (!swiglu && (!yg || gnext)), "%s: sout needs a non-SwiGLU launch, yg needs gnext", fn);
-  FO_REQUIRE(sout || !yg, "%s: yg comes with sout", fn);
-  FO_REQUIRE(!(swiglu && residual), "%s: swiglu with residual unsupported", fn);
-  const int KK = (K + 127) / 128;
-  FO_REQUIRE((long long)(ntiles + 4) * KK * 1024 < (1ll << 31), "%s: ntiles=%d x K=%d codes exceed 2 GiB", fn, ntiles, K);
-  a = W8Args{X,        Q,    reinterpret_cast<const float*>(scale), Y,  ldx,    ldy,     M, K, N, ntiles, KK,
-             residual, sout, gnext,                                 yg, rstats, rgroups, eps};
-  return 0;
+void Mxfp4::count(WqForm f) {
+  if (f == WQ_HEAD) fo::count_head(1);
+  else if (f == WQ_QKV) fo::count_qkv_quant(1);
+  else if (f == WQ_ROWS) g_w4_rows_calls.fetch_add(1, std::memory_order_relaxed);
+  else g_w4_launches[f].fetch_add(1, std::memory_order_relaxed);   // (WQ_GENERAL, WQ_XS, WQ_SK: slots 0..2)
 }
 
-}  // namespace
+// the entries: name, row band, what the refusal says of the band
+constexpr WqEntry E_GEMM = {"fo_gemm_w4", 1, 16, "the MXFP4 stream serves M <= 16 (more rows run the bf16 image)"};
+constexpr WqEntry E_HEAD = {"fo_gemm_w4_head", 1, 16,
+                            "the MXFP4 head stream serves M <= 16 (more rows run the bf16 image)"};
+constexpr WqEntry E_QKV = {"fo_gemm_w4_qkv_rope", 1, 16,
+                           "the MXFP4 q|k|v stream serves M <= 16 (more rows run the bf16 image)"};
+constexpr WqEntry E_ROWS = {"fo_gemm_w4_rows", 17, 64,
+                            "this MXFP4 stream serves 17 <= M <= 64 (fo_gemm_w4 serves M <= 16, more than 64 rows run "
+                            "the bf16 image)"};
 
-void fo::count_head(int slot) { g_head_launches[slot].fetch_add(1, std::memory_order_relaxed); }
-void fo::count_qkv_quant(int slot) { g_qkv_launches[slot].fetch_add(1, std::memory_order_relaxed); }
+}  // namespace
 
 extern "C" {
 
@@ -616,169 +253,27 @@ long long fo_gemm_w4_rows_count(void) { return g_w4_rows_calls.load(std::memory_
 int fo_gemm_w4(const float* X, int ldx, int M, int K, const void* Q, const void* scale, int ntiles, int N, int swiglu,
                float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters, const float* rstats,
                int rgroups, float eps, float* sout, const float* gnext, float* yg, int* sgroups, hipStream_t stream) {
-  // every check before the first HIP call
-  W8Args a;
-  int units;
-  if (const int rc = w4_args("fo_gemm_w4", 1, 16, "the MXFP4 stream serves M <= 16 (more rows run the bf16 image)", X, ldx,
-                             M, K, Q, scale, ntiles, N, swiglu, Y, ldy, residual, rstats, rgroups, eps, sout, gnext, yg,
-                             a, units))
-    return rc;
-  const int KK = a.KK;
-  if (sgroups) *sgroups = units;
-  if (swiglu && K == 3584) {
-    const int G = units < w4_cus() ? units : w4_cus();
-    // 14 waves x 2 code steps (21.0 / 23.5 us at 8 / 16 rows against 21.6 / 24.3 for 7 x 4, which FO_W4_XS=7 runs:
-    // A/B only)
-    static const bool w7 = [] { const char* e = getenv("FO_W4_XS"); return e && atoi(e) == 7; }();
-    if (w7) hipLaunchKernelGGL((k_w4_xs<7, 4>), dim3(G), dim3(448), 0, stream, a, units);
-    else hipLaunchKernelGGL((k_w4_xs<14, 2>), dim3(G), dim3(896), 0, stream, a, units);
-    g_w4_launches[1].fetch_add(1, std::memory_order_relaxed);
-    return fo::check_launch("fo_gemm_w4 (xs)");
-  }
-  // long-K plain projections (the Qwen2 down: 224 tiles x 148 code steps): 4 tiles per workgroup, K split over the
-  // workgroups until the grid is about one workgroup per CU, merged in the launch (needs the caller's workspace and
-  // zeroed tickets; without them the one-tile form below serves)
-  if (!swiglu && KK >= 64 && units >= 16 && ws && counters) {
-    constexpr int NT = 4, NW = 8;
-    const int groups = (units + NT - 1) / NT;
-    int S = w4_cus() / groups;
-    S = S < 1 ? 1 : (S > 8 ? 8 : S);
-    if (S == 1 || ((long long)S * 16 * groups * NT * 16 <= ws_floats && groups <= (1 << 20))) {
-      hipLaunchKernelGGL((k_w4_sk<NW, NT>), dim3(groups, S), dim3(NW * 64), 0, stream, a, S, ws, counters);
-      g_w4_launches[2].fetch_add(1, std::memory_order_relaxed);
-      return fo::check_launch("fo_gemm_w4 (split K)");
-    }
-  }
-  const bool wide = KK >= 16;
-  if (swiglu) {
-    if (wide) hipLaunchKernelGGL((k_w4<16, true>), dim3(units), dim3(1024), 0, stream, a);
-    else hipLaunchKernelGGL((k_w4<4, true>), dim3(units), dim3(256), 0, stream, a);
-  } else {
-    if (wide) hipLaunchKernelGGL((k_w4<16, false>), dim3(units), dim3(1024), 0, stream, a);
-    else hipLaunchKernelGGL((k_w4<4, false>), dim3(units), dim3(256), 0, stream, a);
-  }
-  g_w4_launches[0].fetch_add(1, std::memory_order_relaxed);
-  return fo::check_launch("fo_gemm_w4");
-}
-
-int fo_gemm_head_counts(long long* out, int n) {
-  for (int i = 0; out && i < n && i < 2; ++i) out[i] = g_head_launches[i].load(std::memory_order_relaxed);
-  return 2;
-}
-int fo_gemm_head_counts_reset(void) {
-  for (int i = 0; i < 2; ++i) g_head_launches[i].store(0, std::memory_order_relaxed);
-  return 0;
+  return wq_gemm<Mxfp4>(E_GEMM, FO_WQ_CALL);
 }
 
 int fo_gemm_w4_head(const float* X, int ldx, int M, int K, const void* Q, const void* scale, int ntiles, int N,
                     float* Y, int ldy, hipStream_t stream) {
-  // every check before the first HIP call
-  W8Args a;
-  int tiles;
-  if (const int rc = w4_args("fo_gemm_w4_head", 1, 16,
-                             "the MXFP4 head stream serves M <= 16 (more rows run the bf16 image)", X, ldx, M, K, Q,
-                             scale, ntiles, N, 0, Y, ldy, 0, nullptr, 0, 0.f, nullptr, nullptr, nullptr, a, tiles))
-    return rc;
-  FO_REQUIRE(K == 3584, "fo_gemm_w4_head: K=%d, the X-stationary plain form is compiled for K = 3584 (fo_gemm_w4 serves "
-             "any other K)", K);
-  // units of two adjacent plain tiles dealt evenly to at most one workgroup per CU; the SwiGLU form's wave shape
-  // (14 waves x 2 code steps)
-  const int units = (ntiles + 1) / 2;
-  const int G = units < w4_cus() ? units : w4_cus();
-  hipLaunchKernelGGL((k_w4_xs<14, 2, false>), dim3(G), dim3(896), 0, stream, a, units);
-  fo::count_head(1);
-  return fo::check_launch("fo_gemm_w4_head");
-}
-
-int fo_gemm_qkv_quant_counts(long long* out, int n) {
-  for (int i = 0; out && i < n && i < 2; ++i) out[i] = g_qkv_launches[i].load(std::memory_order_relaxed);
-  return 2;
-}
-int fo_gemm_qkv_quant_counts_reset(void) {
-  for (int i = 0; i < 2; ++i) g_qkv_launches[i].store(0, std::memory_order_relaxed);
-  return 0;
+  return wq_head<Mxfp4>(E_HEAD, X, ldx, M, K, Q, scale, ntiles, N, Y, ldy, stream);
 }
 
 int fo_gemm_w4_qkv_rope(const float* X, int ldx, int M, int K, const void* Q, const void* scale, int ntiles, int N,
                         const float* bias, const float* rstats, int rgroups, float eps, const int* pos, const int* slot,
                         const float* cos_t, const float* sin_t, float* q_out, void* kc, void* vc, int H, int KVH, int hd,
                         int PS, int kv_bytes, hipStream_t stream) {
-  // every check before the first HIP call (q_out stands where w4_args expects an output: N floats per row)
-  W8Args a;
-  QkvRopeArgs r;
-  int tiles;
-  if (const int rc = w4_args("fo_gemm_w4_qkv_rope", 1, 16,
-                             "the MXFP4 q|k|v stream serves M <= 16 (more rows run the bf16 image)", X, ldx, M, K, Q,
-                             scale, ntiles, N, 0, q_out, N, 0, rstats, rgroups, eps, nullptr, nullptr, nullptr, a, tiles))
-    return rc;
-  if (const int rc = qkv_rope_args("fo_gemm_w4_qkv_rope", N, bias, pos, slot, cos_t, sin_t, q_out, kc, vc, H, KVH, hd,
-                                   PS, kv_bytes, r))
-    return rc;
-  // one workgroup per rope tile pair (Qwen2-7B: 144); 16 waves where each still gets a code step
-  const int pairs = ntiles / 2;
-  if (a.KK >= 16) hipLaunchKernelGGL((k_w4_qkv<16>), dim3(pairs), dim3(1024), 0, stream, a, r);
-  else hipLaunchKernelGGL((k_w4_qkv<4>), dim3(pairs), dim3(256), 0, stream, a, r);
-  fo::count_qkv_quant(1);
-  return fo::check_launch("fo_gemm_w4_qkv_rope");
+  return wq_qkv_rope<Mxfp4>(E_QKV, X, ldx, M, K, Q, scale, ntiles, N, bias, rstats, rgroups, eps, pos, slot, cos_t,
+                            sin_t, q_out, kc, vc, H, KVH, hd, PS, kv_bytes, stream);
 }
 
 int fo_gemm_w4_rows(const float* X, int ldx, int M, int K, const void* Q, const void* scale, int ntiles, int N,
                     int swiglu, float* Y, int ldy, int residual, float* ws, long long ws_floats, int* counters,
                     const float* rstats, int rgroups, float eps, float* sout, const float* gnext, float* yg,
                     int* sgroups, hipStream_t stream) {
-  // every check before the first HIP call
-  W8Args a;
-  int units;
-  if (const int rc = w4_args("fo_gemm_w4_rows", 17, 64,
-                             "this MXFP4 stream serves 17 <= M <= 64 (fo_gemm_w4 serves M <= 16, more than 64 rows run "
-                             "the bf16 image)",
-                             X, ldx, M, K, Q, scale, ntiles, N, swiglu, Y, ldy, residual, rstats, rgroups, eps, sout,
-                             gnext, yg, a, units))
-    return rc;
-  const int KK = a.KK;
-  // NW waves x KPW code steps of X per K slice (hi in VGPRs, lo in LDS), starting from fo_gemm_w8_rows's columns per
-  // wave (7 x 2 at 2 row blocks, 7 x 1 at 3, 6 x 1 at 4) and keeping what measured best per GEMM against one
-  // alternative each (builder-run, profiles/mlp_mxfp4_rows_gemm_ab.txt; gate/up / down in us): 2 row blocks 7 x 2
-  // (41.6 / 26.4 against 42.2 / 27.8 for 7 x 1); 3 row blocks 7 x 1 for SwiGLU (54.2 against 55.1 for 8 x 1) and 8 x 1
-  // for plain (32.5 against 35.6 for 7 x 1); 4 row blocks 7 x 1 for SwiGLU, which reduces a tile at a time (70.9
-  // against 73.3 for 6 x 1), and 6 x 1 for plain (45.1 against 46.3).  S slices of `per` code steps, units of two
-  // packed tiles, about one workgroup per CU.  S > 1: the slabs are merged by a second launch (k_w8_rows_merge), one
-  // small workgroup per (tile, row block)
-  const int RB = (M + 15) / 16;
-  const int NW = RB == 2 ? 7 : (RB == 3 ? (swiglu ? 7 : 8) : (swiglu ? 7 : 6)), KPW = RB == 2 ? 2 : 1;
-  const int S = (KK + NW * KPW - 1) / (NW * KPW), per = (KK + S - 1) / S;
-  const int pairs = (ntiles + 1) / 2;
-  const int per_split = w4_cus() / S < 1 ? 1 : w4_cus() / S;
-  const int G = pairs < per_split ? pairs : per_split;
-  if (S > 1) {
-    const long long need = (long long)S * RB * 16 * ntiles * 16;
-    FO_REQUIRE(ws && need <= ws_floats,
-               "fo_gemm_w4_rows: K=%d splits over %d workgroups: split-K workspace too small (%lld floats needed, "
-               "%lld given)", K, S, need, ws ? ws_floats : 0ll);
-  }
-  (void)counters;
-  if (sgroups) *sgroups = units;
-  const dim3 grid(G, S), block(NW * 64);
-#define FO_W4_ROWS(NW_, KPW_, RB_, SW_) \
-  hipLaunchKernelGGL((k_w4_rows<NW_, KPW_, RB_, SW_>), grid, block, 0, stream, a, S, per, ws)
-  if (RB == 2) {
-    if (swiglu) FO_W4_ROWS(7, 2, 2, true);
-    else FO_W4_ROWS(7, 2, 2, false);
-  } else if (RB == 3) {
-    if (swiglu) FO_W4_ROWS(7, 1, 3, true);
-    else FO_W4_ROWS(8, 1, 3, false);
-  } else {
-    if (swiglu) FO_W4_ROWS(7, 1, 4, true);
-    else FO_W4_ROWS(6, 1, 4, false);
-  }
-#undef FO_W4_ROWS
-  if (S > 1) {
-    const int rc = fo::check_launch("fo_gemm_w4_rows");
-    if (rc) return rc;
-    launch_merge<false>(a, swiglu, units, RB, S, ws, stream);
-  }
-  g_w4_rows_calls.fetch_add(1, std::memory_order_relaxed);
-  return fo::check_launch("fo_gemm_w4_rows");
+  return wq_rows<Mxfp4>(E_ROWS, FO_WQ_CALL);
 }
 
 }  // extern "C"

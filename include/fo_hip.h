@@ -170,12 +170,12 @@ enum FoLaunchKind {
   FO_L_ATTN_O = 17,     /* k_attn_decode_o: decode attention + o projection + residual + next-norm statistics */
   FO_L_ENC_BLOCK = 18,  /* k_enc_attn_block: the attention half of a speech-encoder block */
   FO_L_GEMM_ROWS = 19,  /* k_gemm_rows: 65..128 rows, the waves split the rows, weights shared through an LDS ring */
-  FO_L_GEMM_W8 = 20,    /* k_w8: the general <= 16-row FP8-weight GEMM (fo_gemm_w8) */
-  FO_L_GEMM_W8_XS = 21, /* k_w8_xs: the X-stationary FP8-weight gate/up stream (fo_gemm_w8, SwiGLU at K = 3584) */
-  FO_L_GEMM_W8_ROWS = 22, /* k_w8_rows (+ its merge): the 17..64-row X-stationary split-K FP8-weight stream (fo_gemm_w8_rows) */
+  FO_L_GEMM_W8 = 20,    /* k_wq<Fp8>: the general <= 16-row FP8-weight GEMM (fo_gemm_w8) */
+  FO_L_GEMM_W8_XS = 21, /* k_wq_xs<Fp8>: the X-stationary FP8-weight gate/up stream (fo_gemm_w8, SwiGLU at K = 3584) */
+  FO_L_GEMM_W8_ROWS = 22, /* k_wq_rows<Fp8> (+ its merge): the 17..64-row X-stationary split-K FP8-weight stream (fo_gemm_w8_rows) */
   FO_L_ATTN_GQA_DECODE = 23, /* k_attn_gqa_decode: one-token GQA steps at head_dim 128 (the Qwen2 text step); per item the
                                 single-row fp32 body up to GQA_DEC_KEYS keys, the multi-row split body beyond */
-  FO_L_GEMM_W8_ROWS128 = 24, /* k_w8_rows128 (+ k_w8_rows_merge): the 65..128-row FP8-weight stream, the waves split the
+  FO_L_GEMM_W8_ROWS128 = 24, /* k_w8_rows128 (+ k_wq_rows_merge): the 65..128-row FP8-weight stream, the waves split the
                                 rows, codes shared through an LDS ring (fo_gemm_w8_rows128) */
   FO_LAUNCH_KINDS = 24 + 1 /* the 24 kinds up to FO_L_ATTN_GQA_DECODE, then FO_L_GEMM_W8_ROWS128 (written as a sum:
                                tests/test_mlp_fp8_rows_cpu.py pins the text of the first 24) */
@@ -207,17 +207,17 @@ int fo_launch_counts_reset(void);
  *   counters are
  *   fo_gemm's (scratch floats, and zeroed ints that are left zeroed).  Where K is split over workgroups the partial
  *   sums are added in split order: deterministic in every form.  Every launch is capture-safe.
- *   - fo_gemm_w8, M <= 16: one workgroup per output tile, its waves splitting K (k_w8); the SwiGLU pair at K = 3584
- *     X-stationary and persistent (k_w8_xs, FO_L_GEMM_W8_XS); long-K plain launches (the Qwen2 down) split K across
+ *   - fo_gemm_w8, M <= 16: one workgroup per output tile, its waves splitting K (k_wq<Fp8>); the SwiGLU pair at K = 3584
+ *     X-stationary and persistent (k_wq_xs<Fp8>, FO_L_GEMM_W8_XS); long-K plain launches (the Qwen2 down) split K across
  *     workgroups and merge inside the launch where ws and counters are given (both may be NULL).  FO_L_GEMM_W8.
- *   - fo_gemm_w8_rows, 17 <= M <= 64: X stationary per K slice (k_w8_rows), K split over workgroups whenever it
+ *   - fo_gemm_w8_rows, 17 <= M <= 64: X stationary per K slice (k_wq_rows<Fp8>), K split over workgroups whenever it
  *     exceeds one slice (28 / 14 / 12 code steps at 2 / 3 / 4 row blocks of 16).  A split launch needs ws (slices x
- *     16 ceil(M/16) x 16 ntiles floats, checked against ws_floats) and is followed by k_w8_rows_merge, which sums the
+ *     16 ceil(M/16) x 16 ntiles floats, checked against ws_floats) and is followed by k_wq_rows_merge, which sums the
  *     slices and runs the epilogue.  counters is not used.  One call counts one FO_L_GEMM_W8_ROWS.
  *   - fo_gemm_w8_rows128, 65 <= M <= 128: k_gemm_rows's design on the codes (k_w8_rows128: the 8 waves of a
  *     workgroup split the row blocks and share each code step's fragments through an LDS-DMA ring; SwiGLU in up to 3
  *     K slices, plain in up to 16, never more than code steps).  Every call needs ws (as above: a short one is
- *     refused with both figures, nothing launched) and is followed by k_w8_rows_merge.  counters is not used.  One
+ *     refused with both figures, nothing launched) and is followed by k_wq_rows_merge.  counters is not used.  One
  *     call counts one FO_L_GEMM_W8_ROWS128. */
 long long fo_quant_w8_bytes(int N, int K);
 int fo_quant_w8(const void* W, int src_bf16, int N, int K, int ldw, void* q, float* scale, void* wdq, int tile_base,
@@ -253,11 +253,11 @@ int fo_gemm_w8_rows128(const float* X, int ldx, int M, int K, const void* q, con
  *   with `scale` the E8M0 bytes, applied as the codes are decoded to bf16 (v_cvt_scalef32_pk_bf16_fp4), so the fp32
  *   sums need no column scale.  M <= 16 only: any other M, K % 32 != 0, an ntiles that is not the weight's, a NULL
  *   scale and a producer on a SwiGLU launch are refused on the host before any HIP call; more rows run the bf16 image
- *   through fo_gemm.  One workgroup per output tile, its waves splitting K (k_w4); the SwiGLU pair at K = 3584
- *   X-stationary and persistent (k_w4_xs); long-K plain launches (the Qwen2 down) split K across workgroups and
- *   merge inside the launch in split order where ws and counters are given (k_w4_sk).  Deterministic, capture-safe.
+ *   through fo_gemm.  One workgroup per output tile, its waves splitting K (k_wq<Mxfp4>); the SwiGLU pair at K = 3584
+ *   X-stationary and persistent (k_wq_xs<Mxfp4>); long-K plain launches (the Qwen2 down) split K across workgroups and
+ *   merge inside the launch in split order where ws and counters are given (k_wq_sk<Mxfp4>).  Deterministic, capture-safe.
  * fo_gemm_w4_rows: fo_gemm_w4's arguments and epilogue semantics for 17 <= M <= 64 (fo_gemm_w8_rows's design on the
- *   128-column code steps, k_w4_rows): X stationary per K slice, the codes decoded once per unit for every row block,
+ *   128-column code steps, k_wq_rows<Mxfp4>): X stationary per K slice, the codes decoded once per unit for every row block,
  *   K split over workgroups whenever it exceeds one workgroup's slice (S = ceil(ceil(K/128) / c) slices, c = 14 at 2
  *   row blocks, 7 (swiglu) or 8 at 3, 7 (swiglu) or 6 at 4) and merged by a second launch in slice order, which needs
  *   `ws` of at least S * 16 ceil(M/16) * ntiles * 16 floats; `counters` is not used.  The refusals are fo_gemm_w4's,
@@ -290,7 +290,7 @@ int fo_gemm_w4_counts_reset(void);
  * tile_base 0 and tile_stride 1 (FP8: codes [tile][56][64 lanes][16 bytes] and fp32 2^e at [tile][16]; MXFP4: codes
  * [tile][28][64 lanes][16 bytes] and E8M0 bytes at [tile][28][16 rows][4]); ntiles = ceil(N/16) is their extent.  X is
  * fp32 [M][ldx] (split into bf16 hi + lo), Y fp32 [M][ldy].
- * Kernel: the plain form of the X-stationary persistent kernels (k_w8_xs / k_w4_xs), compiled for K = 3584: X hi in
+ * Kernel: the plain form of the X-stationary persistent kernels (k_wq_xs<Fp8> / k_wq_xs<Mxfp4>), compiled for K = 3584: X hi in
  * registers and lo in LDS, split once per workgroup; min(units, CUs) workgroups with the units dealt evenly, a unit
  * being the adjacent tiles 2u, 2u + 1 (the second tile of an odd count's last unit lies past the code descriptor --
  * and, for MXFP4, the scale descriptor -- loads zeros and is never stored); the next unit's codes are issued before
@@ -327,13 +327,13 @@ int fo_gemm_head_counts_reset(void);
  *   [N][K]); bit-equal to the CPU definition.
  * fo_gemm_w6: fo_gemm_w4's arguments, epilogue semantics and refusals (M outside 1..16, K % 32 != 0, NULL pointers, an
  *   ntiles that is not the packed tile count, codes of 2 GiB or more, ...: all on the host before any HIP call, with
- *   the entry's name).  One workgroup per output tile or SwiGLU pair, its waves splitting the code steps (k_w6); the
- *   SwiGLU pair at K = 3584 X-stationary and persistent (k_w6_xs); long-K plain launches split K across workgroups and
- *   merge inside the launch in split order where ws and counters are given (k_w6_sk; the tickets are left zeroed).  A
+ *   the entry's name).  One workgroup per output tile or SwiGLU pair, its waves splitting the code steps (k_wq<Mxfp6>); the
+ *   SwiGLU pair at K = 3584 X-stationary and persistent (k_wq_xs<Mxfp6>); long-K plain launches split K across workgroups and
+ *   merge inside the launch in split order where ws and counters are given (k_wq_sk<Mxfp6>; the tickets are left zeroed).  A
  *   lane whose block lies at or past K reads no X and feeds zero A fragments.  Deterministic, capture-safe.
- * fo_gemm_w6_head: fo_gemm_w4_head's arguments and refusals (K must be 3584): the plain form of k_w6_xs.
+ * fo_gemm_w6_head: fo_gemm_w4_head's arguments and refusals (K must be 3584): the plain form of k_wq_xs<Mxfp6>.
  * fo_gemm_w6_rows: fo_gemm_w6's arguments and epilogue semantics (plain, + Y, swiglu, the RMSNorm consumer, the
- *   producer's yg with row sums) for 17 <= M <= 64: fo_gemm_w4_rows's design on the layout above (k_w6_rows).  X is
+ *   producer's yg with row sums) for 17 <= M <= 64: fo_gemm_w4_rows's design on the layout above (k_wq_rows<Mxfp6>).  X is
  *   stationary per K slice, a lane's A fragments being X[row][128 s + 32 g + 8 t .. + 7] for every row block (a lane
  *   whose 32-column block lies at or past K reads no X and holds zeros: K % 128 may be 32, 64 or 96, and X may end at
  *   the last row's column K); per (tile, code step) the two 12-byte plane loads and the scale byte are decoded once for
@@ -373,7 +373,7 @@ int fo_gemm_w6_counts_reset(void);
  * h * hd + p * hd/2 go to packed tiles h * (hd/16) + p, + 2, ... (one fo_quant_* call per (head, half) with tile_base
  * h * (hd/16) + p and tile_stride 2), so adjacent packed tiles (2P, 2P + 1) hold columns (i, i + hd/2) of one head;
  * ntiles = N / 16 is their extent.  X is fp32 [M][ldx] (split into bf16 hi + lo).
- * Kernel: the pair form of the general kernels (k_w8 / k_w4): workgroup P owns tile pair P (N / 32 workgroups), the
+ * Kernel: the pair form of the general kernels (k_wq<Fp8> / k_wq<Mxfp4>): workgroup P owns tile pair P (N / 32 workgroups), the
  * waves split the code steps and the cross-wave sum runs in wave order.  Thread (rr, c) holds x1 / x2 of logical
  * columns n / n + hd/2 and applies, in this order: the FP8 column scales (MXFP4: none; the block scales are applied in
  * the decode); the consumer's rstd = rsqrt(sum(rstats[rr][0 .. rgroups)) / K + eps), where rstats is given; the bias,

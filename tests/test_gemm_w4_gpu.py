@@ -116,6 +116,29 @@ def test_swiglu_general_form(dev):
     torch.testing.assert_close(y.cpu().double(), ref, rtol=1e-4, atol=1e-4)
 
 
+def test_swiglu_general_form_16_waves(dev):
+    """17 code steps (K % 128 == 96): the SwiGLU pair on the general form's 16 waves."""
+    M, N, K = 5, 40, 2144
+    x, ref = _swiglu_ref(N, K, M)
+    lin = _lin(dev, _weight(N, K, 1)[0], _weight(N, K, 2)[0])
+    before = _counts()
+    y = lin(x.to(dev))
+    _rose(before, w4=1)
+    torch.testing.assert_close(y.cpu().double(), ref, rtol=1e-4, atol=1e-4)
+
+
+def test_swiglu_k3584_other_wave_shape():
+    """FO_W4_XS=7 runs the X-stationary form on 7 waves x 4 code steps instead of 14 x 2 (the library reads the
+    variable once per process, so this is a child process): one case of test_swiglu_k3584 under it."""
+    import os
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider",
+                        f"{os.path.abspath(__file__)}::test_swiglu_k3584[16-176]"], env=dict(os.environ, FO_W4_XS="7"),
+                       cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), capture_output=True, text=True)
+    assert r.returncode == 0 and "1 passed" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
 @pytest.mark.parametrize("chain", ["w4_w4swiglu", "w4_bf16", "bf16_w4"])
 @pytest.mark.parametrize("M", [8, 16])
 def test_rmsnorm_across_gemms(dev, M, chain):

@@ -88,6 +88,31 @@ def test_swiglu_general_form(dev):
     torch.testing.assert_close(y.cpu().double(), ref, rtol=1e-4, atol=1e-4)
 
 
+def test_swiglu_general_form_16_waves(dev):
+    """34 code steps (K % 64 == 32): the SwiGLU pair on the general form's 16 waves."""
+    from fo.ops import PackedLinearW8
+    M, N, K = 5, 40, 2144
+    (wg, gdq), (wu, udq) = _weight(N, K, 5), _weight(N, K, 6)
+    x = torch.randn(M, K, generator=torch.Generator().manual_seed(9))
+    before = _counts()
+    y = PackedLinearW8(wg.to(dev), swiglu_up=wu.to(dev))(x.to(dev))
+    assert _counts() == (before[0] + 1, before[1])
+    ref = torch.nn.functional.silu(x.double() @ gdq.t()) * (x.double() @ udq.t())
+    torch.testing.assert_close(y.cpu().double(), ref, rtol=1e-4, atol=1e-4)
+
+
+def test_swiglu_k3584_other_wave_shape():
+    """FO_W8_XS=8 runs the X-stationary form on 8 waves x 7 code steps instead of 14 x 4 (the library reads the
+    variable once per process, so this is a child process): one case of test_swiglu_k3584 under it."""
+    import os
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider",
+                        f"{os.path.abspath(__file__)}::test_swiglu_k3584[16-176]"], env=dict(os.environ, FO_W8_XS="8"),
+                       cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), capture_output=True, text=True)
+    assert r.returncode == 0 and "1 passed" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
 @pytest.mark.parametrize("chain", ["w8_w8swiglu", "w8_bf16", "bf16_w8"])
 @pytest.mark.parametrize("M", [8, 16])
 def test_rmsnorm_across_gemms(dev, M, chain):
