@@ -337,10 +337,8 @@ class FreezeOmniEngine:
         if g is None or g.max_keys < need:
             if g is not None:
                 g.destroy()
-            if chunks == 1:
-                g = ListenGraph(self, ident, B, R, max(need + 1024, 2048), slots=slots)
-            else:
-                g = ListenGroupGraph(self, ident, B, R, max(need + 1024, 2048), chunks)
+            # (a graph of chunks > 1 always has two slots: its key carries none)
+            g = ListenGraph(self, ident, B, R, max(need + 1024, 2048), chunks, slots if chunks == 1 else 2)
             self._lgraphs[key] = g
         return g
 
@@ -349,7 +347,7 @@ class FreezeOmniEngine:
 
     def listen_pipe(self, chunks=1):
         """A ListenPipe over this engine (encoder stage of chunk c+1 overlapped with the LLM of chunk c); chunks > 1:
-        that many consecutive chunks per Qwen2 stage (ListenGroupGraph)."""
+        that many consecutive chunks per Qwen2 stage (ListenGraph(chunks=...))."""
         return ListenPipe(self, chunks)
 
     MAX_ENC_GRAPHS = 32
@@ -526,18 +524,29 @@ class FreezeOmniEngine:
         return g
 
 
-def _rows_of_one_tensor(items, n):
-    """The items' feature tensors are consecutive [R, 80] rows of ONE storage (a batched fbank's output), so one
+def _rows_of_one_tensor(feats, n):
+    """The feature tensors are consecutive [R, 80] rows of ONE storage (a batched fbank's output), so one
     strided copy takes them all.  Separate tensors that merely sit next to each other in the caching allocator's
     memory (each session's features uploaded on its own) do not qualify: a view over the first one's storage would
     run past its end."""
-    f0 = items[0]["feats"]
+    f0 = feats[0]
     st = f0.untyped_storage()
     base, size = st.data_ptr(), st.nbytes()
-    return (f0.data_ptr() - base + len(items) * n * 4 <= size and
-            all(it["feats"].is_contiguous() and it["feats"].numel() == n and
-                it["feats"].untyped_storage().data_ptr() == base and
-                it["feats"].data_ptr() == f0.data_ptr() + b * n * 4 for b, it in enumerate(items)))
+    return (f0.data_ptr() - base + len(feats) * n * 4 <= size and
+            all(f.is_contiguous() and f.numel() == n and f.untyped_storage().data_ptr() == base and
+                f.data_ptr() == f0.data_ptr() + b * n * 4 for b, f in enumerate(feats)))
+
+
+def _copy_feats(dst, feats):
+    """The sessions' [R, 80] features into a captured stage's static buffer dst [B, R, 80], on the current stream:
+    one copy when they are one batched tensor's rows (a batched fbank, the duplex tick's deliver_deferred puts one
+    identity's rows next to each other), else session by session."""
+    B, R, F = dst.shape
+    if _rows_of_one_tensor(feats, R * F):
+        dst.copy_(feats[0].as_strided((B, R, F), (R * F, F, 1)))
+    else:
+        for b, f in enumerate(feats):
+            dst[b].copy_(f)
 
 
 class _HostRing:
@@ -608,13 +617,7 @@ class EncoderGraph:
         h[4 * B:5 * B] = [it["ada_cache"].slot for it in items]
         st = self.stream
         with torch.cuda.stream(st):
-            # the duplex tick's batched fbank puts one identity's rows next to each other (deliver_deferred): one copy
-            f0, n = items[0]["feats"], self.R * 80
-            if _rows_of_one_tensor(items, n):
-                self.feats.copy_(f0.as_strided((B, self.R, 80), (n, 80, 1)))
-            else:
-                for b, it in enumerate(items):
-                    self.feats[b].copy_(it["feats"].reshape(self.R, 80))
+            _copy_feats(self.feats, [it["feats"].reshape(self.R, 80) for it in items])
         self.ring.upload(j, self.meta_d, st)
         _lib.call("fo_graph_launch", self.exec, st.cuda_stream)
         self.enc.advance(caches, self.T)
@@ -628,61 +631,78 @@ class EncoderGraph:
 
 
 class ListenGraph:
-    """Steady-state listen step for B sessions of one identity (status ipu_cl / ipu_el: no chat
-    prefix) as two captured hipGraphs (models/audioLLM.py:350-429):
+    """Steady-state listen for B sessions of one identity (status ipu_cl / ipu_el: no chat prefix), C = `chunks`
+    consecutive chunks per Qwen2 stage, as captured hipGraphs (models/audioLLM.py:350-429):
       encoder stage: features -> encoder -> adapter -> fp16-rounded LLM input rows (x slot)
       LLM stage:     x slot -> Qwen2 chunk prefill on paged KV -> final norm -> dialog-state head
     Per-call inputs go through static buffers: the features (device copy) and one metadata block per
     stage (encoder ring positions / adapter cache slots; LLM positions, cache slots, visible keys,
-    block tables), each uploaded with a single async copy from pinned memory.
+    block tables: kv.GroupMeta), each uploaded with a single async copy from pinned memory.
 
-    run(items): both stages back to back on the engine stream.
-    pipelined: with slots=2, the encoder stage of chunk c+1 runs on a side stream while the LLM stage
-    of chunk c runs on the engine stream (ListenPipe); the two stages share nothing but the x slot,
+    chunks = 1, slots = 1: run(items), both stages back to back on the engine stream (engine.listen()).
+    pipelined: with slots=2, the encoder stage of chunk (group) c+1 runs on a side stream while the LLM stage
+    of chunk (group) c runs on the engine stream (ListenPipe); the two stages share nothing but the x slot,
     ordered by events.  The state decision of chunk c does not depend on chunk c+1, so the results are
-    those of the sequential order."""
+    those of the sequential order.
 
-    def __init__(self, eng, ident, B, R, max_keys, slots=1):
+    chunks > 1 (what older notes and bench.py's help call ListenGroupGraph): C consecutive chunks in ONE Qwen2
+    stage (the listen of an offline input: the reference feeds a wav's chunks back to back,
+    bin/inference.py:119-150).  The group's encoder stage is one captured replay over its chunks (the encoder is
+    chunk-recurrent: _enc_body), writing their rows into the group's x slot chunk-major ([chunk][session][token]);
+    the LLM stage then prefills all C x B x To rows at once -- each session's C chunks are its next C*To positions,
+    causal, so chunk j's rows see chunks < j of the same stage as the sequential order does -- and the dialog-state
+    head reads every chunk's last row (one decision per chunk, models/audioLLM.py:420-429).  Work items are (chunk,
+    session): To tokens each (the tables: kv.GroupMeta).  The Qwen2 weights stream once per C chunks instead of
+    once per chunk; the GEMMs run at m x B x To rows -- at 8 sessions of 2 tokens,
+    m x 16: the split-K 17..64-row paths (k_gemm_xsk) up to m = 4, the 65..128-row family (k_gemm_rows) from m = 5
+    to the benchmark's C = 8 -- whose row-count dependent tilings give the sequential results to fp32 rounding, not
+    bit for bit.  A group of m < C chunks (the end of the input) replays stages captured for m, on the group's
+    buffers and with the group's item-table attention form; only a C = 1 graph runs the dense form (uniform).
+
+    Every stage is captured on first use, per (slot, chunks in the group)."""
+
+    def __init__(self, eng, ident, B, R, max_keys, chunks=1, slots=1):
         dev = eng.device
         self.eng, self.ident, self.B, self.R, self.max_keys = eng, ident, B, R, max_keys
+        self.C, self.slots = chunks, slots
+        C = chunks
         enc, ada, llm = eng.enc[ident], eng.ada[ident], eng.llm
         self.enc, self.ada, self.llm = enc, ada, llm
-        self.feats = torch.empty(B, R, 80, dtype=F32, device=dev)
-        self.eb = enc.buffers(B, R)
+        # the group's features, chunk-major ([chunk][session] windows): each submit_encoder copies its chunk's rows in
+        self.feats = torch.empty(C * B, R, 80, dtype=F32, device=dev)
+        self.eb = enc.buffers(C * B, R)
         self.T = enc.dims(R)[2]
         self.ab = ada.buffers(B, self.T)
         self.To = To = ada.out_len(self.T)
-        n = B * To
         G = llm.H // llm.KVH
-        assert To * G <= 16, "listen graph: one attention work item per session"
-        PS = llm.pool.PS
-        self.maxb = (max_keys + PS - 1) // PS
-        # encoder metadata [enc 4B | ada slots B]; LLM metadata [tok_pos n | tok_slot n | tok_nvis n | block table]
-        self.emeta_d = torch.zeros(5 * B, dtype=I32, device=dev)
-        self.lmeta_d = torch.zeros(3 * n + B * self.maxb, dtype=I32, device=dev)
-        self.ering, self.lring = _HostRing(5 * B), _HostRing(3 * n + B * self.maxb)
-        self.eb["meta"] = self.emeta_d[0:4 * B]
-        self.ab["slots"] = self.emeta_d[4 * B:5 * B]
-        m = self.lmeta_d
-        items = torch.tensor([[b, b * To, To] for b in range(B)], dtype=I32).reshape(-1).to(dev)
-        self.rows = torch.tensor([b * To + To - 1 for b in range(B)], dtype=I32).to(dev)
-        self.meta = SimpleNamespace(T=n, S=B, tok_pos=m[0:n], tok_slot=m[n:2 * n], tok_nvis=m[2 * n:3 * n],
-                                    block_table=m[3 * n:].view(B, self.maxb), items=items, n_items=B,
-                                    max_rows=To * G, max_keys=max_keys, uniform=True)
-        self.slots = slots
+        assert To * G <= 16, "listen graph: one attention work item per (session, chunk)"
+        self.n1 = n1 = B * To
+        self.n = n = C * n1
+        # the Qwen2 stage's chunk-major tables (kv.GroupMeta): items, decision rows, per-m views, host fill
+        self.gm = gm = GroupMeta(B, To, C, G, max_keys, llm.pool.PS, dev, uniform=(C == 1))
+        self.maxb = gm.maxb
+        # encoder metadata [chunk j: enc 4B] x C | ada slots B -- filled chunk by chunk on the host, uploaded once;
+        # LLM metadata: gm.buf [tok_pos n | tok_slot n | tok_nvis n | block table]
+        self.emeta_d = torch.zeros(4 * B * C + B, dtype=I32, device=dev)
+        self.hmeta = np.zeros(4 * B * C + B, np.int32)
+        self.lmeta_d = gm.buf
+        self.ering, self.lring = _HostRing(4 * B * C + B), _HostRing(gm.size)
+        self.eb["meta"] = self.emeta_d[0:4 * B * C]
+        self.ab["slots"] = self.emeta_d[4 * B * C:]
+        self.rows, self.metas = gm.rows, gm.metas
         self.xs = [torch.empty(n, llm.D, dtype=F32, device=dev) for _ in range(slots)]
-        self.x = self.xs[0]
-        self.ws = llm.stack.workspace(n, ops.attn_nsplit(max_keys, B, llm.KVH), dev)
+        self.ws = llm.stack.workspace(n, ops.attn_nsplit(max_keys, C * B, llm.KVH), dev)
         self.predict = ident == "user" and bool(eng.predict_usr_state) and llm.head_w is not None
-        self.probs = torch.empty(B, 3, dtype=F32, device=dev)
-        self.probs_host = [torch.empty(B, 3, dtype=F32).pin_memory() for _ in range(slots)]
+        self.probs = torch.empty(C * B, 3, dtype=F32, device=dev)
+        self.probs_host = [torch.empty(C * B, 3, dtype=F32).pin_memory() for _ in range(slots)]
         self.inflight = [None] * slots
         self.main = ops.engine_stream(dev)
         self.side = ops.engine_stream(dev, side=True) if slots > 1 else self.main
         # the encoder stage is captured on the stream it replays on, so its split-K scratch (ops.Runtime)
         # is not the LLM stage's while the two overlap
-        self.enc_exec = [self._capture(self.side, lambda k=k: self._enc_body(k), ENC_GEMM_TUNE) for k in range(slots)]
-        self.llm_exec = [self._capture(self.main, lambda k=k: self._llm_body(k)) for k in range(slots)]
+        self.enc_exec = [{} for _ in range(slots)]   # slot -> {chunks in the group: captured encoder stage}
+        self.llm_exec = [{} for _ in range(slots)]   # slot -> {chunks in the group: captured LLM stage}
+        self.enc_todo = [0] * slots   # chunks whose features are in the slot but whose encoder stage is not queued
         self.ev_enc = [self._event() for _ in range(slots)]
         self.ev_llm = [self._event() for _ in range(slots)]
         self.llm_used = [False] * slots
@@ -711,165 +731,6 @@ class ListenGraph:
                 _lib.call("fo_gemm_tune", 0, 0)
         return ex
 
-    def _enc_body(self, k):
-        B, R = self.B, self.R
-        xe, T = self.enc.run(self.feats, B, R, self.eb)
-        emb, To = self.ada.run(xe, B, T, self.ab)
-        ops.gather_rows(emb, None, out=self.xs[k], round_fp16=True)   # inputs_embeds.half()
-
-    def _llm_body(self, k):
-        llm, x = self.llm, self.xs[k]
-        llm.stack.forward(x, self.meta, self.ws)
-        ops.rmsnorm(x, llm.norm, llm.eps, out=x)
-        if self.predict:
-            ops.state_head(x, self.rows, llm.head_w, llm.head_b, self.probs)
-
-    # ---------------------------------------------------------------- stages
-    def submit_encoder(self, items, k=0):
-        """Encoder stage of one chunk into x slot k (side stream when pipelined).  Advances the
-        encoder caches; returns the per-session pe_index after this chunk."""
-        B = self.B
-        caches = [it["enc_cache"] for it in items]
-        emeta, new_pe = self.enc.host_meta(caches, [it["pe_index"] or 0 for it in items])
-        j, h = self.ering.next()
-        h[0:4 * B] = emeta
-        h[4 * B:5 * B] = [it["ada_cache"].slot for it in items]
-        st = self.side
-        if self.slots > 1 and self.llm_used[k]:
-            _lib.call("fo_stream_wait_event", st.cuda_stream, self.ev_llm[k])  # slot k's last reader is done
-        with torch.cuda.stream(st):
-            f0 = items[0]["feats"]
-            if _rows_of_one_tensor(items, self.R * 80):
-                self.feats.copy_(f0.as_strided((B, self.R, 80), (self.R * 80, 80, 1)))  # one batched tensor
-            else:
-                for b, it in enumerate(items):
-                    self.feats[b].copy_(it["feats"])
-        self.ering.upload(j, self.emeta_d, st)
-        _lib.call("fo_graph_launch", self.enc_exec[k], st.cuda_stream)
-        _lib.call("fo_event_record", self.ev_enc[k], st.cuda_stream)
-        self.enc.advance(caches, self.T)
-        return new_pe
-
-    def submit_llm(self, items, new_pe, k=0, wait=True):
-        """LLM stage of the chunk whose encoder stage filled x slot k (engine stream); appends To KV
-        rows per session.  wait=True returns the per-session results (reads the state head back);
-        wait=False only queues the stage and its state-head copy: collect_llm(k) reads them later."""
-        B, To, maxb = self.B, self.To, self.maxb
-        n = B * To
-        j, h = self.lring.next()
-        bt = h[3 * n:].reshape(B, maxb)
-        for b, it in enumerate(items):
-            kv = it["kv"]
-            old = kv.length
-            kv.reserve(old + To)
-            if len(kv.pages) > maxb:
-                raise RuntimeError("listen graph block table too small")
-            for i in range(To):
-                r = b * To + i
-                h[r] = old + i
-                h[n + r] = kv.slot(old + i)
-                h[2 * n + r] = old + i + 1
-            bt[b, :len(kv.pages)] = kv.pages
-            kv.length = old + To
-        st = self.main
-        self.lring.upload(j, self.lmeta_d, st)
-        if self.side is not self.main:
-            _lib.call("fo_stream_wait_event", st.cuda_stream, self.ev_enc[k])
-        _lib.call("fo_graph_launch", self.llm_exec[k], st.cuda_stream)
-        if self.predict:
-            with torch.cuda.stream(st):
-                self.probs_host[k].copy_(self.probs, non_blocking=True)
-        _lib.call("fo_event_record", self.ev_llm[k], st.cuda_stream)
-        self.llm_used[k] = True
-        self.inflight[k] = (items, new_pe)
-        return self.collect_llm(k) if wait else None
-
-    def collect_llm(self, k):
-        """Results of the LLM stage queued in slot k (waits for it)."""
-        items, new_pe = self.inflight[k]
-        self.inflight[k] = None
-        To = self.To
-        _lib.call("fo_event_sync", self.ev_llm[k])
-        probs = self.probs_host[k].numpy() if self.predict else None
-        res = []
-        for b, it in enumerate(items):
-            r = {"enc_cache": it["enc_cache"], "ada_cache": it["ada_cache"], "pe_index": new_pe[b],
-                 "hidden_row": (self.xs[k], b * To + To - 1), "probs": None}
-            if probs is not None:
-                r["probs"] = {"state_1": float(probs[b, 1]), "state_2": float(probs[b, 2])}
-            res.append(r)
-        return res
-
-    def run(self, items):
-        return self.submit_llm(items, self.submit_encoder(items, 0), 0)
-
-    def destroy(self):
-        if self.exec is not None:
-            for ex in self.enc_exec + self.llm_exec:
-                _lib.call("fo_graph_destroy", ex)
-            for e in self.ev_enc + self.ev_llm:
-                _lib.call("fo_event_destroy", e)
-            self.ering.destroy()
-            self.lring.destroy()
-            self.exec = None
-
-
-class ListenGroupGraph:
-    """C consecutive steady-state chunks of B sessions in ONE Qwen2 stage (the listen of an offline input: the
-    reference feeds a wav's chunks back to back, bin/inference.py:119-150).  Each chunk's encoder stage is its own
-    captured replay (the encoder is chunk-recurrent), writing its rows into the group's x slot chunk-major
-    ([chunk][session][token]); the LLM stage then prefills all C x B x To rows at once -- each session's C chunks are
-    its next C*To positions, causal, so chunk j's rows see chunks < j of the same stage as the sequential order does
-    -- and the dialog-state head reads every chunk's last row (one decision per chunk, models/audioLLM.py:420-429).
-    Work items are (chunk, session): To tokens each, as in ListenGraph (the tables: kv.GroupMeta).  The Qwen2 weights
-    stream once per C chunks instead of once per chunk; the GEMMs run at m x B x To rows -- at 8 sessions of 2 tokens,
-    m x 16: the split-K 17..64-row paths (k_gemm_xsk) up to m = 4, the 65..128-row family (k_gemm_rows) from m = 5
-    to the benchmark's C = 8 -- whose row-count dependent tilings give the sequential results to fp32 rounding, not
-    bit for bit.  A group of m < C chunks (the end of the input) replays an LLM stage captured for m.  Two slots: the
-    encoder stages of group g+1 run on the side stream while group g's LLM stage runs (ListenPipe)."""
-
-    def __init__(self, eng, ident, B, R, max_keys, C):
-        dev = eng.device
-        self.eng, self.ident, self.B, self.R, self.max_keys, self.C = eng, ident, B, R, max_keys, C
-        enc, ada, llm = eng.enc[ident], eng.ada[ident], eng.llm
-        self.enc, self.ada, self.llm = enc, ada, llm
-        # the group's features, chunk-major ([chunk][session] windows): each push copies its chunk's rows in
-        self.feats = torch.empty(C * B, R, 80, dtype=F32, device=dev)
-        self.eb = enc.buffers(C * B, R)
-        self.T = enc.dims(R)[2]
-        self.ab = ada.buffers(B, self.T)
-        self.To = To = ada.out_len(self.T)
-        G = llm.H // llm.KVH
-        assert To * G <= 16, "listen group graph: one attention work item per (session, chunk)"
-        self.n1 = n1 = B * To
-        self.n = n = C * n1
-        # the Qwen2 stage's chunk-major tables (kv.GroupMeta): items, decision rows, per-m views, host fill
-        self.gm = gm = GroupMeta(B, To, C, G, max_keys, llm.pool.PS, dev)
-        self.maxb = gm.maxb
-        # encoder metadata [chunk j: enc 4B] x C | ada slots B -- filled chunk by chunk on the host, uploaded once
-        self.emeta_d = torch.zeros(4 * B * C + B, dtype=I32, device=dev)
-        self.hmeta = np.zeros(4 * B * C + B, np.int32)
-        self.lmeta_d = gm.buf
-        self.ering, self.lring = _HostRing(4 * B * C + B), _HostRing(gm.size)
-        self.eb["meta"] = self.emeta_d[0:4 * B * C]
-        self.ab["slots"] = self.emeta_d[4 * B * C:]
-        self.items, self.rows, self.metas = gm.items, gm.rows, gm.metas
-        self.xs = [torch.empty(n, llm.D, dtype=F32, device=dev) for _ in range(2)]
-        self.ws = llm.stack.workspace(n, ops.attn_nsplit(max_keys, C * B, llm.KVH), dev)
-        self.predict = ident == "user" and bool(eng.predict_usr_state) and llm.head_w is not None
-        self.probs = torch.empty(C * B, 3, dtype=F32, device=dev)
-        self.probs_host = [torch.empty(C * B, 3, dtype=F32).pin_memory() for _ in range(2)]
-        self.inflight = [None, None]
-        self.main = ops.engine_stream(dev)
-        self.side = ops.engine_stream(dev, side=True)
-        self.enc_exec = [{}, {}]   # slot -> {chunks in the group: captured encoder stage}
-        self.llm_exec = [{}, {}]   # slot -> {chunks in the group: captured LLM stage}
-        self.enc_todo = [0, 0]     # chunks whose features are in the slot but whose encoder stage is not queued
-        self.ev_enc = [ListenGraph._event() for _ in range(2)]
-        self.ev_llm = [ListenGraph._event() for _ in range(2)]
-        self.llm_used = [False, False]
-        self.exec = True
-
     def _enc_body(self, k, m):
         """The encoder stage of m chunks: one encoder pass over all their rows (SpeechEncoderEngine.run(chunks=m)),
         then the adapter chunk by chunk (its causal conv cache carries from one to the next), each chunk's rows
@@ -887,10 +748,12 @@ class ListenGroupGraph:
         if self.predict:
             ops.state_head(x, self.rows[:m * self.B], llm.head_w, llm.head_b, self.probs)
 
-    def submit_encoder(self, items, k, j):
+    # ---------------------------------------------------------------- stages
+    def submit_encoder(self, items, k=0, j=0):
         """Chunk j of the group in slot k: its ring / position metadata (the encoder caches advanced as the
         sequential order does) and its features into the slot's group buffers; the group's encoder stage (side
-        stream) is queued with its last chunk (launch_encoder).  Returns the per-session pe_index after this chunk."""
+        stream when pipelined) is queued with its last chunk (launch_encoder).  Returns the per-session pe_index
+        after this chunk."""
         B = self.B
         caches = [it["enc_cache"] for it in items]
         emeta, new_pe = self.enc.host_meta(caches, [it["pe_index"] or 0 for it in items])
@@ -898,15 +761,10 @@ class ListenGroupGraph:
         if j == 0:
             self.hmeta[4 * B * self.C:] = [it["ada_cache"].slot for it in items]
         st = self.side
-        if j == 0 and self.llm_used[k]:
+        if j == 0 and self.slots > 1 and self.llm_used[k]:
             _lib.call("fo_stream_wait_event", st.cuda_stream, self.ev_llm[k])   # slot k's last reader is done
         with torch.cuda.stream(st):
-            dst = self.feats[j * B:(j + 1) * B]
-            if _rows_of_one_tensor(items, self.R * 80):
-                dst.copy_(items[0]["feats"].as_strided((B, self.R, 80), (self.R * 80, 80, 1)))
-            else:
-                for b, it in enumerate(items):
-                    dst[b].copy_(it["feats"])
+            _copy_feats(self.feats[j * B:(j + 1) * B], [it["feats"] for it in items])
         self.enc.advance(caches, self.T)
         self.enc_todo[k] = j + 1
         if j + 1 == self.C:
@@ -920,7 +778,7 @@ class ListenGroupGraph:
             return
         ex = self.enc_exec[k].get(m)
         if ex is None:
-            ex = self.enc_exec[k][m] = ListenGraph._capture(self.side, lambda: self._enc_body(k, m), ENC_GEMM_TUNE)
+            ex = self.enc_exec[k][m] = self._capture(self.side, lambda: self._enc_body(k, m), ENC_GEMM_TUNE)
         q, h = self.ering.next()
         h[:] = self.hmeta
         st = self.side
@@ -929,21 +787,23 @@ class ListenGroupGraph:
         _lib.call("fo_event_record", self.ev_enc[k], st.cuda_stream)
         self.enc_todo[k] = 0
 
-    def submit_llm(self, groups, pes, k):
-        """The LLM stage of the m = len(groups) chunks whose encoder stages filled slot k (engine stream); appends
-        m * To KV rows per session.  collect_llm(k) reads its results."""
+    def submit_llm(self, groups, pes, k=0):
+        """The LLM stage of the m = len(groups) chunks whose encoder stage filled slot k (engine stream): groups /
+        pes are each chunk's items / pe_index list as submit_encoder took / returned them.  Appends m * To KV rows per
+        session; only queues the stage and its state-head copy: collect_llm(k) reads the results."""
         B = self.B
         m = len(groups)
         if self.enc_todo[k]:   # a partial group (the end of the input): its encoder stage is queued now
             self.launch_encoder(k)
         ex = self.llm_exec[k].get(m)
         if ex is None:
-            ex = self.llm_exec[k][m] = ListenGraph._capture(self.main, lambda: self._llm_body(k, m))
+            ex = self.llm_exec[k][m] = self._capture(self.main, lambda: self._llm_body(k, m))
         q, h = self.lring.next()
         self.gm.fill(h, [it["kv"] for it in groups[0]], m)
         st = self.main
         self.lring.upload(q, self.lmeta_d, st)
-        _lib.call("fo_stream_wait_event", st.cuda_stream, self.ev_enc[k])
+        if self.side is not self.main:
+            _lib.call("fo_stream_wait_event", st.cuda_stream, self.ev_enc[k])
         _lib.call("fo_graph_launch", ex, st.cuda_stream)
         if self.predict:
             with torch.cuda.stream(st):
@@ -970,6 +830,11 @@ class ListenGroupGraph:
                 res.append(r)
             out.append(res)
         return out
+
+    def run(self, items):
+        """chunks = 1: both stages of one chunk back to back; its result list."""
+        self.submit_llm([items], [self.submit_encoder(items)])
+        return self.collect_llm(0)[0]
 
     def destroy(self):
         if self.exec is not None:
@@ -1116,71 +981,32 @@ class ListenPipe:
     (encoder / adapter caches are advanced in place at submission, like listen().)
 
     Every push must be graphable (same identity and batch, no chat prefix, open caches); the results
-    are identical to calling listen() chunk by chunk."""
+    are identical to calling listen() chunk by chunk.
+
+    chunks = C > 1: the same with groups of C consecutive chunks in the place of chunks (ListenGraph(chunks=C)): a
+    push queues its chunk's features, every C-th push the group's two stages.  push then returns (pe after this
+    chunk, None or the per-chunk result lists of the previous group, in chunk order) and flush the per-chunk result
+    lists of what is left (a partial last group of m < C chunks included); decide() is asked chunk by chunk, and
+    a refusal rolls back every later chunk already in a stage (the rest of its group and the speculative next group).
+    With chunks = 1 a group is one chunk, and push / flush hand out its one result list itself (_per_chunk)."""
 
     def __init__(self, eng, chunks=1):
         self.eng, self.g, self.pending, self.k = eng, None, None, 0
         self.stopped = False
         self.C = int(chunks)
-        self.acc = []   # chunks > 1: (items, pe) of the group being assembled in slot k
+        self.acc = []   # (items, pe) of the group being assembled in slot k
+
+    def _per_chunk(self, out):
+        return out[0] if self.C == 1 and out else out
 
     def push(self, items, decide=None):
         eng = self.eng
         if self.stopped:
             raise RuntimeError("ListenPipe: decide() stopped this pipe (flush and start a new one)")
-        if self.C > 1:
-            return self._push_group(items, decide)
         with torch.cuda.stream(ops.engine_stream(eng.device)):
             if not eng._graphable(items):
                 raise ValueError("ListenPipe.push: items must be steady-state chunks (no chat prefix, open caches)")
-            g = eng._listen_graph_for(items, slots=2, extra=64 * 2)
-            if self.g is not None and g is not self.g:
-                raise RuntimeError("ListenPipe: the batch changed (flush before changing sessions)")
-            self.g = g
-            k = self.k
-            pe = g.submit_encoder(items, k)
-            # chunk c's LLM stage is queued speculatively right behind chunk c-1's on the engine stream, so the
-            # stream never idles while the host reads c-1's state head back; if the decision on c-1 stops the
-            # listen (dialog_ss), chunk c is rolled back below and never reaches the context
-            g.submit_llm(items, pe, k, wait=False)
-            out = None
-            if self.pending is not None:
-                out = g.collect_llm(self.pending)
-            self.pending = k
-            self.k = 1 - k
-            if decide is not None and out is not None and not decide(out):
-                self._roll_back(k)
-                self.stopped = True
-            return pe, out
-
-    def _roll_back(self, k):
-        """Undo the speculative LLM stage in slot k: wait for it, drop the KV rows it appended."""
-        g = self.g
-        items, _ = g.inflight[k]
-        _lib.call("fo_event_sync", g.ev_llm[k])
-        g.inflight[k] = None
-        for it in items:
-            it["kv"].truncate(it["kv"].length - g.To)
-        self.pending = None
-
-    def flush(self):
-        if self.C > 1:
-            return self._flush_group()
-        if self.pending is None:
-            return None
-        with torch.cuda.stream(ops.engine_stream(self.eng.device)):
-            k, self.pending = self.pending, None
-            return self.g.collect_llm(k)
-
-    # ---- chunks > 1 (ListenGroupGraph): push returns (pe after this chunk, None or the per-chunk result lists of the
-    # previous group, in chunk order); decide() is asked chunk by chunk, and a refusal rolls back every later chunk
-    # already in a stage (the rest of its group and the speculative next group)
-    def _push_group(self, items, decide):
-        eng = self.eng
-        with torch.cuda.stream(ops.engine_stream(eng.device)):
-            if not eng._graphable(items):
-                raise ValueError("ListenPipe.push: items must be steady-state chunks (no chat prefix, open caches)")
-            g = eng._listen_graph_for(items, extra=64 * 2 * self.C, chunks=self.C)
+            g = eng._listen_graph_for(items, slots=2, extra=64 * 2 * self.C, chunks=self.C)
             if self.g is not None and g is not self.g:
                 raise RuntimeError("ListenPipe: the batch changed (flush before changing sessions)")
             self.g = g
@@ -1190,6 +1016,9 @@ class ListenPipe:
             self.kvs = [it["kv"] for it in items]
             out = None
             if len(self.acc) == self.C:
+                # group c's LLM stage is queued speculatively right behind group c-1's on the engine stream, so the
+                # stream never idles while the host reads c-1's state head back; if a decision on c-1 stops the
+                # listen (dialog_ss), group c is rolled back below and never reaches the context
                 g.submit_llm([a for a, _ in self.acc], [p for _, p in self.acc], k)
                 self.acc = []
                 if self.pending is not None:
@@ -1197,10 +1026,10 @@ class ListenPipe:
                 self.pending = k
                 self.k = 1 - k
                 if decide is not None and out is not None:
-                    self._decide_group(out, decide, newer=[k])
-            return pe, out
+                    self._decide(out, decide, newer=[k])
+            return pe, self._per_chunk(out)
 
-    def _decide_group(self, out, decide, newer):
+    def _decide(self, out, decide, newer):
         """Ask decide() chunk by chunk; on a refusal drop the chunks after it from `out` and from every session's KV,
         together with every stage in `newer` (waited for first): the context holds exactly the chunks up to the
         refused one, as in the sequential order."""
@@ -1222,7 +1051,7 @@ class ListenPipe:
             self.stopped = True
             return
 
-    def _flush_group(self):
+    def flush(self):
         g = self.g
         if g is None:
             return None
@@ -1237,4 +1066,5 @@ class ListenPipe:
                 self.acc = []
                 out += g.collect_llm(k)
                 self.k = 1 - k
-            return out or None
+            return self._per_chunk(out or None)
+

@@ -260,7 +260,7 @@ class BatchMeta:
 
 
 class GroupMeta:
-    """Metadata of the Qwen2 stage of a listen group (engine.ListenGroupGraph): m <= C consecutive chunks of B
+    """Metadata of the Qwen2 stage of a listen group (engine.ListenGraph, every C): m <= C consecutive chunks of B
     sessions, To tokens a chunk, in one forward whose rows are chunk-major ([chunk][session][token]).  Session b's
     chunk j holds its positions old + j*To .. old + (j+1)*To - 1, causal, so it sees the keys that chunks < j of the
     same forward append.  Work items are (chunk, session) in that order, To tokens each; `rows` are the decision rows
@@ -268,9 +268,13 @@ class GroupMeta:
 
     buf: the static device block [tok_pos n | tok_slot n | tok_nvis n | block table B x maxb], n = C*B*To, that the
     captured stages read; metas[m]: the views of a group of m chunks (what DecoderStack.forward takes);
-    fill(h, seqs, m) writes one group's values into a host block of `size` int32 (uploaded to buf by the caller)."""
+    fill(h, seqs, m) writes one group's values into a host block of `size` int32 (uploaded to buf by the caller).
+    uniform: what every metas[m] says of itself -- True lets the attention take no item table (item b = sequence b,
+    BatchMeta.uniform), which holds for C = 1 only; the one-chunk-per-stage listen graph asks for it, a group graph
+    (its trailing one-chunk group included) and the tests that pin the item-table form do not."""
 
-    def __init__(self, B, To, C, gqa, max_keys, page_size, device):
+    def __init__(self, B, To, C, gqa, max_keys, page_size, device, uniform=False):
+        assert not uniform or C == 1, "GroupMeta: only a one-chunk stage has item b = sequence b"
         self.B, self.To, self.C = B, To, C
         self.n1 = n1 = B * To
         self.n = n = C * n1
@@ -285,7 +289,7 @@ class GroupMeta:
         self.metas = {m: SimpleNamespace(T=m * n1, S=B, tok_pos=lm[0:m * n1], tok_slot=lm[n:n + m * n1],
                                          tok_nvis=lm[2 * n:2 * n + m * n1], block_table=bt,
                                          items=self.items[:3 * m * B], n_items=m * B, max_rows=To * gqa,
-                                         max_keys=max_keys, uniform=False)
+                                         max_keys=max_keys, uniform=uniform)
                       for m in range(1, C + 1)}
 
     def fill(self, h, seqs, m):
@@ -297,7 +301,7 @@ class GroupMeta:
             old = kv.length
             kv.reserve(old + m * To)
             if len(kv.pages) > maxb:
-                raise RuntimeError("listen group graph block table too small")
+                raise RuntimeError("listen graph block table too small")
             for j in range(m):
                 for i in range(To):
                     r = j * n1 + b * To + i

@@ -285,7 +285,7 @@ class SpeechEncoderEngine:
     def run(self, feats, B, R, bufs, chunks=1):
         """The device part of infer(): bufs from buffers(B, R) with bufs['meta'] already uploaded.
         chunks > 1: `chunks` consecutive chunks of the same B sessions in one pass (an offline input's listen,
-        fo.engine.ListenGroupGraph): feats [chunks * B, R, 80] chunk-major, bufs from buffers(chunks * B, R), meta
+        fo.engine.ListenGraph(chunks=C)): feats [chunks * B, R, 80] chunk-major, bufs from buffers(chunks * B, R), meta
         [chunks][4 B] (each chunk's ring / position metadata, host_meta after the chunks before it).  Every row-wise
         step (the Conv2dSubsampling4 front end -- each chunk's window carries its own context frames --, the embed,
         the norms, q|k|v, linear_out, the FFN) runs once over all the rows; the rel-pos attention runs chunk by chunk

@@ -1,5 +1,5 @@
 """Device time of the listen's Qwen2 stage per chunk when C consecutive chunks of 8 users share one stage
-(fo.engine.ListenGroupGraph, C x 16 rows) against one chunk per stage (ListenGraph, 16 rows), real geometry; each
+(fo.engine.ListenGraph(chunks=C), C x 16 rows) against one chunk per stage (chunks=1, 16 rows), real geometry; each
 stage graph-replayed alone, then with its C encoder stages beside it on the side stream (the pipe's overlap).
 python scripts/group_stage_time.py [C ...] (GPU only)."""
 import ctypes
@@ -50,19 +50,13 @@ for C in Cs:
     res = eng.listen(items)
     items = [dict(identity="user", status="ipu_cl", feats=feats[b], kv=kvs[b], enc_cache=r["enc_cache"],
                   ada_cache=r["ada_cache"], pe_index=r["pe_index"]) for b, r in enumerate(res)]
-    if C == 1:
-        g = eng._listen_graph_for(items, slots=2, extra=128)
-        pe = g.submit_encoder(items, 0)
-        g.submit_llm(items, pe, 0)
-        llm_ex, enc_ex = g.llm_exec[0], [g.enc_exec[1]]
-    else:
-        g = eng._listen_graph_for(items, extra=128 * C, chunks=C)
-        pes = [g.submit_encoder(items, 0, j) for j in range(C)]
-        g.submit_llm([items] * C, pes, 0)
-        g.collect_llm(0)
-        for j in range(C):
-            g.submit_encoder(items, 1, j)
-        llm_ex, enc_ex = g.llm_exec[0][C], [g.enc_exec[1][C]]
+    g = eng._listen_graph_for(items, slots=2, extra=128 * C, chunks=C)
+    pes = [g.submit_encoder(items, 0, j) for j in range(C)]
+    g.submit_llm([items] * C, pes, 0)
+    g.collect_llm(0)
+    for j in range(C):
+        g.submit_encoder(items, 1, j)
+    llm_ex, enc_ex = g.llm_exec[0][C], [g.enc_exec[1][C]]
     torch.cuda.synchronize()
     main, side = g.main.cuda_stream, g.side.cuda_stream
 

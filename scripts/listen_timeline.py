@@ -34,20 +34,20 @@ orig_enc, orig_llm = ListenGraph.submit_encoder, ListenGraph.submit_llm
 counter = {"enc": 0, "llm": 0}
 
 
-def enc_wrap(self, items, k=0):
+def enc_wrap(self, items, k=0, j=0):
     c = counter["enc"]
     counter["enc"] += 1
     marks.append(("enc0", c, ev(self.side)))
-    r = orig_enc(self, items, k)
+    r = orig_enc(self, items, k, j)
     marks.append(("enc1", c, ev(self.side)))
     return r
 
 
-def llm_wrap(self, items, new_pe, k=0, wait=True):
+def llm_wrap(self, groups, pes, k=0):
     c = counter["llm"]
     counter["llm"] += 1
     marks.append(("llm0", c, ev(self.main)))
-    r = orig_llm(self, items, new_pe, k, wait)
+    r = orig_llm(self, groups, pes, k)
     marks.append(("llm1", c, ev(self.main)))
     return r
 

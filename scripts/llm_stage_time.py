@@ -32,8 +32,12 @@ for _ in range(3):   # steady-state chunks (graph path)
                   ada_cache=r["ada_cache"], pe_index=r["pe_index"]) for b, r in enumerate(res)]
     res = eng.listen(items)
 g = eng._listen_graph_for(items, slots=2, extra=128)
-pe = g.submit_encoder(items, 0)
-g.submit_llm(items, pe, 0)
+# (stages are captured on first use, per slot and chunks in the group: slot 1's encoder stage, the one the pipe
+# runs beside slot 0's LLM stage, by submitting a chunk to it)
+g.submit_llm([items], [g.submit_encoder(items, 0)], 0)
+g.collect_llm(0)
+g.submit_encoder(items, 1)
+llm_ex, enc_ex = g.llm_exec[0][1], g.enc_exec[1][1]
 torch.cuda.synchronize()
 main, side = g.main.cuda_stream, g.side.cuda_stream
 e0, e1 = ctypes.c_void_p(), ctypes.c_void_p()
@@ -59,17 +63,17 @@ lib.fo_event_create(ctypes.byref(ev_side))
 
 
 def llm_only():
-    _lib.call("fo_graph_launch", g.llm_exec[0], main)
+    _lib.call("fo_graph_launch", llm_ex, main)
 
 
 def enc_only():
-    _lib.call("fo_graph_launch", g.enc_exec[1], main)
+    _lib.call("fo_graph_launch", enc_ex, main)
 
 
 def both():   # encoder stage of the next chunk on the side stream beside this chunk's LLM stage
-    _lib.call("fo_graph_launch", g.enc_exec[1], side)
+    _lib.call("fo_graph_launch", enc_ex, side)
     _lib.call("fo_event_record", ev_side, side)
-    _lib.call("fo_graph_launch", g.llm_exec[0], main)
+    _lib.call("fo_graph_launch", llm_ex, main)
     _lib.call("fo_stream_wait_event", main, ev_side)
 
 
@@ -105,7 +109,7 @@ for nk in (150, 300, 600):
     def both_tiny(gx=gx):
         _lib.call("fo_graph_launch", gx, side)
         _lib.call("fo_event_record", ev_side, side)
-        _lib.call("fo_graph_launch", g.llm_exec[0], main)
+        _lib.call("fo_graph_launch", llm_ex, main)
         _lib.call("fo_stream_wait_event", main, ev_side)
     print(f"{nk:4d} tiny side-stream kernels: alone {timed(tiny_only):8.1f} us, beside the LLM stage "
           f"{timed(both_tiny):8.1f} us", flush=True)

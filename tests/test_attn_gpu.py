@@ -199,7 +199,7 @@ _group_cases = {}
 
 
 def _group_case(dev, H, KVH, hd):
-    """One group per geometry (pool, queries, kv.GroupMeta tables filled as ListenGroupGraph fills them, and the
+    """One group per geometry (pool, queries, kv.GroupMeta tables filled as ListenGraph(chunks=C) fills them, and the
     float64 reference), shared by the split settings; nothing in it is written after this."""
     if (H, KVH, hd) in _group_cases:
         return _group_cases[(H, KVH, hd)]
@@ -239,7 +239,7 @@ def _group_case(dev, H, KVH, hd):
 @pytest.mark.parametrize("H,KVH,hd", [(28, 4, 128), (4, 2, 32)])
 @pytest.mark.parametrize("graph_splits", [True, False])
 def test_attention_chunk_major_group_items(dev, H, KVH, hd, graph_splits):
-    """The item table of a listen group (engine.ListenGroupGraph at the benchmark's 8 chunks per Qwen2 stage): 8
+    """The item table of a listen group (engine.ListenGraph(chunks=C) at the benchmark's 8 chunks per Qwen2 stage): 8
     sessions of ragged lengths x 8 chunks of 2 tokens in one launch, rows chunk-major ([chunk][session][token]) so a
     session's 16 rows are not contiguous, the 64 items in (chunk, session) order -- one session's items interleaved
     with the others' -- and every row seeing the keys up to its own position (tok_nvis = pos + 1), i.e. the keys of

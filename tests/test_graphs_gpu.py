@@ -192,7 +192,7 @@ def _group_pipe(eng, feats_seq, n_users, C, decide=None):
 
 @pytest.mark.parametrize("C,n_chunks", [(2, 9), (4, 10), (3, 3), (8, 17), (7, 16)])
 def test_listen_group_pipe_matches_one_chunk_per_stage(eng, dev, C, n_chunks):
-    """C consecutive chunks per Qwen2 stage (fo.engine.ListenGroupGraph, the offline input's listen): every chunk's
+    """C consecutive chunks per Qwen2 stage (fo.engine.ListenGraph(chunks=C), the offline input's listen): every chunk's
     state probabilities (1e-4) and last hidden row (1e-3, the oracle-parity bound) equal the one-chunk-per-stage
     pipe's (the encoder and Qwen2 GEMMs tile C x the rows), its pe_index and the context lengths exactly; a partial
     last group (n_chunks % C) is flushed.  (8, 17) and (7, 16): the benchmark's 8 chunks per stage as 8 + 8 + 1 and

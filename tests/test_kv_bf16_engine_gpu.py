@@ -206,7 +206,7 @@ def _tiny_flow(eng, dev):
             for kv in kvs + [base]:
                 kv.free()
     assert len(eng._lgraphs) >= 1 and len(eng._tgraphs) >= 1   # the captured paths really ran
-    # the grouped listen (ListenGroupGraph), the bench's order
+    # the grouped listen (ListenGraph(chunks=C)), the bench's order
     base, kvs, state = sessions()
     try:
         pipe = eng.listen_pipe(2)

@@ -226,7 +226,7 @@ def test_real_geometry_encoder_adapter_match_reference(dev):
 
 @pytest.mark.parametrize("C,one_launch", [(4, True), (3, True), (4, False), (8, True), (7, True)])
 def test_real_geometry_encoder_chunk_groups_match_reference(dev, C, one_launch, monkeypatch):
-    """SpeechEncoderEngine.run(chunks=C) (the offline listen's encoder stage, fo.engine.ListenGroupGraph): C
+    """SpeechEncoderEngine.run(chunks=C) (the offline listen's encoder stage, fo.engine.ListenGraph(chunks=C)): C
     consecutive chunks of 2 sessions in one pass -- the front end, norms and GEMMs over all C x B x T rows, the rel-pos
     attention chunk by chunk on the ring -- against the reference's chunk-by-chunk outputs: framing A for 20 chunks
     (the 64-frame ring fills and trims inside a group), framing B for 8 chunks across the RelPE wrap (a partial last

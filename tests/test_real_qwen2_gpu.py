@@ -230,7 +230,7 @@ def _group_embeds(chunk, b, D=3584):
 def test_qwen2_real_geometry_listen_groups_match_reference(dev, llm, gold, C):
     """real_qwen2_group_t2.npz (make_golden.py real_qwen2_group: 15 consecutive 2-row chunks per session fed one call
     at a time to the reference's _llm_forward_core / _prediction_head_forward after the 9 + 2b-row prefill, each
-    session its own DynamicCache) against the Qwen2 stage of engine.ListenGroupGraph at C chunks per stage, driven
+    session its own DynamicCache) against the Qwen2 stage of engine.ListenGraph(chunks=C) at C chunks per stage, driven
     through the product's own tables (kv.GroupMeta: chunk-major rows, (chunk, session) items, decision rows, the
     tok_pos / tok_slot / tok_nvis / block-table fill), workspace and split count sized as _listen_graph_for sizes
     them, every distinct m captured with ListenGraph._capture on the engine stream and replayed.
@@ -266,7 +266,7 @@ def test_qwen2_real_geometry_listen_groups_match_reference(dev, llm, gold, C):
         h, bm = llm.forward(x0, [(q, r) for q, r in zip(seqs, rows0)])
         _close(h[bm.last_rows_host], gold["hid0"], 2e-3, 0, "prefill last rows")
         torch.cuda.synchronize()
-        # EngineCore._listen_graph_for as ListenPipe._push_group calls it (extra = 64 * 2 * C), ListenGroupGraph.__init__
+        # EngineCore._listen_graph_for as ListenPipe.push calls it (extra = 64 * 2 * C), ListenGraph.__init__
         max_keys = max(max(q.length for q in seqs) + 64 * 2 * C + 1024, 2048)
         gm = GroupMeta(B, To, C, llm.H // llm.KVH, max_keys, llm.pool.PS, dev)
         x = torch.empty(C * n1, D, dtype=torch.float32, device=dev)
@@ -276,7 +276,7 @@ def test_qwen2_real_geometry_listen_groups_match_reference(dev, llm, gold, C):
         with torch.cuda.stream(main):
             ops.Runtime.get(dev)   # the engine stream's GEMM scratch exists before anything is captured on it
 
-        def body(m):   # ListenGroupGraph._llm_body
+        def body(m):   # ListenGraph._llm_body
             xm = x[:m * n1]
             llm.stack.forward(xm, gm.metas[m], ws)
             ops.rmsnorm(xm, llm.norm, llm.eps, out=xm)

@@ -27,7 +27,7 @@ def test_state_head_matches_fp32(D):
 def test_state_head_group_decision_rows():
     """A listen group's state head at the benchmark's shape: 64 decision rows out of the 128 chunk-major rows of 8
     chunks x 8 sessions x 2 tokens (row j*n1 + b*To + To-1 for chunk j, session b: kv.GroupMeta's table, the one
-    ListenGroupGraph hands the kernel) at D = 3584, against the float64 softmax, 1e-5 absolute as above."""
+    ListenGraph(chunks=C) hands the kernel) at D = 3584, against the float64 softmax, 1e-5 absolute as above."""
     from fo.kv import GroupMeta
     dev = torch.device("cuda:0")
     B, To, C, D = 8, 2, 8, 3584
