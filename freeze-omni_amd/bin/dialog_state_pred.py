@@ -55,7 +55,8 @@ class DialogStateParams(DuplexSession):
                 "llm_mlp_mxfp4_rows": c.get("llm_mlp_mxfp4_rows", 16),
                 "llm_mlp_mxfp6_rows": c.get("llm_mlp_mxfp6_rows", 16), "llm_kv": c.get("llm_kv", "fp32"),
                 "llm_lm_head_weights": c.get("llm_lm_head_weights", "bf16"),
-                "llm_attn_weights": c.get("llm_attn_weights", "bf16")})
+                "llm_attn_weights": c.get("llm_attn_weights", "bf16"),
+                "llm_rows_x": c.get("llm_rows_x", "fp32")})
         return cls.PIPELINE_POOL
 
     def __init__(self, sid, socketio=None, event_outlet=None, user_ipu_outlet_list=(), parent_logger=None, vad=None):

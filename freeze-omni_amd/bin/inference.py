@@ -68,6 +68,9 @@ def get_args(argv=None):
     p.add_argument("--llm_attn_weights", choices=FORMATS["attn_weights"], default="bf16",
                    help="Qwen2 attention projection (q, k, v, o) weights: bf16, weight-only FP8 (e4m3 codes x a power of "
                         "two per output row) or weight-only MXFP4 (e2m1 codes x a power of two per 32 columns)")
+    p.add_argument("--llm_rows_x", choices=FORMATS["llm_rows_x"], default="fp32",
+                   help="GEMM inputs of the 65..128-row Qwen2 forwards (grouped listens, long prefills): fp32 or rounded "
+                        "to bf16, the reference's autocast arithmetic; steps of <= 64 rows are unchanged")
     p.add_argument("--role", default="You are a helpful assistant.")
     p.add_argument("--max_text_tokens", type=int, default=MAX_TEXT_TOKENS)
     args = p.parse_args(argv)

@@ -343,6 +343,7 @@ def dialog_session_factory(args):
     cfg["llm_kv"] = getattr(args, "llm_kv", None) or cfg.get("llm_kv", "fp32")
     cfg["llm_lm_head_weights"] = getattr(args, "llm_lm_head_weights", None) or cfg.get("llm_lm_head_weights", "bf16")
     cfg["llm_attn_weights"] = getattr(args, "llm_attn_weights", None) or cfg.get("llm_attn_weights", "bf16")
+    cfg["llm_rows_x"] = getattr(args, "llm_rows_x", None) or cfg.get("llm_rows_x", "fp32")
     ic = cfg.setdefault("inference_control", {})
     ic.update(top_k=args.top_k, top_p=args.top_p, temperature=args.temperature)
     DialogStateParams.DIALOG_STATE_PRED_CONFIGS = cfg
@@ -395,6 +396,9 @@ def get_parser():
     p.add_argument("--llm_attn_weights", choices=FORMATS["attn_weights"], default=None,
                    help="Qwen2 attention projection (q, k, v, o) weights: bf16 (default), weight-only FP8, or "
                         "weight-only MXFP4")
+    p.add_argument("--llm_rows_x", choices=FORMATS["llm_rows_x"], default=None,
+                   help="GEMM inputs of the 65..128-row Qwen2 forwards (grouped listens, long prefills): fp32 (default) or "
+                        "rounded to bf16, the reference's autocast arithmetic; steps of <= 64 rows are unchanged")
     p.add_argument("--config", default=None, help="duplex YAML (configs/dialog_state_pred_config.yaml form)")
     return p
 

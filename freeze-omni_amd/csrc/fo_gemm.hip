@@ -16,6 +16,7 @@
 //    epilogue, so results are deterministic and no cross-workgroup fence sits inside the GEMM.
 //  * mfma_f32_16x16x32_bf16 accumulates in fp32; bias/activation/residual/SwiGLU are fused
 //    into the epilogue.
+#include <atomic>
 #include <type_traits>
 
 #include "fo_common.h"
@@ -982,6 +983,9 @@ thread_local PackArm g_xpk;    // fo_gemm_set_xpack: the next launch's packed X 
 thread_local PackArm g_ypk;    // fo_gemm_set_ypack: the next launch's packed yg / Y output (hi, lo)
 thread_local PackArm g_yp32k;  // fo_gemm_set_ypack32 / _xpack32: fp32 fragment-order copies
 thread_local PackArm g_xp32k;
+// fo_gemm_set_x_bf16: the next launch may round its fp32 X rows to bf16 (taken by k_gemm_rows launches only, §5.12)
+thread_local int g_xb = 0;
+std::atomic<long long> g_rows_xb_launches{0};   // fo_gemm_rows_xb_count: k_gemm_rows launches that took it
 inline int arm_pack(PackArm& g, const void* p0, const void* p1, bool two, int cols, int cap_rb, const char* what) {
   g = PackArm{};
   FO_REQUIRE(!two || (p0 == nullptr) == (p1 == nullptr), "%s: both halves or neither", what);
@@ -1321,7 +1325,10 @@ __device__ __forceinline__ void wait_vm_barrier() {
 // f = 8 c + (r & 7) + 8 h (mod 64) holding chunk c of row r, which keeps the consumer's two ds_read_b128 free of
 // bank conflicts (its 16-lane groups read 16 consecutive 16-B slots).  Wave w computes row block w (RPW of them) for
 // every tile.
-template <int NWV, int RPW, int NTC, int DW, int DX>
+// XB (fo_gemm_set_x_bf16): the fragment is rounded once to bf16 and only the hi products are issued, in
+// the fp32 arm's order -- what this kernel computes on an X whose elements are bf16 values already (lo = +0).  X is still
+// fetched as fp32 rows, so the ring, the padding loads and every vmcnt count are those of the fp32 arm.
+template <int NWV, int RPW, int NTC, int DW, int DX, bool XB = false>
 __global__ __launch_bounds__(NWV * 64) void k_gemm_rows(GemmArgs a, int G, int tiles_per) {
   constexpr int RB = NWV * RPW;
   constexpr int LPW = (NTC + NWV - 1) / NWV;   // weight loads per wave per k-step (tile t: wave t % NWV)
@@ -1420,7 +1427,7 @@ __global__ __launch_bounds__(NWV * 64) void k_gemm_rows(GemmArgs a, int G, int t
       xp[r][0] = xr[i % PX][rb0 + r][xh0][xs0];
       xp[r][1] = xr[i % PX][rb0 + r][xh0][xs1];
     }
-    bf16x8 xh[RPW], xl[RPW];
+    bf16x8 xh[RPW], xl[XB ? 1 : RPW];
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
       const float f[8] = {xp[r][0].x, xp[r][0].y, xp[r][0].z, xp[r][0].w,
@@ -1429,7 +1436,7 @@ __global__ __launch_bounds__(NWV * 64) void k_gemm_rows(GemmArgs a, int G, int t
       for (int e = 0; e < 8; ++e) {
         const __bf16 h = (__bf16)f[e];
         xh[r][e] = h;
-        xl[r][e] = (__bf16)(f[e] - (float)h);
+        if constexpr (!XB) xl[r][e] = (__bf16)(f[e] - (float)h);
       }
     }
     // the weight fragments in groups of TG (all of them up to 20 tiles: VGPRs), each group's hi products of every
@@ -1447,12 +1454,14 @@ __global__ __launch_bounds__(NWV * 64) void k_gemm_rows(GemmArgs a, int G, int t
 #pragma unroll
           for (int r = 0; r < RPW; ++r)
             acc[t0 + t][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[r], wf[t], acc[t0 + t][r], 0, 0, 0);
+      if constexpr (!XB) {
 #pragma unroll
-      for (int t = 0; t < TG; ++t)
-        if (t0 + t < NTC)
+        for (int t = 0; t < TG; ++t)
+          if (t0 + t < NTC)
 #pragma unroll
-          for (int r = 0; r < RPW; ++r)
-            acc[t0 + t][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl[r], wf[t], acc[t0 + t][r], 0, 0, 0);
+            for (int r = 0; r < RPW; ++r)
+              acc[t0 + t][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl[r], wf[t], acc[t0 + t][r], 0, 0, 0);
+      }
     }
   }
   wait_vm<0>();   // (the padding loads past the last k-step) nothing of this workgroup's DMA outlives it
@@ -1595,9 +1604,10 @@ constexpr long long W_MID_BIG = 16 * MiB;       // 17..64 rows: 4-tile column gr
 constexpr long long W_HALVES_PLAIN = 8 * MiB;   // 65..128 rows as two halves: plain projections
 constexpr int DOWN_SPLIT = 8;                   // K split of the 7 / 8-tile long-K stream (Qwen2 down: 256 / 224 workgroups)
 
-// the packed buffers armed for a launch (one launch each)
+// what is armed for a launch (one launch each): the packed buffers, and the leave to round X to bf16
 struct Packs {
   PackArm x, y, y32, x32;
+  int xb = 0;
 };
 
 int check_call(const GemmCall& c, const Packs& pk) {
@@ -1701,6 +1711,7 @@ inline bool stream_call(const GemmCall& c) {
 // tiles re-reading the weights per row tile (q|k|v 80 us, r06q) or two row halves (o 2 x 22.8 us))
 struct RowsPlan {
   int S = 1, tiles_per = 0, G = 0;   // K splits, tiles per workgroup, tile groups
+  bool xb = false;                   // bf16-rounded X (fo_gemm_set_x_bf16 armed this launch)
 };
 bool plan_rows(const GemmCall& c, const Packs& pk, const WeightDesc& w, RowsPlan& p) {
   if (!(g_rows && c.M > 64 && c.M <= 128 && stream_call(c) && !c.sout1 && !c.rstats1 && w.bytes >= W_ROWS &&
@@ -1723,6 +1734,7 @@ bool plan_rows(const GemmCall& c, const Packs& pk, const WeightDesc& w, RowsPlan
     p.G = (w.ntiles + p.tiles_per - 1) / p.tiles_per;
     p.S = max(1, min(16, cus / p.G));
   }
+  p.xb = pk.xb != 0;
   const long long need = (long long)p.S * 128 * w.ntiles * 16;
   return p.tiles_per <= (c.swiglu ? 30 : 16) && need <= c.ws_floats && c.ws != nullptr && (c.K >> 5) >= p.S;
 }
@@ -1733,8 +1745,11 @@ int launch_rows(const GemmCall& c, GemmArgs& a, const RowsPlan& p) {
   const int total = p.S * p.G;
   const dim3 grid(8 * ((total + 7) / 8));
   // (instantiated tile counts: the Qwen2 gate/up's 14 pairs and down's 14 tiles per workgroup, else the next size)
-#define FO_ROWS(NTC_, DW_, DX_) \
-  hipLaunchKernelGGL((k_gemm_rows<8, 1, NTC_, DW_, DX_>), grid, dim3(512), 0, c.stream, a, p.G, p.tiles_per)
+#define FO_ROWS_XB(NTC_, DW_, DX_, XB_) \
+  hipLaunchKernelGGL((k_gemm_rows<8, 1, NTC_, DW_, DX_, XB_>), grid, dim3(512), 0, c.stream, a, p.G, p.tiles_per)
+#define FO_ROWS(NTC_, DW_, DX_)                 \
+  if (p.xb) FO_ROWS_XB(NTC_, DW_, DX_, true);   \
+  else FO_ROWS_XB(NTC_, DW_, DX_, false)
   if (c.swiglu && p.tiles_per > 20) {
     // the weights and X the same number of k-steps ahead: vmcnt retires in order, so the wait for a k-step's X also
     // waits for every weight load issued before it -- an X lead shorter than the weights' caps their depth at it
@@ -1748,11 +1763,13 @@ int launch_rows(const GemmCall& c, GemmArgs& a, const RowsPlan& p) {
     FO_ROWS(16, 3, 3);
   }
 #undef FO_ROWS
+#undef FO_ROWS_XB
   int rc = fo::check_launch("fo_gemm/rows");
   if (rc) return rc;
   launch_reduce(a, c.swiglu, 128, c.N, c.M, c.stream);
   fo::count_launch(FO_L_GEMM_ROWS);
   fo::count_launch(FO_L_GEMM_REDUCE);
+  if (p.xb) g_rows_xb_launches.fetch_add(1, std::memory_order_relaxed);
   return fo::check_launch("fo_gemm/rows reduce");
 }
 
@@ -2120,9 +2137,10 @@ int launch_grid(const GemmCall& c, GemmArgs& a, const WeightDesc& w) {
 // Y = act(X @ W^T + bias) (+Y if residual).  X bf16 or fp32 [M][ldx], K % 32 == 0.
 // swiglu != 0: Wp holds interleaved (gate, up) tile pairs, Y[m][n] = silu(gate) * up, n < N.
 int gemm_impl(const GemmCall& c) {
-  // the packed buffers armed for this launch are consumed whatever happens below (one launch each)
-  const Packs pk{g_xpk, g_ypk, g_yp32k, g_xp32k};
+  // what is armed for this launch is consumed whatever happens below (one launch each)
+  const Packs pk{g_xpk, g_ypk, g_yp32k, g_xp32k, g_xb};
   g_xpk = g_ypk = g_yp32k = g_xp32k = PackArm{};
+  g_xb = 0;
   if (int rc = check_call(c, pk)) return rc;
   WeightDesc w;
   w.ntiles = (c.swiglu ? 2 : 1) * ((c.N + 15) / 16);
@@ -2313,6 +2331,22 @@ int fo_gemm_set_trace(void* trace) {
 
 int fo_gemm_set_xpack(const void* hi, const void* lo, int cols, int cap_rb) {
   return arm_pack(g_xpk, hi, lo, true, cols, cap_rb, "fo_gemm_set_xpack");
+}
+
+// The calling thread's next launch through gemm_impl may round its fp32 X rows to bf16 (1; 0 disarms).  A permission:
+// only a launch that plan_rows gives to k_gemm_rows takes it; any launch consumes it.
+int fo_gemm_set_x_bf16(int on) {
+  g_xb = 0;
+  FO_REQUIRE(on == 0 || on == 1, "fo_gemm_set_x_bf16: 0 or 1 (got %d)", on);
+  g_xb = on;
+  return 0;
+}
+
+long long fo_gemm_rows_xb_count(void) { return g_rows_xb_launches.load(std::memory_order_relaxed); }
+
+int fo_gemm_rows_xb_count_reset(void) {
+  g_rows_xb_launches.store(0, std::memory_order_relaxed);
+  return 0;
 }
 
 int fo_gemm_set_ypack32(void* p, int cols, int cap_rb) {

@@ -77,6 +77,9 @@ _SIGS = {
                                 c_vp, c_vp, c_vp, c_float, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "fo_attn_max_rows": (c_int, [c_int]),
     "fo_gemm_set_rows": (c_int, [c_int]),
+    "fo_gemm_set_x_bf16": (c_int, [c_int]),
+    "fo_gemm_rows_xb_count": (c_ll, []),
+    "fo_gemm_rows_xb_count_reset": (c_int, []),
     "fo_set_kv_bf16": (c_int, [c_int]),
     "fo_conv_set_trace": (c_int, [c_vp]),
     "fo_attention_set_trace": (c_int, [c_vp]),

@@ -71,8 +71,20 @@ class FreezeOmniEngine:
     def __init__(self, model_path, llm_path=None, device="cuda:0", max_sessions=64, llm_kv_tokens=None,
                  tts_kv_tokens=None, source=None, receive_weights=False, train_yaml=None, mlp_weights="bf16",
                  mlp_fp8_rows=16, llm_kv="fp32", mlp_mxfp4_rows=16, lm_head_weights="bf16",
-                 attn_weights="bf16", mlp_mxfp6_rows=16):
-        """attn_weights: "bf16" (default), "fp8" or "mxfp4": self_attn.{q,k,v,o}_proj.weight of every Qwen2 layer under
+                 attn_weights="bf16", mlp_mxfp6_rows=16, llm_rows_x="fp32"):
+        """llm_rows_x: "fp32" (default) or "bf16": the GEMM inputs of the Qwen2 stack's 65..128-row forwards -- the 8-,
+        7-, 6- and 5-chunk listen groups at 8 sessions, a 65..128-row prefill -- rounded once to bf16, the reference's
+        bf16-autocast arithmetic.  Launches of <= 64 rows, the row-halves fallback and every quantised
+        code stream keep fp32 inputs, so a session's one-chunk listens, duplex ticks and text steps are bit for bit
+        what they are without it.  It changes no weights (replicas and the weight broadcast need nothing) and combines
+        freely with every weight and KV option; the speech decoder's stack and the encoder are untouched.
+        Builder-run A/B (not driver-timed):
+        per GEMM launched back to back at 128 rows, fp32 -> bf16: q|k|v 28.3 -> 26.5, o 24.4 -> 22.5, gate/up 98.6 ->
+        84.9, down 54.9 -> 44.6 us;
+        inside the stack less: the captured 8-chunk Qwen2 stage 5,784 -> 5,509 us (0.95); beyond the fp32 arm's spread
+        (profiles/rows_x_bf16_*).  The mode misses the fp32-calibrated hidden bound against the reference-run golden
+        (4.9e-3 against 2e-3).
+        attn_weights: "bf16" (default), "fp8" or "mxfp4": self_attn.{q,k,v,o}_proj.weight of every Qwen2 layer under
         weight-only FP8 per output row or MXFP4, independent of mlp_weights, mlp_*_rows, lm_head_weights
         and llm_kv; the biases and the AR speech decoder's stack are untouched.  Steps of <= 16 rows stream the codes
         where ops.ATTN_POLICY says so; everything else runs the exact bf16 image.  `src` serves the dequantised
@@ -122,6 +134,7 @@ class FreezeOmniEngine:
         self.llm_kv = check_format("llm_kv", llm_kv)
         self.lm_head_weights = check_format("lm_head_weights", lm_head_weights)
         self.attn_weights = check_format("attn_weights", attn_weights)
+        self.llm_rows_x = check_format("llm_rows_x", llm_rows_x)
         self._llm_options()   # (refuses a *_rows option without its format before anything is loaded)
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
@@ -169,7 +182,7 @@ class FreezeOmniEngine:
             if r != 16 and self.mlp_weights != fmt:
                 raise ValueError(f"mlp_{fmt}_rows={r} needs mlp_weights={fmt!r}")
         return dict(mlp_weights=self.mlp_weights, mlp_rows=rows.get(self.mlp_weights, 16), kv_dtype=self.llm_kv,
-                    lm_head_weights=self.lm_head_weights, attn_weights=self.attn_weights)
+                    lm_head_weights=self.lm_head_weights, attn_weights=self.attn_weights, rows_x=self.llm_rows_x)
 
     def _model_source(self, raw):
         """`raw` as the model this engine computes: the MLP, the head and / or the attention projections replaced by

@@ -16,8 +16,12 @@ from .weights import ReceiveSource
 
 class LLMEngine:
     def __init__(self, src, llm_cfg, device, head_src=None, kv_tokens=65536, page_size=16, max_pos=None,
-                 mlp_weights="bf16", mlp_rows=16, kv_dtype="fp32", lm_head_weights="bf16", attn_weights="bf16"):
-        """mlp_weights: "bf16" (default), "fp8", "mxfp4" or "mxfp6" -- mlp.{gate,up,down}_proj.weight of every layer
+                 mlp_weights="bf16", mlp_rows=16, kv_dtype="fp32", lm_head_weights="bf16", attn_weights="bf16",
+                 rows_x="fp32"):
+        """rows_x: "fp32" (default) or "bf16" -- the GEMM inputs of the 65..128-row forwards (the 5..8-chunk listen
+        groups at 8 sessions, a 65..128-row prefill) rounded to bf16, the reference's autocast arithmetic (DESIGN
+        §5.12; DecoderStack rows_x).  Steps of <= 64 rows are bit for bit what they are without it.
+        mlp_weights: "bf16" (default), "fp8", "mxfp4" or "mxfp6" -- mlp.{gate,up,down}_proj.weight of every layer
         under that weight-only format, and mlp_rows, the most rows of a step that stream
         the codes: DecoderStack's options of the same names.
         attn_weights: "bf16" (default), "fp8" or "mxfp4" -- self_attn.{q,k,v,o}_proj.weight of every layer under
@@ -37,6 +41,7 @@ class LLMEngine:
         self.mlp_weights = check_format("mlp_weights", mlp_weights)
         self.lm_head_weights = check_format("lm_head_weights", lm_head_weights)
         self.attn_weights = check_format("attn_weights", attn_weights)
+        self.rows_x = check_format("llm_rows_x", rows_x)
         self.mlp_rows = mlp_rows
         self.kv_dtype = kv_dtype
         c = llm_cfg
@@ -53,7 +58,7 @@ class LLMEngine:
                            dtype={"fp32": torch.float32, "bf16": torch.bfloat16, "e4m3": torch.float8_e4m3fn}[kv_dtype])
         self.stack = DecoderStack(src, "model.layers.", c["num_hidden_layers"], self.D, self.H, self.KVH, self.eps,
                                   True, self.rope, self.pool, first_fp16=True, mlp_weights=mlp_weights,
-                                  mlp_rows=mlp_rows, attn_weights=attn_weights)
+                                  mlp_rows=mlp_rows, attn_weights=attn_weights, rows_x=rows_x)
         self.embed_tokens = src.get("model.embed_tokens.weight", torch.bfloat16)
         self.norm = src.get("model.norm.weight")
         if lm_head_weights == "bf16":

@@ -217,15 +217,17 @@ class PackedLinear:
     shift = None
 
     def __call__(self, x, out=None, act="none", residual=False, out_dtype=F32, splitk=0, M=None, norm=None,
-                 stats_out=None, xpack=None, ypack=None):
+                 stats_out=None, xpack=None, ypack=None, x_round=None):
         """x: fp32 or bf16 [M, >=Kp] (row stride x.stride(0)); returns out [M, N].
         norm: (RowStats, eps): x is the producer's yg (= residual * gamma) and rows are scaled by the
         RMSNorm rstd from the producer's statistics; stats_out: RowStats this GEMM fills (see RowStats).
         xpack: XPack holding x (<= 64 rows) pre-split in fragment order (written by its producer), read instead of
         splitting x by the kernels that take packed X (include/fo_hip.h fo_gemm_set_xpack; the others read x);
-        ypack: XPack this GEMM fills with stats_out's yg -- or, without stats_out, its output (<= 64 rows)."""
+        ypack: XPack this GEMM fills with stats_out's yg -- or, without stats_out, its output (<= 64 rows).
+        x_round: None, or "bf16": the launch may round its fp32 x to bf16 (fo_gemm_set_x_bf16, DESIGN §5.12: taken by
+        the 65..128-row k_gemm_rows launches only; every other launch runs as without it)."""
         if norm is not None or stats_out is not None:
-            return self._call_norm(x, out, act, residual, out_dtype, splitk, M, norm, stats_out, xpack, ypack)
+            return self._call_norm(x, out, act, residual, out_dtype, splitk, M, norm, stats_out, xpack, ypack, x_round)
         _check_dev(x)
         if x.dtype not in (BF16, F32):
             raise TypeError("PackedLinear input must be fp32 or bf16")
@@ -235,7 +237,7 @@ class PackedLinear:
         if out is None:
             out = torch.empty(M, self.N, dtype=out_dtype, device=x.device)
         rt = Runtime.get(x.device)
-        with _packed(xpack, None):
+        with _packed(xpack, None, x_round=x_round):
             _lib.call("fo_gemm", x.data_ptr(), 1 if x.dtype == F32 else 0, x.stride(0), M, self.Kp,
                       self.packed.data_ptr(), self.N, 1 if self.swiglu else 0, ptr(self.bias), ptr(self.scale),
                       ptr(self.shift), out.data_ptr(), out.stride(0), 1 if out.dtype == BF16 else 0, ACT[act],
@@ -282,9 +284,11 @@ class PackedLinear:
         stats.groups = sg.value
         return out
 
-    def qkv_rope(self, x, M, pos, slot, cos_t, sin_t, q_out, kc, vc, H, KVH, PS, norm=None, splitk=0, xpack=None):
+    def qkv_rope(self, x, M, pos, slot, cos_t, sin_t, q_out, kc, vc, H, KVH, PS, norm=None, splitk=0, xpack=None,
+                 x_round=None):
         """Fused q|k|v projection + bias + RoPE + paged-KV append (weight packed with rope_hd):
-        q_out [M, H*hd] gets the rotated queries, kc/vc (one layer's pages) the token's K/V rows at slot[m]."""
+        q_out [M, H*hd] gets the rotated queries, kc/vc (one layer's pages) the token's K/V rows at slot[m].
+        x_round: as in __call__."""
         _check_dev(x)
         if self.rope_hd is None:
             raise RuntimeError("qkv_rope needs a weight packed with rope_hd")
@@ -293,7 +297,7 @@ class PackedLinear:
         rt = Runtime.get(x.device)
         rst, rg, eps = _norm_args(norm)[:3]
         kvb = kv_bytes(kc, vc)
-        with _packed(xpack, None):
+        with _packed(xpack, None, x_round=x_round):
             _lib.call("fo_gemm_qkv_rope_kv", x.data_ptr(), 1 if x.dtype == F32 else 0, x.stride(0), M, self.Kp,
                       self.packed.data_ptr(), self.N, ptr(self.bias), rt.ws.data_ptr(), rt.ws.numel(),
                       rt.counters.data_ptr(), splitk, rst, rg, eps, pos.data_ptr(), slot.data_ptr(), cos_t.data_ptr(),
@@ -301,7 +305,8 @@ class PackedLinear:
                       kvb, stream(x.device))
         return q_out
 
-    def _call_norm(self, x, out, act, residual, out_dtype, splitk, M, norm, stats_out, xpack=None, ypack=None):
+    def _call_norm(self, x, out, act, residual, out_dtype, splitk, M, norm, stats_out, xpack=None, ypack=None,
+                   x_round=None):
         import ctypes
         _check_dev(x)
         if x.stride(-1) != 1 or x.shape[-1] < self.Kp or out_dtype != F32:
@@ -314,7 +319,7 @@ class PackedLinear:
         sg = ctypes.c_int(0)
         if ypack is not None and stats_out is None:
             raise ValueError("ypack packs the stats_out yg: pass stats_out")
-        with _packed(xpack, ypack):
+        with _packed(xpack, ypack, x_round=x_round):
             _lib.call("fo_gemm_rms", x.data_ptr(), 1 if x.dtype == F32 else 0, x.stride(0), M, self.Kp,
                       self.packed.data_ptr(), self.N, 1 if self.swiglu else 0, ptr(self.bias), out.data_ptr(),
                       out.stride(0), ACT[act], 1 if residual else 0, rt.ws.data_ptr(), rt.ws.numel(),
@@ -590,14 +595,17 @@ class PackedLinearQuant(_QuantCodes):
         return rows <= self.stream_rows and (rows + 15) // 16 in self.rows_rb
 
     def __call__(self, x, out=None, act="none", residual=False, out_dtype=F32, splitk=0, M=None, norm=None,
-                 stats_out=None, xpack=None, ypack=None):
+                 stats_out=None, xpack=None, ypack=None, x_round=None):
+        """x_round goes to the bf16 image only: the code streams read fp32 rows whatever it says."""
         rows = x.shape[0] if M is None else M
         head = self._head   # (the head entry is plain: anything else runs the image)
         if (not self.streams(rows) or x.dtype != F32 or act != "none" or out_dtype != F32 or
                 (out is not None and out.dtype != F32) or
                 (head and (residual or norm is not None or stats_out is not None))):
             return self.bf16(x, out=out, act=act, residual=residual, out_dtype=out_dtype, splitk=splitk, M=M, norm=norm,
-                             stats_out=stats_out, xpack=xpack, ypack=ypack)
+                             stats_out=stats_out, xpack=xpack, ypack=ypack, x_round=x_round)
+        if x_round not in X_ROUNDS:
+            raise ValueError(f"x_round must be one of {X_ROUNDS}, got {x_round!r}")
         _check_dev(x)
         if x.stride(-1) != 1 or x.shape[-1] < self.Kp:
             raise ValueError(f"{type(self).__name__} input needs unit stride and >= {self.Kp} columns, got "
@@ -702,10 +710,13 @@ class PackedQKVQuant(_QuantCodes):
         """Whether a qkv_rope call of `rows` fp32 rows streams the codes (else it runs the bf16 image)."""
         return rows <= 16 and self.stream
 
-    def qkv_rope(self, x, M, pos, slot, cos_t, sin_t, q_out, kc, vc, H, KVH, PS, norm=None, splitk=0, xpack=None):
+    def qkv_rope(self, x, M, pos, slot, cos_t, sin_t, q_out, kc, vc, H, KVH, PS, norm=None, splitk=0, xpack=None,
+                 x_round=None):
         if not self.streams(M) or x.dtype != F32:
             return self.bf16.qkv_rope(x, M, pos, slot, cos_t, sin_t, q_out, kc, vc, H, KVH, PS, norm=norm,
-                                      splitk=splitk, xpack=xpack)
+                                      splitk=splitk, xpack=xpack, x_round=x_round)
+        if x_round not in X_ROUNDS:
+            raise ValueError(f"x_round must be one of {X_ROUNDS}, got {x_round!r}")
         _check_dev(x)
         if x.stride(-1) != 1 or x.shape[-1] < self.K:
             raise ValueError(f"qkv_rope input needs unit stride and >= {self.K} columns, got {tuple(x.shape)}")
@@ -819,15 +830,23 @@ class XPack32:
         self.buf = torch.empty(K * 16 * self.rb, dtype=F32, device=device)
 
 
+X_ROUNDS = (None, "bf16")   # x_round of the GEMM wrappers
+
+
 class _packed:
     """Arms fo_gemm's packed-X input / packed-yg output for the one launch inside the block (thread-local in the
     library, consumed by that launch -- also when the launch refuses its arguments, e.g. a pack whose extent does not
-    fit); the disarm on an exception covers a failure between the setters and the launch."""
+    fit); the disarm on an exception covers a failure between the setters and the launch.  x_round="bf16" arms
+    fo_gemm_set_x_bf16 beside them, with the same lifetime."""
 
-    def __init__(self, xpack, ypack, xpack32=None, ypack32=None):
-        self.x, self.y, self.x32, self.y32 = xpack, ypack, xpack32, ypack32
+    def __init__(self, xpack, ypack, xpack32=None, ypack32=None, x_round=None):
+        if x_round not in X_ROUNDS:
+            raise ValueError(f"x_round must be one of {X_ROUNDS}, got {x_round!r}")
+        self.x, self.y, self.x32, self.y32, self.xb = xpack, ypack, xpack32, ypack32, x_round == "bf16"
 
     def __enter__(self):
+        if self.xb:
+            _lib.call("fo_gemm_set_x_bf16", 1)
         if self.x is not None:
             _lib.call("fo_gemm_set_xpack", self.x.hi.data_ptr(), self.x.lo.data_ptr(), self.x.K, self.x.rb)
         if self.y is not None:
@@ -839,6 +858,8 @@ class _packed:
 
     def __exit__(self, et, ev, tb):
         if et is not None:
+            if self.xb:
+                _lib.call("fo_gemm_set_x_bf16", 0)
             if self.x is not None:
                 _lib.call("fo_gemm_set_xpack", None, None, 0, 0)
             if self.y is not None:
@@ -1082,6 +1103,16 @@ def kv8_launch_counts():
 
 def kv8_launch_counts_reset():
     _lib.call("fo_kv8_counts_reset")
+
+
+def rows_xb_launch_count():
+    """k_gemm_rows launches that took bf16-rounded X (x_round="bf16") since the last reset; they also
+    count as gemm_rows / gemm_reduce in launch_counts()."""
+    return int(_lib.load().fo_gemm_rows_xb_count())
+
+
+def rows_xb_launch_count_reset():
+    _lib.call("fo_gemm_rows_xb_count_reset")
 
 
 def _check_kv8(what, kc, kscale, vc, vscale):

@@ -23,6 +23,7 @@ FORMATS = {"mlp_weights": ("bf16",) + WEIGHT_FORMATS,
            "lm_head_weights": ("bf16",) + WEIGHT_FORMATS,
            "attn_weights": ("bf16",) + ATTN_WEIGHT_FORMATS,
            "llm_kv": ("fp32", "bf16", "e4m3"),
+           "llm_rows_x": ("fp32", "bf16"),
            "FakeQuantSource format": WEIGHT_FORMATS,
            "FakeQuantSource lm_head": (None,) + WEIGHT_FORMATS,
            "FakeQuantSource attn": (None,) + ATTN_WEIGHT_FORMATS}

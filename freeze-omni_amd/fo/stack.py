@@ -34,8 +34,18 @@ class Layer:
 
 class DecoderStack:
     def __init__(self, src, prefix, n_layers, D, H, KVH, eps, bias, rope, pool, kv_layer0=0, first_fp16=False,
-                 attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT, mlp_weights="bf16", mlp_rows=16, attn_weights="bf16"):
-        """attn_weights: "bf16", "fp8" or "mxfp4": the q|k|v and o projections under weight-only FP8 / MXFP4
+                 attn_keys_per_split=ops.ATTN_KEYS_PER_SPLIT, mlp_weights="bf16", mlp_rows=16, attn_weights="bf16",
+                 rows_x="fp32"):
+        """rows_x: "fp32", or "bf16": forwards of 65..128 rows hand their four GEMMs x_round="bf16" (the
+        k_gemm_rows launches round their fp32 input rows to bf16, the reference's autocast arithmetic; an arithmetic,
+        not a dispatch choice -- all four GEMMs, no per-GEMM policy).  Forwards of <= 64 rows, the row-halves fallback
+        and every quantised code stream keep fp32 inputs, bit for bit.  Builder-run A/B (not driver-timed):
+        per GEMM launched back to back at 128 rows, fp32 -> bf16: q|k|v 28.3 -> 26.5, o 24.4 -> 22.5, gate/up 98.6 ->
+        84.9, down 54.9 -> 44.6 us;
+        inside the stack less: the captured 8-chunk Qwen2 stage 5,784 -> 5,509 us (0.95); beyond the fp32 arm's spread
+        (profiles/rows_x_bf16_*).  The mode misses the fp32-calibrated hidden bound against the reference-run golden
+        (4.9e-3 against 2e-3).
+        attn_weights: "bf16", "fp8" or "mxfp4": the q|k|v and o projections under weight-only FP8 / MXFP4
         (ops.PackedQKVQuant, and ops.PackedLinearW8 / W4 with kind="attn_o": the four projection weights become
         q * 2^e, the biases stay; forwards of <= 16 rows stream the codes where ops.ATTN_POLICY says so, everything else
         runs the exact bf16 image).  Independent of the MLP options.
@@ -46,6 +56,7 @@ class DecoderStack:
         ops.W8_ROWS_POLICY / W4_ROWS_POLICY / W6_ROWS_POLICY) or 128 (FP8: 65..128-row ones as well)."""
         self.mlp_weights = check_format("mlp_weights", mlp_weights)
         self.attn_weights = check_format("attn_weights", attn_weights)
+        self.rows_x = check_format("llm_rows_x", rows_x)
         self.mlp_rows = mlp_rows
         self.n, self.D, self.H, self.KVH, self.hd, self.eps = n_layers, D, H, KVH, D // H, eps
         self.attn_kps = attn_keys_per_split
@@ -201,6 +212,8 @@ class DecoderStack:
                 xgp_qkv = None
             if self.layers[0].o.streams(T):
                 attp = xgp_gu = None
+        # rows_x="bf16": the 65..128-row forwards' GEMMs may round their fp32 input rows to bf16 (k_gemm_rows only)
+        xr = "bf16" if self.rows_x == "bf16" and 64 < T <= 128 else None
         eager = x.is_cuda and not torch.cuda.is_current_stream_capturing()
         kps = self.attn_kps or (ops.attn_keys_per_split(meta.max_keys, meta.n_items, KVH, hd, x.device) if eager else 128)
         for i, L in enumerate(self.layers):
@@ -216,7 +229,7 @@ class DecoderStack:
             xin, norm = (h, None) if i == 0 else (xg, (sA, self.eps))
             if i == 0 and not pre_normed:
                 ops.rmsnorm(x, L.ln1, self.eps, out=h, round_fp16=self.first_fp16, M=T)
-            L.qkv.qkv_rope(xin, T, *rope, norm=norm, xpack=xgp_qkv if i > 0 else None)
+            L.qkv.qkv_rope(xin, T, *rope, norm=norm, xpack=xgp_qkv if i > 0 else None, x_round=xr)
             scales = {}
             if self.kv8:
                 scales = {"kscale": self.pool.ks[li], "vscale": self.pool.vs[li]}
@@ -230,12 +243,14 @@ class DecoderStack:
                               meta.block_table, self.pool.PS, kc, vc, H, KVH, hd, scale,
                               nsplit, part_ml, part_o, att, tickets=ws["tickets"], keys_per_split=kps,
                               opack=attp, **scales)
-                L.o(att, out=x, residual=True, M=T, stats_out=sB.set(L.ln2, xg), xpack=attp, ypack=xgp_gu)
-            L.gu(xg, out=m, M=T, norm=(sB, self.eps), xpack=xgp_gu)
+                L.o(att, out=x, residual=True, M=T, stats_out=sB.set(L.ln2, xg), xpack=attp, ypack=xgp_gu,
+                    x_round=xr)
+            L.gu(xg, out=m, M=T, norm=(sB, self.eps), xpack=xgp_gu, x_round=xr)
             if i == last and final_norm is None:
-                L.down(m, out=x, residual=True, M=T)
+                L.down(m, out=x, residual=True, M=T, x_round=xr)
             elif i == last:
-                L.down(m, out=x, residual=True, M=T, stats_out=sA.set(final_norm, xg))
+                L.down(m, out=x, residual=True, M=T, stats_out=sA.set(final_norm, xg), x_round=xr)
             else:
-                L.down(m, out=x, residual=True, M=T, stats_out=sA.set(self.layers[i + 1].ln1, xg), ypack=xgp_qkv)
+                L.down(m, out=x, residual=True, M=T, stats_out=sA.set(self.layers[i + 1].ln1, xg), ypack=xgp_qkv,
+                       x_round=xr)
         return x

@@ -94,14 +94,15 @@ class AudioLLM:
     @classmethod
     def from_model_dir(cls, model_path, llm_path=None, device="cuda:0", train_yaml=None, receive_weights=False,
                        mlp_weights="bf16", mlp_fp8_rows=16, llm_kv="fp32", mlp_mxfp4_rows=16, lm_head_weights="bf16",
-                       attn_weights="bf16", mlp_mxfp6_rows=16, **kw):
+                       attn_weights="bf16", mlp_mxfp6_rows=16, llm_rows_x="fp32", **kw):
         """FreezeOmniEngine's options of the same names, each independent of the others:
         mlp_weights, lm_head_weights, attn_weights: the Qwen2 MLP, output head and q, k, v, o projections as "bf16" or
         under one of the option's weight-only formats (fo.quant.FORMATS);
         mlp_fp8_rows: 16, 64 or 128 (with fp8, 64 lets 17..64-row Qwen2 steps stream the codes too, 128 65..128-row
         ones as well); mlp_mxfp4_rows: 16 or 64 (with mxfp4, 64 lets 17..64-row Qwen2 steps stream the codes too);
         mlp_mxfp6_rows: 16 or 64 (the same with mxfp6);
-        llm_kv: "fp32", "bf16" or "e4m3", the Qwen2 paged KV's element."""
+        llm_kv: "fp32", "bf16" or "e4m3", the Qwen2 paged KV's element;
+        llm_rows_x: "fp32" or "bf16", the GEMM inputs of the Qwen2 stack's 65..128-row forwards."""
         for opt, value in (("mlp_weights", mlp_weights), ("lm_head_weights", lm_head_weights),
                            ("attn_weights", attn_weights)):
             check_format(opt, value)
@@ -109,7 +110,8 @@ class AudioLLM:
                                     receive_weights=receive_weights, mlp_weights=mlp_weights,
                                     mlp_fp8_rows=mlp_fp8_rows, llm_kv=llm_kv,
                                     mlp_mxfp4_rows=mlp_mxfp4_rows, lm_head_weights=lm_head_weights,
-                                    attn_weights=attn_weights, mlp_mxfp6_rows=mlp_mxfp6_rows), **kw)
+                                    attn_weights=attn_weights, mlp_mxfp6_rows=mlp_mxfp6_rows,
+                                    llm_rows_x=llm_rows_x), **kw)
 
     def setup_logger(self, parent_logger=None):
         if parent_logger is not None:

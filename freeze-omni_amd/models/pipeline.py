@@ -36,7 +36,8 @@ class inferencePipeline:
         args["llm_mlp_fp8_rows"]: 16 (default), 64 or 128, its mlp_fp8_rows;
         args["llm_mlp_mxfp4_rows"]: 16 (default) or 64, its mlp_mxfp4_rows;
         args["llm_mlp_mxfp6_rows"]: 16 (default) or 64, its mlp_mxfp6_rows;
-        args["llm_kv"]: "fp32" (default), "bf16" or "e4m3", its llm_kv (the Qwen2 paged KV's element)."""
+        args["llm_kv"]: "fp32" (default), "bf16" or "e4m3", its llm_kv (the Qwen2 paged KV's element);
+        args["llm_rows_x"]: "fp32" (default) or "bf16", its llm_rows_x (the 65..128-row Qwen2 GEMM inputs)."""
         if isinstance(args, argparse.Namespace):
             args = vars(args)
         for opt in ("mlp_weights", "lm_head_weights", "attn_weights"):
@@ -57,7 +58,8 @@ class inferencePipeline:
                                              mlp_mxfp6_rows=args.get("llm_mlp_mxfp6_rows") or 16,
                                              llm_kv=args.get("llm_kv") or "fp32",
                                              lm_head_weights=args.get("llm_lm_head_weights") or "bf16",
-                                             attn_weights=args.get("llm_attn_weights") or "bf16")
+                                             attn_weights=args.get("llm_attn_weights") or "bf16",
+                                             llm_rows_x=args.get("llm_rows_x") or "fp32")
         if weights_from is not None:
             from fo.replica import copy_frozen
             copy_frozen(weights_from.model.engine, self.model.engine)

@@ -140,6 +140,19 @@ int fo_gemm_set_xpack(const void* hi, const void* lo, int cols, int cap_rb);
 int fo_gemm_set_ypack(void* hi, void* lo, int cols, int cap_rb);
 int fo_gemm_set_ypack32(void* p, int cols, int cap_rb);
 int fo_gemm_set_xpack32(const void* p, int cols, int cap_rb);
+/* bf16 GEMM inputs for the 65..128-row launches (the reference's autocast arithmetic).
+ * fo_gemm_set_x_bf16(1) arms the calling thread's NEXT launch of any fo_gemm* entry (thread-local, consumed by that
+ * launch whether it succeeds, is refused, or has no use for it; 0 disarms; any other value is refused, -2, and leaves
+ * nothing armed).  The arm is a permission: only a launch that takes k_gemm_rows (65..128 fp32 rows, >= 16 MiB of
+ * packed weight, slabs that fit, fo_gemm_set_rows on) computes epilogue(bf16(X) . W^T) -- every X element rounded once
+ * to bf16 (nearest even), the products accumulated in fp32 in the order of the fp32 arm's hi products, everything
+ * else unchanged -- which is bit for bit the unarmed launch on X.bfloat16().float().  Every other launch (<= 64 rows,
+ * the row-halves fallback, bf16 X, small weights, the quantised code streams) runs as if nothing were armed.
+ * fo_gemm_rows_xb_count: the k_gemm_rows launches that took the arm since the last reset (process-wide, counted on
+ * the host at issue; they also count as FO_L_GEMM_ROWS / FO_L_GEMM_REDUCE as before). */
+int fo_gemm_set_x_bf16(int on);
+long long fo_gemm_rows_xb_count(void);
+int fo_gemm_rows_xb_count_reset(void);
 /* the calling thread's NEXT fo_attention (<= 64 tokens, not with the separate combine launch; cols = H * hd) or
  * fo_relpos_attention_fused (<= 64 rows; cols = h * dk) launch also writes its output packed as fo_gemm_set_xpack
  * reads it, with the same extent check.  A launch whose host contract is broken (keys beyond the block table)
