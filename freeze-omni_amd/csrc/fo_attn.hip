@@ -574,15 +574,23 @@ __global__ __launch_bounds__(256) void k_relpos_attn(const float* q, int ldq, co
   }
 }
 
-// Fused ring append + rel-pos attention for one (user, head): the chunk's new K/V rows come straight
-// from the QKV GEMM output and are written into the user's ring (MultiHeadedAttention.infer's
-// cat-and-trim, models/encoder/attention.py:415-428) while every key/value/position row this head
-// needs is staged in LDS with 16-B coalesced loads; scores, softmax and P.V then run out of LDS.
-__global__ __launch_bounds__(256) void k_relpos_fused(const float* qkv, int ldq, float* kr, float* vr, int cap,
-                                                      const int* start, const int* len, const int* ring,
-                                                      const float* ptab, const int* pstart, const float* bu,
-                                                      const float* bv, int T, int h, int dk, float scale, float* out,
-                                                      int ldo, uint16_t* oph, uint16_t* opl, int prb) {
+// Rel-pos attention of one chunk for one (user, head) out of LDS, the body of both encoder kernels below: every key /
+// value / position row this head needs is staged in LDS with 16-B coalesced loads; scores, softmax and P.V then run
+// out of LDS (MultiHeadedAttention.infer, models/encoder/attention.py:415-428).  The caller resolves the work group's
+// ring slot rb, ring start st, rows Lold already in the ring (Lold + T <= cap, which the host cannot check: the
+// engine's cap is its buffersize + the largest T), position start ps and first q|k|v row row0.
+//   fused   (CHUNKS = false, k_relpos_fused): a context row is in the ring or is one of the chunk's own q|k|v rows;
+//           the new rows are appended to the ring while staging (the cat-and-trim), and the output is also written
+//           packed when oph is set.
+//   grouped (CHUNKS = true, k_relpos_chunks): chunk jc of a group whose q|k|v rows are chunk-major (row
+//           (jc * B + b) * T + i); a context row is in the ring as it was before the launch, one of the chunk's own
+//           rows, or a row of an earlier chunk of the group.  The ring is neither written nor read where the group
+//           will append (k_relpos_chunks_append does that afterwards); no packed output.
+template <bool CHUNKS>
+__device__ __forceinline__ void relpos_body(const float* qkv, int ldq, float* kr, float* vr, int cap, size_t rb, int st,
+                                            int Lold, int ps, size_t row0, int jc, int B, const float* ptab,
+                                            const float* bu, const float* bv, int T, int h, int dk, float scale,
+                                            float* out, int ldo, uint16_t* oph, uint16_t* opl, int prb) {
   extern __shared__ float smem[];
   const int KP = dk + 4;  // padded rows: lanes on consecutive keys hit distinct banks
   float* k_s = smem;                  // [cap][KP]
@@ -593,14 +601,11 @@ __global__ __launch_bounds__(256) void k_relpos_fused(const float* qkv, int ldq,
   float* sc = qv + T * dk;            // [T][cap]
   const int b = blockIdx.x, hh = blockIdx.y;
   const int d = h * dk;
-  const size_t rb = ring ? (size_t)ring[b] : (size_t)b;
-  const int Lold = len[b], Lk = Lold + T;
-  const int st = start[b];
-  const int ps = pstart[b];
+  const int Lk = Lold + T;
   const int D4 = dk / 4;
+  typedef float v4f __attribute__((ext_vector_type(4)));   // (a native vector: the arrays stay in VGPRs)
   // staging: each thread's key / value / position rows (up to RB_ per batch) are all loaded before any of them
-  // is stored to LDS -- one dependent memory round trip per batch instead of one per row (a chunk's new rows come
-  // from the q|k|v output through the same branch-free loads and are then appended to the ring)
+  // is stored to LDS -- one dependent memory round trip per batch instead of one per row
   constexpr int RB_ = 8;
   // the chunk's query rows (+ the u / v position biases), at most 2 per thread, ride in the first batch
   float qx[2], qbu[2], qbv[2];
@@ -608,23 +613,47 @@ __global__ __launch_bounds__(256) void k_relpos_fused(const float* qkv, int ldq,
   for (int r = 0; r < 2; ++r) {
     const int e = threadIdx.x + r * 256;
     const int i = e < T * dk ? e / dk : 0, c = e < T * dk ? e % dk : 0;
-    qx[r] = qkv[((size_t)b * T + i) * ldq + hh * dk + c];
+    qx[r] = qkv[(row0 + i) * ldq + hh * dk + c];
     qbu[r] = bu[hh * dk + c];
     qbv[r] = bv[hh * dk + c];
   }
   for (int e0 = 0; e0 < Lk * D4; e0 += RB_ * 256) {
-    typedef float v4f __attribute__((ext_vector_type(4)));   // (a native vector: the arrays stay in VGPRs)
     v4f kk[RB_], vv[RB_], pp[RB_];
 #pragma unroll
     for (int q = 0; q < RB_; ++q) {
       const int e = e0 + q * 256 + threadIdx.x;
       const bool on = e < Lk * D4;
       const int j = on ? e / D4 : 0, c = on ? (e % D4) * 4 : 0;
-      const bool old_row = j < Lold;
-      const size_t ro = (rb * cap + (st + j) % cap) * d + hh * dk + c;
-      const float* src = qkv + ((size_t)b * T + (old_row ? 0 : j - Lold)) * ldq + hh * dk + c;
-      kk[q] = *reinterpret_cast<const v4f*>(old_row ? kr + ro : src + d);
-      vv[q] = *reinterpret_cast<const v4f*>(old_row ? vr + ro : src + 2 * d);
+      if constexpr (CHUNKS) {
+        // row j of the context: the chunk's own (j >= Lold), one an earlier chunk of this launch appended (age <
+        // jc * T), or one in the ring from before the launch
+        const int age = Lold - 1 - j;
+        const float* src;
+        const float* ksrc;
+        const float* vsrc;
+        if (j >= Lold) {
+          src = qkv + (row0 + (j - Lold)) * ldq + hh * dk + c;
+          ksrc = src + d;
+          vsrc = src + 2 * d;
+        } else if (age < jc * T) {
+          const int jj = jc - 1 - age / T, t = T - 1 - age % T;
+          src = qkv + (((size_t)jj * B + b) * T + t) * ldq + hh * dk + c;
+          ksrc = src + d;
+          vsrc = src + 2 * d;
+        } else {
+          const size_t ro = (rb * cap + (st + j) % cap) * d + hh * dk + c;
+          ksrc = kr + ro;
+          vsrc = vr + ro;
+        }
+        kk[q] = *reinterpret_cast<const v4f*>(ksrc);
+        vv[q] = *reinterpret_cast<const v4f*>(vsrc);
+      } else {   // branch-free: the chunk's new rows come from the q|k|v output through the same loads
+        const bool old_row = j < Lold;
+        const size_t ro = (rb * cap + (st + j) % cap) * d + hh * dk + c;
+        const float* src = qkv + (row0 + (old_row ? 0 : j - Lold)) * ldq + hh * dk + c;
+        kk[q] = *reinterpret_cast<const v4f*>(old_row ? kr + ro : src + d);
+        vv[q] = *reinterpret_cast<const v4f*>(old_row ? vr + ro : src + 2 * d);
+      }
       pp[q] = *reinterpret_cast<const v4f*>(ptab + (size_t)(ps + j) * d + hh * dk + c);
     }
 #pragma unroll
@@ -632,10 +661,12 @@ __global__ __launch_bounds__(256) void k_relpos_fused(const float* qkv, int ldq,
       const int e = e0 + q * 256 + threadIdx.x;
       if (e < Lk * D4) {
         const int j = e / D4, c = (e % D4) * 4;
-        if (j >= Lold) {   // the chunk's new rows enter the ring
-          const size_t ro = (rb * cap + (st + j) % cap) * d + hh * dk + c;
-          *reinterpret_cast<v4f*>(kr + ro) = kk[q];
-          *reinterpret_cast<v4f*>(vr + ro) = vv[q];
+        if constexpr (!CHUNKS) {
+          if (j >= Lold) {   // the chunk's new rows enter the ring
+            const size_t ro = (rb * cap + (st + j) % cap) * d + hh * dk + c;
+            *reinterpret_cast<v4f*>(kr + ro) = kk[q];
+            *reinterpret_cast<v4f*>(vr + ro) = vv[q];
+          }
         }
         *reinterpret_cast<v4f*>(k_s + j * KP + c) = kk[q];
         *reinterpret_cast<v4f*>(v_s + j * KP + c) = vv[q];
@@ -653,7 +684,7 @@ __global__ __launch_bounds__(256) void k_relpos_fused(const float* qkv, int ldq,
   }
   for (int e = threadIdx.x + 512; e < T * dk; e += blockDim.x) {   // (T * dk > 512: not used at dk 64, T <= 8)
     const int i = e / dk, c = e % dk;
-    const float x = qkv[((size_t)b * T + i) * ldq + hh * dk + c];
+    const float x = qkv[(row0 + i) * ldq + hh * dk + c];
     qu[i * dk + c] = x + bu[hh * dk + c];
     qv[i * dk + c] = x + bv[hh * dk + c];
   }
@@ -695,156 +726,36 @@ __global__ __launch_bounds__(256) void k_relpos_fused(const float* qkv, int ldq,
     const float* pr = sc + i * cap;
     float acc = 0.f;
     for (int j = 0; j < Lk; ++j) acc += pr[j] * v_s[j * KP + c];
-    out[((size_t)b * T + i) * ldo + hh * dk + c] = acc;
-    if (oph) xpack_store(oph, opl, b * T + i, hh * dk + c, acc, prb);   // the out projection's packed input
+    out[(row0 + i) * ldo + hh * dk + c] = acc;
+    if constexpr (!CHUNKS) {
+      if (oph) xpack_store(oph, opl, (int)row0 + i, hh * dk + c, acc, prb);   // the out projection's packed input
+    }
   }
 }
 
-// k_relpos_fused over C consecutive chunks of the same users in ONE launch (the offline listen's grouped encoder,
-// SpeechEncoderEngine.run(chunks=C)): per (user, head) the chunks run in order, each with its own ring / position
-// metadata (meta[chunk][start B | len B | ring B | pstart B], host_meta after the chunks before it) and the chunk's
-// rows of the group's q|k|v output (chunk-major: row (j * B + b) * T + i).  The ring rows that chunks < j of this
-// launch appended are read from their q|k|v rows, never re-read from the ring this launch writes (so no global
-// write-then-read inside the launch); every chunk still appends its rows to the ring for the launches after it.
-// Chunk j sees exactly the left context the sequential per-chunk launches give it.
-// k_relpos_fused over C consecutive chunks of the same users in ONE launch (the offline listen's grouped encoder,
-// SpeechEncoderEngine.run(chunks=C)): one workgroup per (user, head, chunk), all chunks at once -- chunk j's context is
-// the ring as it was before the launch (meta[chunk][start B | len B | ring B | pstart B]: host_meta after the chunks
-// before it) plus the k / v columns of the earlier chunks' q|k|v rows (chunk-major: row (j * B + b) * T + i), which the
-// group's q|k|v GEMM has already produced; nothing is read from ring slots this launch's appends
-// (k_relpos_chunks_append, the next launch) will write.  Chunk j sees exactly the left context the sequential
-// per-chunk launches give it.
+// Fused ring append + rel-pos attention of one chunk, one work group per (user, head): relpos_body's fused form.
+__global__ __launch_bounds__(256) void k_relpos_fused(const float* qkv, int ldq, float* kr, float* vr, int cap,
+                                                      const int* start, const int* len, const int* ring,
+                                                      const float* ptab, const int* pstart, const float* bu,
+                                                      const float* bv, int T, int h, int dk, float scale, float* out,
+                                                      int ldo, uint16_t* oph, uint16_t* opl, int prb) {
+  const int b = blockIdx.x;
+  relpos_body<false>(qkv, ldq, kr, vr, cap, ring ? (size_t)ring[b] : (size_t)b, start[b], len[b], pstart[b],
+                     (size_t)b * T, 0, 0, ptab, bu, bv, T, h, dk, scale, out, ldo, oph, opl, prb);
+}
+
+// C consecutive chunks of the same users in ONE launch (the offline listen's grouped encoder,
+// SpeechEncoderEngine.run(chunks=C)), one work group per (user, head, chunk), all chunks at once: relpos_body's
+// grouped form with chunk jc's metadata (meta[jc][start B | len B | ring B | pstart B]: host_meta after the chunks
+// before it).  Chunk jc sees exactly the left context the sequential per-chunk launches give it.
 __global__ __launch_bounds__(256) void k_relpos_chunks(const float* qkv, int ldq, float* kr, float* vr, int cap,
                                                        const int* meta, int B, int C, const float* ptab,
                                                        const float* bu, const float* bv, int T, int h, int dk,
                                                        float scale, float* out, int ldo) {
-  extern __shared__ float smem[];
-  const int KP = dk + 4;
-  float* k_s = smem;
-  float* v_s = k_s + cap * KP;
-  float* p_s = v_s + cap * KP;
-  float* qu = p_s + cap * KP;
-  float* qv = qu + T * dk;
-  float* sc = qv + T * dk;
-  const int b = blockIdx.x, hh = blockIdx.y;
-  const int d = h * dk;
-  const int D4 = dk / 4;
-  typedef float v4f __attribute__((ext_vector_type(4)));
-  constexpr int RB_ = 8;
-  {
-    const int jc = blockIdx.z;
-    const int* m = meta + (size_t)jc * 4 * B;
-    const size_t rb = (size_t)m[2 * B + b];
-    const int Lold = m[B + b], Lk = Lold + T;
-    const int st = m[b];
-    const int ps = m[3 * B + b];
-    const size_t row0 = ((size_t)jc * B + b) * T;   // this chunk's first q|k|v row
-    float qx[2], qbu[2], qbv[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int e = threadIdx.x + r * 256;
-      const int i = e < T * dk ? e / dk : 0, c = e < T * dk ? e % dk : 0;
-      qx[r] = qkv[(row0 + i) * ldq + hh * dk + c];
-      qbu[r] = bu[hh * dk + c];
-      qbv[r] = bv[hh * dk + c];
-    }
-    for (int e0 = 0; e0 < Lk * D4; e0 += RB_ * 256) {
-      v4f kk[RB_], vv[RB_], pp[RB_];
-#pragma unroll
-      for (int q = 0; q < RB_; ++q) {
-        const int e = e0 + q * 256 + threadIdx.x;
-        const bool on = e < Lk * D4;
-        const int j = on ? e / D4 : 0, c = on ? (e % D4) * 4 : 0;
-        // row j of the context: the chunk's own (j >= Lold), one an earlier chunk of this launch appended (age <
-        // jc * T), or one in the ring from before the launch
-        const int age = Lold - 1 - j;
-        const float* src;
-        const float* ksrc;
-        const float* vsrc;
-        if (j >= Lold) {
-          src = qkv + (row0 + (j - Lold)) * ldq + hh * dk + c;
-          ksrc = src + d;
-          vsrc = src + 2 * d;
-        } else if (age < jc * T) {
-          const int jj = jc - 1 - age / T, t = T - 1 - age % T;
-          src = qkv + (((size_t)jj * B + b) * T + t) * ldq + hh * dk + c;
-          ksrc = src + d;
-          vsrc = src + 2 * d;
-        } else {
-          const size_t ro = (rb * cap + (st + j) % cap) * d + hh * dk + c;
-          ksrc = kr + ro;
-          vsrc = vr + ro;
-        }
-        kk[q] = *reinterpret_cast<const v4f*>(ksrc);
-        vv[q] = *reinterpret_cast<const v4f*>(vsrc);
-        pp[q] = *reinterpret_cast<const v4f*>(ptab + (size_t)(ps + j) * d + hh * dk + c);
-      }
-#pragma unroll
-      for (int q = 0; q < RB_; ++q) {
-        const int e = e0 + q * 256 + threadIdx.x;
-        if (e < Lk * D4) {
-          const int j = e / D4, c = (e % D4) * 4;
-          *reinterpret_cast<v4f*>(k_s + j * KP + c) = kk[q];
-          *reinterpret_cast<v4f*>(v_s + j * KP + c) = vv[q];
-          *reinterpret_cast<v4f*>(p_s + j * KP + c) = pp[q];
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int e = threadIdx.x + r * 256;
-      if (e < T * dk) {
-        qu[e] = qx[r] + qbu[r];
-        qv[e] = qx[r] + qbv[r];
-      }
-    }
-    for (int e = threadIdx.x + 512; e < T * dk; e += blockDim.x) {
-      const int i = e / dk, c = e % dk;
-      const float x = qkv[(row0 + i) * ldq + hh * dk + c];
-      qu[i * dk + c] = x + bu[hh * dk + c];
-      qv[i * dk + c] = x + bv[hh * dk + c];
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < T * Lk; e += blockDim.x) {
-      const int i = e / Lk, j = e % Lk;
-      const float* kk = k_s + j * KP;
-      const float* pp = p_s + j * KP;
-      const float* a1 = qu + i * dk;
-      const float* a2 = qv + i * dk;
-      float s1 = 0.f, s2 = 0.f;
-      for (int c = 0; c < dk; c += 4) {
-        const float4 k4 = *reinterpret_cast<const float4*>(kk + c), p4 = *reinterpret_cast<const float4*>(pp + c);
-        const float4 u4 = *reinterpret_cast<const float4*>(a1 + c), w4 = *reinterpret_cast<const float4*>(a2 + c);
-        s1 += u4.x * k4.x + u4.y * k4.y + u4.z * k4.z + u4.w * k4.w;
-        s2 += w4.x * p4.x + w4.y * p4.y + w4.z * p4.z + w4.w * p4.w;
-      }
-      sc[i * cap + j] = (s1 + s2) * scale;
-    }
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int i = wave; i < T; i += blockDim.x / 64) {
-      float mx = -INFINITY;
-      for (int j = lane; j < Lk; j += 64) mx = fmaxf(mx, sc[i * cap + j]);
-      mx = wave_max(mx);
-      float sum = 0.f;
-      for (int j = lane; j < Lk; j += 64) {
-        const float e = expf(sc[i * cap + j] - mx);
-        sc[i * cap + j] = e;
-        sum += e;
-      }
-      sum = wave_sum(sum);
-      const float r = 1.f / sum;
-      for (int j = lane; j < Lk; j += 64) sc[i * cap + j] *= r;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < T * dk; e += blockDim.x) {
-      const int i = e / dk, c = e % dk;
-      const float* pr = sc + i * cap;
-      float acc = 0.f;
-      for (int j = 0; j < Lk; ++j) acc += pr[j] * v_s[j * KP + c];
-      out[(row0 + i) * ldo + hh * dk + c] = acc;
-    }
-  }
+  const int b = blockIdx.x, jc = blockIdx.z;
+  const int* m = meta + (size_t)jc * 4 * B;
+  relpos_body<true>(qkv, ldq, kr, vr, cap, (size_t)m[2 * B + b], m[b], m[B + b], m[3 * B + b],
+                    ((size_t)jc * B + b) * T, jc, B, ptab, bu, bv, T, h, dk, scale, out, ldo, nullptr, nullptr, 0);
 }
 
 // The ring appends of a listen group's C chunks, after k_relpos_chunks has read the ring: chunk j's T rows (k, v
@@ -892,12 +803,50 @@ thread_local uint16_t* g_oph = nullptr;
 thread_local uint16_t* g_opl = nullptr;
 thread_local int g_op_cols = 0, g_op_rb = 0;
 
+// The armed packed output, taken and disarmed: the launch that takes it consumes it whatever happens.
+struct OPack {
+  uint16_t *hi, *lo;
+  int cols, rb;
+};
+inline OPack take_opack() {
+  const OPack o{g_oph, g_opl, g_op_cols, g_op_rb};
+  g_oph = g_opl = nullptr;
+  g_op_cols = g_op_rb = 0;
+  return o;
+}
+
+// Dynamic LDS of relpos_body: k_s / v_s / p_s [cap][dk + 4], qu / qv [T][dk], sc [T][cap] floats; refused for the
+// entry `fn` past 160 KiB.
+inline int relpos_lds(const char* fn, int cap, int T, int dk, size_t* lds) {
+  *lds = (size_t)(3 * cap * (dk + 4) + 2 * T * dk + T * cap) * sizeof(float);
+  FO_REQUIRE(*lds <= 160 * 1024, "%s: ring of %d x %d exceeds LDS", fn, cap, dk);
+  return 0;
+}
+
 // the launch counters of the FP8 KV cache (fo_kv8_counts): fo_kv8_append, fo_attention_kv8
 std::atomic<long long> g_kv8_launches[2];
 
 inline int grid_for(long long n) {
   long long g = (n + 255) / 256;
   return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
+}
+
+// The multi-row launch over a cache of KVB-byte elements (4: fp32, 2: bf16, 1: e4m3): 8 waves at head dim 128, with
+// two row tiles past 16 query rows; 4 waves at 64 and 32.
+template <int KVB>
+void launch_rows(int hd, int max_rows, dim3 grid, const AttnArgs& a, hipStream_t s) {
+  if (hd == 128 && max_rows > 16) hipLaunchKernelGGL((k_attn_mfma<128, 8, 2, false, KVB>), grid, dim3(512), 0, s, a);
+  else if (hd == 128) hipLaunchKernelGGL((k_attn_mfma<128, 8, 1, false, KVB>), grid, dim3(512), 0, s, a);
+  else if (hd == 64) hipLaunchKernelGGL((k_attn_mfma<64, 4, 1, false, KVB>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((k_attn_mfma<32, 4, 1, false, KVB>), grid, dim3(256), 0, s, a);
+}
+
+// The single-row decode launch over a cache of KVB-byte elements (4: fp32, 2: bf16).
+template <int KVB>
+void launch_decode(int hd, dim3 grid, const AttnArgs& a, hipStream_t s) {
+  if (hd == 128) hipLaunchKernelGGL((k_attn_decode<128, KVB>), grid, dim3(DEC_NT), 0, s, a);
+  else if (hd == 64) hipLaunchKernelGGL((k_attn_decode<64, KVB>), grid, dim3(DEC_NT), 0, s, a);
+  else hipLaunchKernelGGL((k_attn_decode<32, KVB>), grid, dim3(DEC_NT), 0, s, a);
 }
 
 }  // namespace
@@ -1006,24 +955,24 @@ static int attention_any(const char* fn, const float* q, int T, const int* items
                          const float* ks, const float* vs, int H, int KVH, int hd, float scale, int nsplit,
                          float* part_ml, float* part_o, float* out, int* tickets, int keys_per_split, int kv_bytes,
                          bool kv8, hipStream_t s) {
-  uint16_t *oph = g_oph, *opl = g_opl;   // the armed packed output is consumed by this launch whatever happens
-  const int op_cols = g_op_cols, op_rb = g_op_rb;
-  g_oph = g_opl = nullptr;
-  g_op_cols = g_op_rb = 0;
+  const OPack op = take_opack();
   FO_REQUIRE(T > 0 && n_items > 0 && KVH > 0 && H % KVH == 0, "%s: bad shape", fn);
-  FO_REQUIRE(!oph || (op_cols == H * hd && op_rb * 16 >= T),
-             "%s: packed output of %d columns x %d row blocks armed for %d x %d tokens", fn, op_cols, op_rb,
+  FO_REQUIRE(!op.hi || (op.cols == H * hd && op.rb * 16 >= T),
+             "%s: packed output of %d columns x %d row blocks armed for %d x %d tokens", fn, op.cols, op.rb,
              H * hd, T);
   FO_REQUIRE(items || T % n_items == 0, "%s: items NULL needs T / n_items tokens per item", fn);
   FO_REQUIRE(hd == 32 || hd == 64 || hd == 128, "%s: head_dim %d unsupported", fn, hd);
   FO_REQUIRE(kv8 || kv_bytes == 4 || kv_bytes == 2, "%s: kv_bytes %d (4 = fp32, 2 = bf16)", fn, kv_bytes);
   FO_REQUIRE(!kv8 || (kc && vc && ks && vs), "%s: NULL codes or scales", fn);
   FO_REQUIRE(PS > 0, "%s: page size %d", fn, PS);
-  const bool kv16 = kv_bytes != 4;   // (narrow: the forms below exist for an fp32 cache only)
-  // forms without a bf16 instantiation are refused by name, never run on the wrong element size
+  const bool kv16 = kv_bytes != 4;   // (narrow: bf16 or e4m3)
+  // The multi-row forms built for an fp32 cache only -- the 4-wave and the traced one here, the 2-wave one at the rows
+  // launch below -- are each named beside the refusal that keeps a narrow cache off them (by name, for every launch
+  // of the entry: never run on the wrong element size); the rows launch picks among them before the common ladder.
+  const bool nw4 = hd == 128 && attn_waves() == 4;                        // k_attn_mfma<128>
+  const bool traced = g_attn_trc && hd == 128 && !nw4 && max_rows <= 16;  // k_attn_mfma<128, 8, 1, true>
   FO_REQUIRE(!kv16 || !g_attn_trc, "%s: the traced launches (fo_attention_set_trace) read an fp32 cache only", fn);
-  FO_REQUIRE(!kv16 || hd != 128 || attn_waves() == 8,
-             "%s: FO_ATTN_NW=4 at head_dim 128 (k_attn_mfma<128, 4>) reads an fp32 cache only", fn);
+  FO_REQUIRE(!kv16 || !nw4, "%s: FO_ATTN_NW=4 at head_dim 128 (k_attn_mfma<128, 4>) reads an fp32 cache only", fn);
   // up to 32 query rows per item on the 8-wave head-dim-128 kernel (two row tiles share every K / V load: a duplex
   // tick's 4 tokens x 7 query heads per kv head read the session's keys once, not twice), 16 elsewhere
   const int rows_max = attn_max_rows(hd);
@@ -1035,7 +984,7 @@ static int attention_any(const char* fn, const float* q, int T, const int* items
   FO_REQUIRE(!tickets || nsplit == 1 || (long long)T * H * nsplit * hd * 4 < (1ll << 31),
              "%s: %d tokens x %d heads x %d splits of partials exceed the merge's 2 GiB window", fn, T, H, nsplit);
   AttnArgs a{q, items, tok_nvis, block_table, kc, vc, part_ml, part_o, out, H, KVH, PS, maxb, nsplit, scale,
-             tickets, keys_per_split, items ? 1 : T / n_items, oph, opl, (T + 15) / 16, g_attn_trc,
+             tickets, keys_per_split, items ? 1 : T / n_items, op.hi, op.lo, (T + 15) / 16, g_attn_trc,
              g_attn_trc && getenv("FO_ATTN_TRACE_REPS") ? atoi(getenv("FO_ATTN_TRACE_REPS")) : 1, ks, vs};
   const bool dec = max_rows == 1 && (long long)maxb * PS <= DEC_MAXK;
   FO_REQUIRE(!a.oph || (T <= 64 && (dec || nsplit == 1 || tickets)),
@@ -1044,12 +993,8 @@ static int attention_any(const char* fn, const float* q, int T, const int* items
                            "FP8 form (the AR speech decoder's cache stays fp32)", fn);
   if (dec) {  // one query row per (session, head): decode kernel
     dim3 g1(n_items, H);
-    if (kv16 && hd == 128) hipLaunchKernelGGL((k_attn_decode<128, 2>), g1, dim3(DEC_NT), 0, s, a);
-    else if (kv16 && hd == 64) hipLaunchKernelGGL((k_attn_decode<64, 2>), g1, dim3(DEC_NT), 0, s, a);
-    else if (kv16) hipLaunchKernelGGL((k_attn_decode<32, 2>), g1, dim3(DEC_NT), 0, s, a);
-    else if (hd == 128) hipLaunchKernelGGL((k_attn_decode<128>), g1, dim3(DEC_NT), 0, s, a);
-    else if (hd == 64) hipLaunchKernelGGL((k_attn_decode<64>), g1, dim3(DEC_NT), 0, s, a);
-    else hipLaunchKernelGGL((k_attn_decode<32>), g1, dim3(DEC_NT), 0, s, a);
+    if (kv16) launch_decode<2>(hd, g1, a, s);
+    else launch_decode<4>(hd, g1, a, s);
     fo::count_launch(FO_L_ATTN_DECODE);
     if (a.oph) fo::count_launch(FO_L_ATTN_OPACK);
     return fo::check_launch("fo_attention/decode");
@@ -1064,7 +1009,7 @@ static int attention_any(const char* fn, const float* q, int T, const int* items
   if (gqa_dec) {
     if (kv8) hipLaunchKernelGGL((k_attn_gqa_decode<128, 1>), grid, dim3(DEC_NT), 0, s, a);
     else if (kv16) hipLaunchKernelGGL((k_attn_gqa_decode<128, 2>), grid, dim3(DEC_NT), 0, s, a);
-    else hipLaunchKernelGGL((k_attn_gqa_decode<128>), grid, dim3(DEC_NT), 0, s, a);
+    else hipLaunchKernelGGL((k_attn_gqa_decode<128, 4>), grid, dim3(DEC_NT), 0, s, a);
     fo::count_launch(FO_L_ATTN_GQA_DECODE);
     if (kv8) g_kv8_launches[1].fetch_add(1, std::memory_order_relaxed);
     if (a.oph) fo::count_launch(FO_L_ATTN_OPACK);
@@ -1072,27 +1017,16 @@ static int attention_any(const char* fn, const float* q, int T, const int* items
   }
   // splits under 64 keys (the text step's short contexts spread over more CUs: a split's K / V arrive at one CU's
   // memory parallelism) take the 2-wave form with 32-key tiles
-  const bool small = hd == 128 && tickets && keys_per_split < 64 && max_rows <= 16 && !a.trc;
+  const bool small = hd == 128 && tickets && keys_per_split < 64 && max_rows <= 16 && !a.trc;   // k_attn_mfma<128, 2>
   FO_REQUIRE(!kv16 || !small, "%s: keys_per_split %d takes the 2-wave form (k_attn_mfma<128, 2>), which reads "
                               "an fp32 cache only; a bf16 or FP8 cache needs >= 64", fn, keys_per_split);
-  if (kv8) {
-    if (hd == 128 && max_rows > 16) hipLaunchKernelGGL((k_attn_mfma<128, 8, 2, false, 1>), grid, dim3(512), 0, s, a);
-    else if (hd == 128) hipLaunchKernelGGL((k_attn_mfma<128, 8, 1, false, 1>), grid, dim3(512), 0, s, a);
-    else if (hd == 64) hipLaunchKernelGGL((k_attn_mfma<64, 4, 1, false, 1>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_attn_mfma<32, 4, 1, false, 1>), grid, dim3(256), 0, s, a);
-    g_kv8_launches[1].fetch_add(1, std::memory_order_relaxed);
-  } else if (kv16) {
-    if (hd == 128 && max_rows > 16) hipLaunchKernelGGL((k_attn_mfma<128, 8, 2, false, 2>), grid, dim3(512), 0, s, a);
-    else if (hd == 128) hipLaunchKernelGGL((k_attn_mfma<128, 8, 1, false, 2>), grid, dim3(512), 0, s, a);
-    else if (hd == 64) hipLaunchKernelGGL((k_attn_mfma<64, 4, 1, false, 2>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_attn_mfma<32, 4, 1, false, 2>), grid, dim3(256), 0, s, a);
-  } else if (small) hipLaunchKernelGGL((k_attn_mfma<128, 2>), grid, dim3(128), 0, s, a);
-  else if (hd == 128 && attn_waves() == 8 && max_rows > 16) hipLaunchKernelGGL((k_attn_mfma<128, 8, 2>), grid, dim3(512), 0, s, a);
-  else if (hd == 128 && attn_waves() == 8 && a.trc) hipLaunchKernelGGL((k_attn_mfma<128, 8, 1, true>), grid, dim3(512), 0, s, a);
-  else if (hd == 128 && attn_waves() == 8) hipLaunchKernelGGL((k_attn_mfma<128, 8>), grid, dim3(512), 0, s, a);
-  else if (hd == 128) hipLaunchKernelGGL((k_attn_mfma<128>), grid, dim3(256), 0, s, a);
-  else if (hd == 64) hipLaunchKernelGGL((k_attn_mfma<64>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((k_attn_mfma<32>), grid, dim3(256), 0, s, a);
+  if (small) hipLaunchKernelGGL((k_attn_mfma<128, 2>), grid, dim3(128), 0, s, a);
+  else if (traced) hipLaunchKernelGGL((k_attn_mfma<128, 8, 1, true>), grid, dim3(512), 0, s, a);
+  else if (nw4) hipLaunchKernelGGL((k_attn_mfma<128>), grid, dim3(256), 0, s, a);
+  else if (kv8) launch_rows<1>(hd, max_rows, grid, a, s);
+  else if (kv16) launch_rows<2>(hd, max_rows, grid, a, s);
+  else launch_rows<4>(hd, max_rows, grid, a, s);
+  if (kv8) g_kv8_launches[1].fetch_add(1, std::memory_order_relaxed);
   fo::count_launch(FO_L_ATTN_MFMA);
   if (a.oph) fo::count_launch(FO_L_ATTN_OPACK);
   int rc = fo::check_launch("fo_attention/rows");
@@ -1158,20 +1092,17 @@ int fo_relpos_attention_fused(const float* qkv, int ldq, float* kr, float* vr, i
                               const int* len, const int* ring, const float* ptab, const int* pstart, const float* bu,
                               const float* bv, int B, int T, int h, int dk, float scale, float* out, int ldo,
                               hipStream_t s) {
-  uint16_t *oph = g_oph, *opl = g_opl;   // consumed by this launch whatever happens
-  const int op_cols = g_op_cols, op_rb = g_op_rb;
-  g_oph = g_opl = nullptr;
-  g_op_cols = g_op_rb = 0;
-  FO_REQUIRE(!oph || (op_cols == h * dk && op_rb * 16 >= B * T),
-             "fo_relpos_attention_fused: packed output of %d columns x %d row blocks armed for %d x %d rows", op_cols,
-             op_rb, h * dk, B * T);
+  const OPack op = take_opack();
+  FO_REQUIRE(!op.hi || (op.cols == h * dk && op.rb * 16 >= B * T),
+             "fo_relpos_attention_fused: packed output of %d columns x %d row blocks armed for %d x %d rows", op.cols,
+             op.rb, h * dk, B * T);
   FO_REQUIRE(T >= 1 && T <= cap && dk % 4 == 0 && (ldq % 4) == 0, "fo_relpos_attention_fused: T=%d dk=%d", T, dk);
-  const size_t lds = (size_t)(3 * cap * (dk + 4) + 2 * T * dk + T * cap) * sizeof(float);
-  FO_REQUIRE(lds <= 160 * 1024, "fo_relpos_attention_fused: ring of %d x %d exceeds LDS", cap, dk);
+  size_t lds;
+  if (int rc = relpos_lds("fo_relpos_attention_fused", cap, T, dk, &lds)) return rc;
   hipLaunchKernelGGL(k_relpos_fused, dim3(B, h), dim3(256), lds, s, qkv, ldq, kr, vr, cap, start, len, ring, ptab,
-                     pstart, bu, bv, T, h, dk, scale, out, ldo, oph, opl, (B * T + 15) / 16);
+                     pstart, bu, bv, T, h, dk, scale, out, ldo, op.hi, op.lo, (B * T + 15) / 16);
   fo::count_launch(FO_L_RELPOS);
-  if (oph) fo::count_launch(FO_L_ATTN_OPACK);
+  if (op.hi) fo::count_launch(FO_L_ATTN_OPACK);
   return fo::check_launch("fo_relpos_attention_fused");
 }
 
@@ -1181,8 +1112,8 @@ int fo_relpos_attention_chunks(const float* qkv, int ldq, float* kr, float* vr, 
   FO_REQUIRE(B >= 1 && C >= 1 && T >= 1 && T <= cap && dk % 4 == 0 && (ldq % 4) == 0,
              "fo_relpos_attention_chunks: B=%d C=%d T=%d dk=%d", B, C, T, dk);
   FO_REQUIRE(C * T <= cap, "fo_relpos_attention_chunks: %d chunks of %d frames exceed the ring (%d)", C, T, cap);
-  const size_t lds = (size_t)(3 * cap * (dk + 4) + 2 * T * dk + T * cap) * sizeof(float);
-  FO_REQUIRE(lds <= 160 * 1024, "fo_relpos_attention_chunks: ring of %d x %d exceeds LDS", cap, dk);
+  size_t lds;
+  if (int rc0 = relpos_lds("fo_relpos_attention_chunks", cap, T, dk, &lds)) return rc0;
   hipLaunchKernelGGL(k_relpos_chunks, dim3(B, h, C), dim3(256), lds, s, qkv, ldq, kr, vr, cap, meta, B, C, ptab, bu,
                      bv, T, h, dk, scale, out, ldo);
   fo::count_launch(FO_L_RELPOS);

@@ -178,7 +178,7 @@ enum FoLaunchKind {
   FO_L_ATTN_MFMA = 12,  /* k_attn_mfma */
   FO_L_ATTN_DECODE = 13,/* k_attn_decode */
   FO_L_ATTN_OPACK = 14, /* an attention launch that wrote packed output */
-  FO_L_RELPOS = 15,     /* k_relpos_fused */
+  FO_L_RELPOS = 15,     /* k_relpos_fused, k_relpos_chunks (one body, relpos_body) */
   FO_L_SUBSAMPLE = 16,  /* fo_subsample: the encoder front end (conv1 stencil + conv2 implicit GEMM + transpose) */
   FO_L_ATTN_O = 17,     /* k_attn_decode_o: decode attention + o projection + residual + next-norm statistics */
   FO_L_ENC_BLOCK = 18,  /* k_enc_attn_block: the attention half of a speech-encoder block */

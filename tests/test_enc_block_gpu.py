@@ -109,7 +109,7 @@ def test_enc_attn_block_refuses_unsupported_geometry(dev):
 
 
 @pytest.mark.parametrize("dk,h,cap,T,C,B", [(64, 16, 72, 4, 4, 8), (8, 4, 16, 4, 4, 3), (64, 16, 72, 7, 3, 2),
-                                             (8, 4, 16, 4, 2, 2)])
+                                             (8, 4, 16, 4, 2, 2), (64, 2, 72, 9, 2, 2)])
 def test_relpos_chunks_equals_sequential_chunk_launches(dev, dk, h, cap, T, C, B):
     """fo_relpos_attention_chunks (a listen group's encoder attention: one workgroup per (user, head, chunk), earlier
     chunks' K / V from the q|k|v rows, the ring appends in a second launch) against C sequential
@@ -122,7 +122,7 @@ def test_relpos_chunks_equals_sequential_chunk_launches(dev, dk, h, cap, T, C, B
 
     from fo import ops
     d = h * dk
-    buffersize = cap - 8
+    buffersize = cap - max(8, T)     # (a full ring and the chunk fit the ring: the kernels stage len + T <= cap rows)
     g = torch.Generator().manual_seed(dk * 100 + C)
     nb_slots = B + 2
     for L0 in (buffersize, 5, 0):
